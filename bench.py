@@ -11,7 +11,22 @@ device.  N>1: one process per GPU (torch.distributed, RCCL); frames are
 partitioned by global frame id (weak scaling, no data-path collective); the
 only collectives are the SUM of the BER counters and the MAX of the step time.
 
-BER match: the `cpu_baseline` leg runs the float64 oracle on the bench's own
+A plain run does only what the headline figure needs: it builds the plan,
+warms up, times `--steps` steps and prints the result line (with the roofline
+priced from the HIP-event timers of those same steps and the committed PMC
+summaries: no run of its own).  `--full` adds the legs that take time of their
+own: the CPU baseline before the GPU is initialised, the BER match and the
+decoder's access-shape ceiling after the timed region (`cpu_baseline`,
+`ber_match` and `roofline.hbm_row_stream.shape_ceiling` / `store_cost` of the
+line; null / the stored figures in a plain run).
+
+`--dump-outputs DIR` writes what the last timed step's `plan.run` returned on
+rank 0 (`counts`, `frame_errors`, `crc_ok` for the coded configs) as
+DIR/<name>.npy in float64 (rank r > 0: DIR/<name>.rank<r>.npy).  Every input
+is a Philox draw keyed by (seed, global frame id), so the same arguments give
+the same inputs and two builds can be compared output for output.
+
+BER match (`--full`): the `cpu_baseline` leg runs the float64 oracle on the bench's own
 frames -- frame ids from both ends of rank 0's first timed step, with the
 oracle's restatement of the device's Philox draws (oracle/philox.py) -- and
 after the timed region rank 0 runs the same frame ids through the same plan:
@@ -24,6 +39,7 @@ exits with their status; under a launcher WORLD_SIZE must equal --gpus.
 
 usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|3|4|5] [--frames F]
                        [--precision f64|f32] [--velocity KMH] [--channel awgn|rayleigh_mp]
+                       [--full] [--dump-outputs DIR]
 """
 import argparse
 import json
@@ -270,8 +286,8 @@ def launch_ranks(args, argv):
 
 
 def cpu_seconds(args):
-    """--cpu-seconds, or 15 s (0 under --dry-run unless given)."""
-    if args.no_cpu:
+    """--full only: --cpu-seconds, or 15 s (0 under --dry-run unless given)."""
+    if args.no_cpu or not args.full:
         return 0.0
     if args.cpu_seconds is not None:
         return float(args.cpu_seconds)
@@ -707,6 +723,23 @@ def dry_run_timers(config, el, steps, rank):
     return {k: (f * el * 1e3 * (1 + 0.01 * rank), steps) for k, f in DRY_STAGE_SHARE[config].items()}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, rank=0):
+    """--dump-outputs: the arrays of the last timed step as <name>.npy, float64
+    (rank r > 0: <name>.rank<r>.npy), at most DUMP_MAX_BYTES in all -- a larger
+    array is cut to a fixed, seeded sample of its elements (sorted indices)."""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_MAX_BYTES // 8 // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = np.asarray(a).astype(np.float64)
+        if a.size > cap:
+            idx = np.sort(np.random.RandomState(SEED).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ('' if rank == 0 else f'.rank{rank}') + '.npy'), a)
+
+
 def make_plan(config, args):
     """The bench plan of one config (the same builders the drop-in API uses)."""
     import lte_phy
@@ -746,10 +779,15 @@ def main():
     ap.add_argument('--channel', choices=('awgn', 'rayleigh_mp'), default=None,
                     help='config 5 only: flat CN(0,1) links (default, simulate_spatial_multiplexing\'s default) '
                          'or PedA Rayleigh at --velocity (3 km/h if 0)')
-    ap.add_argument('--cpu-seconds', type=float, default=None)
-    ap.add_argument('--no-cpu', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the legs that take time of their own: the CPU baseline (cpu_baseline), the '
+                         "BER match on its frames (ber_match) and the decoder's access-shape ceiling")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's outputs (counts, frame_errors, crc_ok) as DIR/<name>.npy")
+    ap.add_argument('--cpu-seconds', type=float, default=None, help='--full: seconds of the CPU baseline leg')
+    ap.add_argument('--no-cpu', action='store_true', help='--full: skip the CPU baseline (and the BER match)')
     ap.add_argument('--no-shape-ceiling', action='store_true',
-                    help="skip measuring the decoder's access-shape ceiling on this box after the timed region "
+                    help="--full: skip measuring the decoder's access-shape ceiling on this box after the timed region "
                          '(scripts/turbo_shape_bench F decoder, a child process; N = 1, coded configs)')
     ap.add_argument('--dry-run', action='store_true', help='no GPU: launcher / sharding / reductions only (gloo)')
     argv = sys.argv[1:]
@@ -808,7 +846,7 @@ def main():
         plan = None
         geom = types.SimpleNamespace(**DRY_GEOM[args.config])
         dev_id = f'rank{rank}'
-        step = lambda k: dry_run_counts(D.frame_ids(k, rank, world, F), S, wl['n_bits'])   # noqa: E731
+        step = lambda k: {'counts': dry_run_counts(D.frame_ids(k, rank, world, F), S, wl['n_bits'])}   # noqa: E731
     else:
         from lte_phy import _capi as C
         C.device_init(local)
@@ -821,7 +859,7 @@ def main():
         def step(k):
             ids = D.frame_ids(k, rank, world, F)
             si = D.snr_index(ids, S)
-            return plan.run(SNRS[si], snr_index=si, n_snr=S, seed=SEED, frame_ids=ids)['counts']
+            return plan.run(SNRS[si], snr_index=si, n_snr=S, seed=SEED, frame_ids=ids)
 
     def barrier():
         if not args.dry_run:
@@ -838,8 +876,10 @@ def main():
         plan.timing(True)
     barrier()
     t0 = time.perf_counter()
+    last = {}
     for k in range(args.steps):
-        counts += step(k)
+        last = step(k)
+        counts += last['counts']
     barrier()
     el = time.perf_counter() - t0
     tim = {}
@@ -850,6 +890,9 @@ def main():
         # --dry-run: synthetic per-rank kernel timers (exercise the roofline
         # gather; the line is marked dry_run)
         tim = dry_run_timers(args.config, el, args.steps, rank)
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank)
 
     el = D.allreduce_max(el, dist)
     counts = D.allreduce_counts(counts, dist)
@@ -876,7 +919,8 @@ def main():
         workload += f' -- links: Rayleigh PedA at {args.velocity or 3.0:g} km/h'
     metric = METRIC if args.config == 2 else f"LTE subframes/sec ({wl['short']}) at 1/2/4/8 GPU; BER match"
     out = {'metric': metric, 'value': round(value, 1), 'unit': 'subframes/s', 'n_gpus': n_dev,
-           'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(el * 1e3 / args.steps, 3),
+           'steps': args.steps, 'warmup': args.warmup, 'full': args.full,
+           'ms_per_step': round(el * 1e3 / max(args.steps, 1), 3),
            'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None, 'dtype': prec,
            'data': 'synthetic (Philox4x32-10 payload bits, Jakes phases and AWGN generated on the GPU)',
            'config': {'workload': workload, 'bench_config': args.config, 'velocity_kmh': args.velocity,
@@ -891,8 +935,8 @@ def main():
     if rank == 0:
         # BER match on the oracle's sample of this run's own frames (outside the timed region)
         out['ber_match'] = ber_match(plan, cpu, wl['coded']) if plan is not None else None
-        if (not args.no_shape_ceiling and world == 1 and prec == 'f64' and plan is not None and out['roofline']
-                and 'hbm_row_stream' in out['roofline']):
+        if (args.full and not args.no_shape_ceiling and world == 1 and prec == 'f64' and plan is not None
+                and out['roofline'] and 'hbm_row_stream' in out['roofline']):
             same_box_shape_ceiling(out['roofline']['hbm_row_stream'], F)
         if cpu:
             cpu = {k: v for k, v in cpu.items() if k not in ('frames', 'config')}

@@ -82,14 +82,14 @@ def _bench(args, env=None):
 
 
 def test_bench_self_launches_ranks_dry_run():
-    """`bench.py --gpus 2` with no launcher starts 2 ranks itself (torch.distributed.run,
+    """`bench.py --gpus 2 --full` with no launcher starts 2 ranks itself (torch.distributed.run,
     gloo in --dry-run), shards frames by global id and reports the distinct
     devices (here: ranks) and the summed counters of both ranks."""
     import json
     from lte_phy import dist as D
     F, steps = 64, 2
     r = _bench(['--gpus', '2', '--dry-run', '--steps', str(steps), '--warmup', '0', '--frames', str(F),
-                '--cpu-seconds', '0.5'])
+                '--full', '--cpu-seconds', '0.5'])
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     assert len(line) == 1, r.stdout          # one JSON line, rank 0 only
@@ -129,7 +129,7 @@ def test_bench_self_launches_ranks_dry_run():
 
 @pytest.mark.parametrize('config', [4, 5])
 def test_bench_other_configs_dry_run_world2(config):
-    """`bench.py --config 4|5 --gpus 2 --dry-run`: config 5 is the config
+    """`bench.py --config 4|5 --gpus 2 --dry-run --full`: config 5 is the config
     BASELINE names for the 8-GPU sharded grid.  The line sums both ranks'
     counters (each config's own payload size), carries a roofline priced on
     the slowest rank (config 4: the decoder's K7 view; config 5: the dominant
@@ -139,7 +139,7 @@ def test_bench_other_configs_dry_run_world2(config):
     from lte_phy import dist as D
     F, steps = 64, 2
     r = _bench(['--config', str(config), '--gpus', '2', '--dry-run', '--steps', str(steps), '--warmup', '0',
-                '--frames', str(F), '--cpu-seconds', '0.3'])
+                '--frames', str(F), '--full', '--cpu-seconds', '0.3'])
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
     assert len(line) == 1, r.stdout
@@ -187,3 +187,49 @@ def test_merge_timers_takes_slowest_rank():
 def test_bench_rejects_world_size_mismatch():
     r = _bench(['--gpus', '2', '--dry-run', '--steps', '1', '--warmup', '0'], env={'WORLD_SIZE': '1'})
     assert r.returncode == 2 and 'WORLD_SIZE' in r.stderr
+
+
+def _bench_mod():
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(root, 'bench.py'))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_bench_plain_run_is_lean_and_dumps_last_step(tmp_path):
+    """A plain run (no --full) times its steps and nothing else: no CPU baseline
+    (even with --cpu-seconds), no BER match; --steps sets the timed steps and
+    the line carries ms_per_step.  --dump-outputs writes the last timed step's
+    arrays as float64 .npy files, the same from run to run."""
+    import json
+    from lte_phy import dist as D
+    F, steps = 64, 3
+    dumps = []
+    for d in ('a', 'b'):
+        r = _bench(['--gpus', '1', '--dry-run', '--steps', str(steps), '--warmup', '1', '--frames', str(F),
+                    '--cpu-seconds', '5', '--dump-outputs', str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][0])
+        assert out['cpu_baseline'] is None and out['ber_match'] is None and out['full'] is False
+        assert out['steps'] == steps and out['ms_per_step'] > 0 and out['dtype'] == 'f64'
+        assert out['unit'] == 'subframes/s' and out['higher_is_better'] is True
+        assert np.array(out['counts'])[:, 3].sum() == F * steps          # `steps` timed steps, no more
+        assert sorted(os.listdir(tmp_path / d)) == ['counts.npy']
+        dumps.append(np.load(tmp_path / d / 'counts.npy'))
+    assert dumps[0].dtype == np.float64 and np.array_equal(dumps[0], dumps[1])
+    ref = _bench_mod().dry_run_counts(D.frame_ids(steps - 1, 0, 1, F), 16)
+    assert np.array_equal(dumps[0], ref.astype(np.float64))
+
+
+def test_dump_outputs_caps_its_size(tmp_path):
+    b = _bench_mod()
+    b.DUMP_MAX_BYTES = 8 * 100
+    big = np.arange(1000, dtype=np.uint32)
+    for d in ('a', 'b'):
+        b.dump_outputs(str(tmp_path / d), {'big': big, 'small': np.ones(3, dtype=np.uint8)}, rank=0)
+    x, y = np.load(tmp_path / 'a' / 'big.npy'), np.load(tmp_path / 'b' / 'big.npy')
+    assert x.dtype == np.float64 and x.size == 50 and np.array_equal(x, y)     # a fixed, seeded sample
+    assert np.all(np.diff(x) > 0) and set(x) <= set(big.astype(float))
+    assert np.array_equal(np.load(tmp_path / 'a' / 'small.npy'), np.ones(3))
