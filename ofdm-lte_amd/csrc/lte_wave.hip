@@ -634,8 +634,13 @@ bool rx_simo_w_supported(const Grid& g, int num_rx, int f64, bool H, bool pstats
 
 // ---------------------------------------------------------------------------
 // Wave-private uncoded OFDM TX + static-tap SIMO channel (float64, N = 1024:
-// config 3; k_ofdm_tx<.., CH = 1>'s outputs): one wave64 per (frame, OFDM
-// symbol), no block barrier.  Lane c, register q builds bin k = 64 q + c from
+// config 3; k_ofdm_tx<.., CH = 1>'s outputs plus k_chan_fix's): as built
+// (TXSW_HALF and TXSW_FRAME, the defaults) one wave64 per frame walking its
+// OFDM symbols in order, no block barrier; it writes no xh head / tail samples
+// (ChainBufs::xh stays unused on this path) and k_chan_fix does not run after
+// it (tx_simo_w_fuses_fix).  With TXSW_FRAME=0 it is one wave per (frame, OFDM
+// symbol) that leaves xh for k_chan_fix.
+// Per symbol: lane c, register q builds bin k = 64 q + c from
 // Grid::kinfo (a data RE's BPS payload bits -> qam_point, a pilot, or 0);
 // wfft::fft1024<INV> and the output scale give x[64 q + c], which is staged in
 // the wave's LDS (the transform's scratch before) so that every RX's taps read
@@ -650,10 +655,15 @@ bool rx_simo_w_supported(const Grid& g, int num_rx, int f64, bool H, bool pstats
 // staged (16 KB), for four waves per SIMD (120 VGPRs) instead of two and a
 // half (profiles/r6_simo_tx_wave/: 14.1 against 15.5 ms per 65 536 frames).
 // TXSW_FRAME (with TXSW_HALF): one wave per frame walking its symbols, which
-// keeps the previous symbol's last register and so also forms each symbol's
-// first max_delay channel-output samples' power (their taps reach into the
-// previous symbol: k_chan_fix's work, which then does not run) from a tenth
-// window slot.
+// keeps the previous symbol's last register (tailp = x[960 + lane], carried
+// across estimation-group boundaries too; zero before symbol 0) and so also
+// forms each symbol's first max_delay channel-output samples' power (their
+// taps reach into the previous symbol: k_chan_fix's work, which then does not
+// run) from a tenth window slot: lane m < max_delay reads this symbol's
+// x[N - cp + m - d] at xs[576 - cp + m - d] or the previous tail at
+// xs[640 + m - d].  The edges -- max_delay == 64 (every lane), 65 (refused),
+// max_delay == cp, cp = 254 / 253, 8 taps through NP = 0, a 15th symbol -- are
+// pinned against the oracle by tests/test_gpu_profiles.py.
 #ifndef TXSW_HALF
 #define TXSW_HALF 1
 #endif

@@ -290,11 +290,18 @@ def add_noise(y: np.ndarray, snr_db: float, z_re=None, z_im=None):
 
 
 def channel_transmit(num, x, channel, snr_db, profile='Pedestrian_A', fD=0.0,
-                     draws=None):
+                     draws=None, paths=None):
     """ChannelSimulator.transmit (core/channel.py:334-345) for 'awgn' and
-    'rayleigh_mp'.  Draw order: per path rand(16), then normal(L) x 2."""
+    'rayleigh_mp'.  Draw order: per path rand(16), then normal(L) x 2.
+    paths=(integer delays, linear gains) replaces the ITU profile's taps
+    (RayleighChannel takes any tap set, core/rayleighchannel.py:13-18; the
+    plan-level tests feed the GPU the same pair)."""
     if channel == 'rayleigh_mp':
-        dl, g = itu_paths(num, profile)
+        if paths is None:
+            dl, g = itu_paths(num, profile)
+        else:
+            dl = np.array([int(d) for d in paths[0]])
+            g = np.array([float(v) for v in paths[1]])
         if draws is None:
             ph = [2 * np.pi * np.random.rand(16) for _ in range(len(dl))]
         else:
@@ -396,11 +403,13 @@ def receive(num: Numerology, y: np.ndarray, equalize=True, sc_fdm=False):
 
 
 def simulate_siso(num: Numerology, bits, snr_db, channel='awgn',
-                  profile='Pedestrian_A', fD=0.0, draws=None, sc_fdm=False, equalize=True):
+                  profile='Pedestrian_A', fD=0.0, draws=None, sc_fdm=False, equalize=True,
+                  paths=None):
     """OFDMSimulator.simulate_siso (core/ofdm_core.py:660-737).  draws=None
     consumes the global RNG like the reference; else uses the given draws.
     sc_fdm: DFT precoding at TX and IDFT after ZF at RX (SURVEY §8f rank 2);
-    equalize=False: OFDMSimulator(enable_equalization=False), no ZF (:294-299)."""
+    equalize=False: OFDMSimulator(enable_equalization=False), no ZF (:294-299);
+    paths: custom tap set instead of the ITU profile (channel_transmit)."""
     bits = np.asarray(bits)
     if bits.size == 0:
         raise ValueError("Bits array cannot be empty")
@@ -408,7 +417,7 @@ def simulate_siso(num: Numerology, bits, snr_db, channel='awgn',
     sig, syms, n_sym = modulate_stream(num, bits, sc_fdm)
     pa = papr(sig)
     d = None if draws is None else draws[0]
-    rx = channel_transmit(num, sig, channel, snr_db, profile, fD, d)
+    rx = channel_transmit(num, sig, channel, snr_db, profile, fD, d, paths)
     data, brx, _ = receive(num, rx, equalize, sc_fdm)
     if draws is None:
         pass  # reseed already happened inside estimate_channel
@@ -423,12 +432,13 @@ def simulate_siso(num: Numerology, bits, snr_db, channel='awgn',
 
 
 def simulate_simo(num: Numerology, bits, snr_db, num_rx=2, channel='awgn',
-                  profile='Pedestrian_A', fD=0.0, draws=None, sc_fdm=False):
+                  profile='Pedestrian_A', fD=0.0, draws=None, sc_fdm=False, paths=None):
     """OFDMSimulator.simulate_simo (core/ofdm_core.py:1536-1679) with
     transmit_simo (:361-412), _demodulate_with_channel_est (:1340-1403) and
     _combine_symbols_mrc (:1405-1534), hard decision on the MRC output.
     sc_fdm: the transmitter DFT-precodes but this receiver never applies the
-    IDFT (the reference's behaviour, BER ~ 0.5)."""
+    IDFT (the reference's behaviour, BER ~ 0.5).  paths: custom tap set
+    instead of the ITU profile (channel_transmit)."""
     bits = np.asarray(bits)
     n0 = len(bits)
     sig, syms, n_sym = modulate_stream(num, bits, sc_fdm)
@@ -436,7 +446,7 @@ def simulate_simo(num: Numerology, bits, snr_db, num_rx=2, channel='awgn',
     rxs = []
     for r in range(num_rx):
         d = None if draws is None else draws[r]
-        rxs.append(channel_transmit(num, sig, channel, snr_db, profile, fD, d))
+        rxs.append(channel_transmit(num, sig, channel, snr_db, profile, fD, d, paths))
     num_acc = None
     den_acc = None
     for r in range(num_rx):

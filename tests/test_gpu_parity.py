@@ -603,9 +603,12 @@ def test_simo_receiver_rx_pairs_match_sequential(C, monkeypatch, nrx, mod, prec)
                                           (3, 'QPSK', 'Vehicular_A')])
 def test_wave_simo_tx_matches_block_tx(C, monkeypatch, nrx, mod, prof):
     """10 MHz SIMO TX + static taps, float64: the wave-private TX
-    (k_ofdm_tx_simo_w: one wave per (frame, symbol), wfft::fft1024<INV>, the
-    symbol staged in LDS for every RX's taps; the default) against k_ofdm_tx
-    (LTE_SIMO_TX_WAVE=0) on the same frames: identical transmitted symbols;
+    (k_ofdm_tx_simo_w: one wave per frame walking its symbols, wfft::fft1024<INV>,
+    half a symbol at a time in an LDS window for every RX's taps, each symbol's
+    head-sample power formed in the kernel so that k_chan_fix does not run; the
+    default) against k_ofdm_tx + k_chan_fix (LTE_SIMO_TX_WAVE=0) on the same
+    frames (both against the oracle: tests/test_gpu_profiles.py): identical
+    transmitted symbols;
     noise powers and combined symbols to 1e-12 (the transform and the power
     sums differ in round-off only); decisions and counts match (at most 2 flips
     allowed).  4, 2 and 3 RX; 6 and 2 paths."""
