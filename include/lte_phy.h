@@ -202,6 +202,13 @@ int lte_plan_info(const lte_plan *plan, int64_t *info8);
 int lte_plan_precision(const lte_plan *plan);
 /* Run the full chain (TX -> channel -> RX (-> turbo)) for one batch of frames. */
 int lte_run(lte_plan *plan, const lte_run_args *args);
+/* Diagnostic, read-only: the kernel path lte_run(plan, args) would take under
+ * the current environment switches, as one "key=value ..." line in buf (cut to
+ * len - 1 characters); returns its length.  Launches and allocates nothing.
+ * SISO / SIMO: tx= tx_stage= ch_fix= rx= xhand= dematch=; multi-antenna: tx=
+ * lp_fuse= ch= link_merge= rx= h_pilots= det_stage= dematch= (ch: fused,
+ * k_channel_mimo or k_channel_tay,J=..,G=..,econ=..). */
+int lte_run_path(const lte_plan *plan, const lte_run_args *args, char *buf, int len);
 /* Per-kernel device time accumulated by lte_run while timing is on (HIP events
  * on the plan's stream).  names: comma-separated kernel names; ms/launches per
  * kernel in the same order.  n_max entries. */

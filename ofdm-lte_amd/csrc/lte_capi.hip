@@ -504,12 +504,6 @@ template <> BfFrameT<double>* bf_frames<double>(lte_plan* p) { return p->bf_fr64
 template <> ChainBufs<float>& cbuf<float>(lte_plan* p) { return p->c32; }
 template <> ChainBufs<double>& cbuf<double>(lte_plan* p) { return p->c64; }
 
-// an on/off switch from the environment (A/B knobs): unset -> def
-bool env_on(const char* name, bool def) {
-  const char* e = std::getenv(name);
-  return e ? std::atoi(e) != 0 : def;
-}
-
 // chunk width of the plan's decoder rows (allocated for ceil(max_frames / 64) groups)
 int turbo_plan_ch(const lte_plan* p) { return turbo_chunk((p->d.max_frames + 63) / 64); }
 
@@ -754,7 +748,8 @@ static int channel_mimo_host(int64_t L, int num_tx, int num_rx, int mode, int ch
                                    (!ray && mode == 1 && link_h) ? dlh.p : nullptr, 0, dcoef.p, dphs.p) == 0;
   const R* lz = (link_noise_on && link_noise) ? dlz.p : nullptr;
   ok = ok && launch_channel_mimo<R>(nullptr, g, m, 1, np, ray ? ddel.p : nullptr, dcoef.p, dphs.p, dgain.p, fs, dx.p,
-                                    dy.p, link_noise_on ? 1 : 0, dfid.p, seed, lz, 0, dlp.p, dls.p, dpp.p, nblk, 0) == 0;
+                                    dy.p, link_noise_on ? 1 : 0, dfid.p, seed, lz, 0, dlp.p, dls.p, dpp.p, nblk,
+                                    channel_mimo_select<R>(m, np, g.N + g.cp, fs, read_knobs()), 0) == 0;
   ok = ok && launch_npow_mimo<R>(nullptr, 1, num_rx, dpp.p, mimo_channel_nblk(g.L, g.N + g.cp), (int)L, dsl.p,
                                  mode == 0 ? (double)num_tx : 1.0, dnp.p) == 0;
   if (ok) {
@@ -1074,7 +1069,7 @@ void lte::plan_txf_lane_order(const std::vector<int32_t>& tx_map, const std::vec
 
 extern "C" {
 
-static int plan_coded_maps(lte_plan* p) {
+static int plan_coded_maps(lte_plan* p, const Knobs& k) {
   const lte_plan_desc& d = p->d;
   if (!segmentation_plan(d.n_bits + 24, p->cbs)) return fail(LTE_EINVAL, "No valid interleaver size");
   p->C = (int)p->cbs.size();
@@ -1164,10 +1159,10 @@ static int plan_coded_maps(lte_plan* p) {
   // instruction but not the kernel time (15.34 ms with it, 15.17 without,
   // DESIGN.md §5 round 4), and its greedy search costs plan-create time on every
   // plan-cache miss.  LTE_TXF_LANE_ORDER=1 turns it on.
-  if (p->res == p->Nd && d.N >= 512 && p->Nd <= d.N / 2 && env_on("LTE_TXF_LANE_ORDER", false)) {
+  if (p->res == p->Nd && d.N >= 512 && p->Nd <= d.N / 2 && k.txf_lane_order) {
     std::vector<int32_t> tfm, tfr;
     plan_txf_lane_order(txm, p->gh.data, p->n_sym, Nd, bps, d.N / 2, tfm, tfr, p->txf_model);
-    if (env_on("LTE_TXF_LANE_ORDER_REPORT", false))
+    if (k.txf_lane_order_report)
       std::fprintf(stderr, "txf lane order: modelled extra LDS cycles per 32-lane gather %.3f (RE order) -> %.3f\n",
                    p->txf_model[0], p->txf_model[1]);
     if (upload(p->txf_map, tfm) || upload(p->txf_re, tfr)) return fail(LTE_ENOMEM, "map upload failed");
@@ -1427,7 +1422,7 @@ int lte_plan_create(const lte_plan_desc* desc, lte_plan** out) {
   // REs per OFDM symbol: SFBC drops an odd last data SC (core/sfbc_alamouti.py:196-200, Q18)
   p->res = sfbc ? (p->Nd & ~1) : p->Nd;
   if (coded) {
-    rc = plan_coded_maps(p);
+    rc = plan_coded_maps(p, read_knobs());
     if (rc) { p->tabs.release(); delete p; return rc; }
     p->PW = (d.n_bits + 24 + 31) / 32 + 1;
   } else {
@@ -1621,11 +1616,197 @@ static R* zn_nv(lte_plan* p) {
   return cbuf<R>(p).llr.p + 2 * (size_t)p->d.max_frames * (p->n_re_bits / p->d.bps);
 }
 
+// ---------------------------------------------------------------------------
+// The run's kernel path: decided once per lte_run from the plan, the run
+// arguments and the switch table (lte_knobs.h); run_siso / run_mimo launch what
+// it says and lte_run_path prints it.  The *_supported functions and the
+// predicates below are the single definition of what is possible; each switch
+// is ANDed in once, here.
+
+// TX with the channel fused in (TxChannelT): SISO / SIMO Rayleigh (SC-FDM
+// precoding included), delays within the CP, no TX / RX stream capture; static
+// taps (fD = 0) or per-symbol Taylor sets while mimo_taylor_ok (3 km/h at
+// 20 MHz: |w| S / 2 = 1.2e-3).
+static bool txch_fusable(const lte_plan* p, const lte_run_args* a) {
+  const lte_plan_desc& d = p->d;
+  if (d.channel != LTE_CH_RAYLEIGH || d.num_rx < 1 || p->mimo || p->bf) return false;
+  if (d.fD != 0.0 && !mimo_taylor_ok(d.fD, d.fs, d.N + d.cp_len)) return false;
+  if (a->in_signal || a->cap_signal_tx || a->cap_signal_rx) return false;
+  return txch_supported(p->grid, d.n_paths, *std::max_element(d.delays, d.delays + d.n_paths));
+}
+
+// Coded TX + channel with one slot per frame (k_ofdm_txf) when its LDS fits
+// (coded streams staged once per frame).
+static bool tx_per_frame(const lte_plan* p) {
+  const int spw = 256 / (p->grid.N >> 3);
+  const size_t el = p->f64 ? 16 : 8;
+  return (size_t)spw * (p->grid.N * el + (size_t)p->enc_words * 4) <= 65536;
+}
+
+// Coded SISO 16/64-QAM without an LLR capture: k_rx_data hands over the
+// equalised symbol and sigma^2_eff per RE and k_dematch_zn demaps while it
+// builds the decoder rows, instead of a round trip of bps LLRs per RE.  The
+// (z, nv) arrays live in the LLR buffer ([max_frames][n_re] z, then
+// [max_frames][n_re] nv: 3 R per RE).
+static bool demap_in_dematch(const lte_plan* p, const lte_run_args* a) {
+  const lte_plan_desc& d = p->d;
+  return d.chain == LTE_CHAIN_CODED && !p->mimo && !p->bf && (d.bps == 4 || d.bps == 6) && !a->cap_llr;
+}
+
+// Fused SISO receiver (k_rx_frame): one RX, coded or uncoded, no SC-FDM.
+static bool rx_fusable(const lte_plan* p) {
+  const lte_plan_desc& d = p->d;
+  return rx_frame_supported(p->grid, d.chain, d.num_rx, (d.sc_fdm && d.chain == LTE_CHAIN_UNCODED) ? 1 : 0);
+}
+// Fused SIMO MRC receiver (k_rx_frame_simo*).
+static bool rx_simo_fusable(const lte_plan* p) {
+  return p->d.chain == LTE_CHAIN_SIMO && rx_frame_simo_supported(p->grid, p->d.num_rx);
+}
+
+// the kernel families, as lte_run_path prints them
+enum SisoTx { TX_NONE, TX_SYM, TX_SYM_CH, TX_FRAME, TX_FRAME_W, TX_SIMO_W };
+static const char* const SISO_TX_NAME[] = {"none", "k_ofdm_tx", "k_ofdm_tx_ch", "k_ofdm_txf", "k_ofdm_txf_w",
+                                           "k_ofdm_tx_simo_w"};
+enum SisoRx { RX_NONE, RX_CHEST_DATA, RX_FRAME, RX_FRAME_W, RX_SIMO, RX_SIMO2, RX_SIMO_W };
+static const char* const SISO_RX_NAME[] = {"none", "k_rx_chest+k_rx_data", "k_rx_frame", "k_rx_frame_w",
+                                           "k_rx_frame_simo", "k_rx_frame_simo2", "k_rx_frame_simo_w"};
+enum MimoTx { MTX_PAIR, MTX_FRAME, MTX_FLAT, MTX_FLAT_PR, MTX_FLAT_W, MTX_SFBC };
+static const char* const MIMO_TX_NAME[] = {"k_ofdm_tx_mimo", "k_ofdm_tx_mimo_frame", "k_ofdm_txch_flat",
+                                           "k_ofdm_txch_flat_pr", "k_ofdm_txch_flat_w", "k_ofdm_txch_sfbc"};
+enum MimoRx { MRX_FFT, MRX_FFT_W, MRX_SFBC };
+static const char* const MIMO_RX_NAME[] = {"k_rx_fft_mimo", "k_rx_fft_mimo_w", "k_rx_sfbc"};
+
+struct SisoPath {
+  SisoTx tx;       // TX_SYM: k_ofdm_tx + k_channel; every other transmitter has the channel fused in
+  bool tx_stage;   // the coded stream staged in LDS
+  bool ch_fix;     // k_chan_fix runs (false: no fused channel, or the TX formed the head power itself)
+  SisoRx rx;
+  bool xhand;      // the TX hands its symbols to the paired receiver (TxChannelT::x_out)
+  bool zn;         // (z, nv) hand-off to k_dematch_zn instead of LLRs
+  bool fused() const { return tx != TX_NONE && tx != TX_SYM; }
+};
+
+struct MimoPath {
+  MimoTx tx;
+  bool lp_fuse;      // MTX_PAIR / MTX_FRAME: transmit_mimo's link power formed by the TX
+  bool ch_sep;       // the channel is its own pass (launch_channel_mimo), described by ch
+  ChanMimoSel ch;
+  bool sfbc_merge;   // MTX_SFBC: the link noise merged into the receiver's draw
+  MimoRx rx;
+  bool h_pilots;     // spatial: LS pilot estimates handed to the detector
+  bool det_stage;    // k_det_spatial stages them in LDS
+  bool zn;
+};
+
+static SisoPath select_siso(const lte_plan* p, const lte_run_args* a, const Knobs& k) {
+  const lte_plan_desc& d = p->d;
+  const Grid& g = p->grid;
+  const bool coded = d.chain == LTE_CHAIN_CODED, tv = d.fD != 0.0;
+  const bool cap_H = a->cap_H != nullptr, cap_ps = a->cap_pilot_stats != nullptr;
+  const int stages = a->stages ? a->stages : LTE_STAGE_ALL, rx = d.num_rx, scf = (d.sc_fdm && !coded) ? 1 : 0;
+  const bool do_tx = stages & LTE_STAGE_TX, do_ch = stages & LTE_STAGE_CHANNEL, do_rx = stages & LTE_STAGE_RX;
+  SisoPath s{};
+  // TX + static-tap channel in one kernel (the received stream is written once)
+  const bool fuse = do_tx && do_ch && k.txch_fuse && txch_fusable(p, a);
+  const int maxd = fuse ? *std::max_element(d.delays, d.delays + d.n_paths) : 0;
+  // receiver: fused (estimation + data path per frame) unless LTE_RX_FUSE=0
+  s.zn = k.demap_in_dematch && demap_in_dematch(p, a);
+  const bool rx_fuse = do_rx && k.rx_fuse;
+  const bool rxf = rx_fuse && rx_fusable(p);
+  const bool rxs = rx_fuse && !rxf && rx_simo_fusable(p);
+  const bool pairs = rxs && k.rxs_pairs && rx_simo2_ok(g, rx, cap_H, cap_ps);
+  s.xhand = fuse && pairs && !tv && k.simo_xhand;
+  if (rxf)
+    s.rx = s.zn && k.rx_wave && rx_frame_w_supported(g, d.chain, p->f64) ? RX_FRAME_W : RX_FRAME;
+  else if (rxs)
+    s.rx = !s.xhand && k.simo_rx_wave && rx_simo_w_supported(g, rx, p->f64, cap_H, cap_ps, false) ? RX_SIMO_W
+           : pairs ? RX_SIMO2 : RX_SIMO;
+  else
+    s.rx = do_rx ? RX_CHEST_DATA : RX_NONE;
+  // transmitter
+  if (!do_tx)
+    s.tx = TX_NONE;
+  else if (!fuse)
+    s.tx = TX_SYM;
+  else if (coded && k.tx_frame && tx_per_frame(p))
+    s.tx = k.tx_wave && !p->txf_map.p && txf_w_supported(g, p->f64, d.n_paths, maxd, rx, tv) ? TX_FRAME_W : TX_FRAME;
+  else
+    s.tx = k.simo_tx_wave && tx_simo_w_supported(g, p->f64, coded, scf, d.n_paths, maxd, rx, tv, s.xhand) ? TX_SIMO_W
+                                                                                                          : TX_SYM_CH;
+  s.tx_stage = s.tx == TX_FRAME ? TXF_STAGE != 0
+               : s.tx == TX_FRAME_W ? k.txw_stage
+               : (s.tx == TX_SYM || s.tx == TX_SYM_CH) && k.tx_stage && tx_stage_supported(g, coded, p->enc_words);
+  // k_ofdm_tx_simo_w built per frame (TXSW_FRAME) forms each symbol's head power itself
+  s.ch_fix = s.fused() && !(s.tx == TX_SIMO_W && TXSW_FRAME);
+  return s;
+}
+
+template <class R>
+static MimoPath select_mimo(const lte_plan* p, const lte_run_args* a, const Knobs& k) {
+  const lte_plan_desc& d = p->d;
+  const Grid& g = p->grid;
+  const MimoGrid& m = p->mg;
+  const bool coded = d.chain == LTE_CHAIN_SFBC_CODED, ray = d.channel == LTE_CH_RAYLEIGH, sfbc = m.mode == MIMO_SFBC;
+  const bool link_noise = sfbc && ray;  // transmit_mimo's per-link 100 dB ChannelSimulator (core/ofdm_core.py:490-503)
+  const bool inj_lz = a->link_noise && link_noise, inj_z = a->noise != nullptr;
+  const int maxd = ray ? *std::max_element(d.delays, d.delays + d.n_paths) : 0;
+  MimoPath s{};
+  // flat links (AWGN: spatial CN(0,1), SFBC exp(j t pi/2)): TX and channel in
+  // one pass per (frame, symbol, RX) -- y_r = IFFT(sum_t h_rt G_t) -- when no
+  // TX-stream capture needs x
+  const bool flat_fuse = !ray && !a->cap_signal_tx && !a->cap_link_stats && (g.N >> 3) >= 64 && m.num_tx <= 4 &&
+                         k.mimo_flat_fuse;
+  // config 4 (SFBC, static-tap Rayleigh links with the 100 dB link noise, Philox
+  // draws): TX and the links' fading in one pass per frame writing the faded RX
+  // signals (k_ofdm_txch_sfbc), then the link noise + RX power (k_link_noise_pairs)
+  // -- x never goes through HBM.  Captures of x / the link statistics and the
+  // reference's own (injected) link noise keep the separate kernels.
+  const bool sfbc_fuse = link_noise && !inj_lz && !inj_z && !a->cap_signal_tx && !a->cap_link_stats &&
+                         sfbc_txch_supported<R>(g, m, d.n_paths, maxd) && k.sfbc_txch_fuse;
+  if (sfbc_fuse)
+    s.tx = MTX_SFBC;
+  else if (flat_fuse)
+    s.tx = k.txch_pr && txch_flat_pr_supported(g, m) ? MTX_FLAT_PR
+           : k.mimo_tx_wave && txch_flat_w_supported(g, m, p->f64) ? MTX_FLAT_W : MTX_FLAT;
+  else
+    s.tx = k.txm_frame && tx_mimo_frame_supported(g, coded, p->enc_words) ? MTX_FRAME : MTX_PAIR;
+  s.ch_sep = s.tx == MTX_PAIR || s.tx == MTX_FRAME;
+  if (s.ch_sep) s.ch = channel_mimo_select<R>(m, ray ? d.n_paths : 1, g.N + g.cp, d.fs, k);
+  // transmit_mimo's link power on the TX symbols in LDS (static taps, N >= 512,
+  // delays within the CP): the channel pass then reads x once
+  s.lp_fuse = s.ch_sep && link_noise && m.n_cs == 1 && !m.exact_jakes && (g.N >> 3) >= 64 && maxd <= g.cp &&
+              d.n_paths <= TXCH_MAXP && k.mimo_lp_fuse;
+  // coded SFBC 16/64-QAM without an LLR capture: the detector hands over the
+  // combined symbols and each RE pair's sigma^2_eff, k_dematch_zn demaps (as
+  // the SISO chain does; LTE_DEMAP_IN_DEMATCH=0 keeps the LLR round trip)
+  s.zn = coded && sfbc && (d.bps == 4 || d.bps == 6) && !a->cap_llr && (m.res & 1) == 0 && m.n_dsc <= m.res &&
+         k.demap_in_dematch;
+  // config 4 (SFBC on Philox draws, zn handoff or uncoded, no capture of the
+  // received grids / estimates / symbols): receiver + detector in one pass
+  // (a capture of the received bits needs the detector's decisions only
+  // uncoded: coded, they come from k_crc_count)
+  const bool rx_fuse = sfbc && !inj_z && !a->cap_H && !a->cap_data_syms && !(a->cap_bits_rx && !coded) &&
+                       (s.zn || !coded) && rx_sfbc_supported<R>(g, m) && k.sfbc_rx_fuse;
+  // the merged link noise (launch_npow_sfbc_merged): the fused TX, then one
+  // noise draw per RX sample in the fused receiver -- only when nothing
+  // observes the received streams or noise powers in between
+  s.sfbc_merge = sfbc_fuse && rx_fuse && !a->cap_signal_rx && !a->cap_noise_power && k.sfbc_link_merge;
+  // spatial multiplexing without a capture of H: the receiver hands over each
+  // estimation symbol's LS pilot estimates and the detector interpolates them
+  // per RE (the same mimo_interp), instead of a round trip of the interpolated
+  // H (num_tx x n_dsc per RX and symbol) through HBM
+  s.h_pilots = !sfbc && !a->cap_H && k.spatial_hp;
+  s.rx = rx_fuse ? MRX_SFBC
+         : k.mimo_rx_wave && rx_fft_mimo_w_supported(g, m, p->f64, s.h_pilots) ? MRX_FFT_W : MRX_FFT;
+  s.det_stage = !sfbc && k.dsp_stage && det_spatial_stage_supported(m, p->f64, g.n_sym, a->n_frames, s.h_pilots);
+  return s;
+}
+
 // Multi-antenna chains (SFBC 2xN, uncoded / coded; TM4 spatial multiplexing)
 // in precision R.
 template <class R>
-static int run_mimo(lte_plan* p, const lte_run_args* a, int B, int n_snr, const std::vector<double>& snr_lin,
-                    const uint32_t* inj_bits, int64_t inj_bits_stride) {
+static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, int B, int n_snr,
+                    const std::vector<double>& snr_lin, const uint32_t* inj_bits, int64_t inj_bits_stride) {
   using V = cx<R>;
   const lte_plan_desc& d = p->d;
   const Grid& g = p->grid;
@@ -1683,39 +1864,15 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, int B, int n_snr, const 
     LCHK(launch_fading_mimo<R>(s, g, m, B, ray ? 1 : 0, d.n_paths, c.gains.p, d.fD, d.fs, p->fid.p, a->seed, inj_ph,
                                inj_ph_stride, inj_lh, inj_lh_stride, c.coef.p, phases));
   }
-  // transmit_mimo's link power on the TX symbols in LDS (static taps, N >= 512,
-  // delays within the CP): the channel pass then reads x once
   TxLinkPower<R> lp{};
   const int maxd = ray ? *std::max_element(d.delays, d.delays + d.n_paths) : 0;
-  const bool lp_fuse = link_noise && m.n_cs == 1 && !m.exact_jakes && (g.N >> 3) >= 64 && maxd <= g.cp &&
-                       d.n_paths <= TXCH_MAXP &&
-                       env_on("LTE_MIMO_LP_FUSE", true);
   // (partials [link][symbol]: the layout k_link_power writes, nch = n_sym blocks per link)
-  if (lp_fuse) lp = TxLinkPower<R>{p->delays.p, c.coef.p, c.link_part.p, d.n_paths, maxd,
-                                   mimo_channel_nblk(p->L, g.N + g.cp)};
-  // flat links (AWGN: spatial CN(0,1), SFBC exp(j t pi/2)): TX and channel in
-  // one pass per (frame, symbol, RX) -- y_r = IFFT(sum_t h_rt G_t) -- when no
-  // TX-stream capture needs x
+  if (path.lp_fuse) lp = TxLinkPower<R>{p->delays.p, c.coef.p, c.link_part.p, d.n_paths, maxd,
+                                        mimo_channel_nblk(p->L, g.N + g.cp)};
   const int nch = mimo_channel_nblk(p->L, g.N + g.cp);
-  const bool flat_fuse = !ray && !a->cap_signal_tx && !a->cap_link_stats && (g.N >> 3) >= 64 && m.num_tx <= 4 &&
-                         env_on("LTE_MIMO_FLAT_FUSE", true);
-  // config 4 (SFBC, static-tap Rayleigh links with the 100 dB link noise, Philox
-  // draws): TX and the links' fading in one pass per frame writing the faded RX
-  // signals (k_ofdm_txch_sfbc), then the link noise + RX power (k_link_noise_pairs)
-  // -- x never goes through HBM.  Captures of x / the link statistics and the
-  // reference's own (injected) link noise keep the separate kernels.
   int npow_nblk = nch;   // RX power partials per (frame, RX) that k_npow_mimo sums
-  const bool sfbc_fuse = link_noise && !inj_lz && !inj_z && !a->cap_signal_tx && !a->cap_link_stats &&
-                         sfbc_txch_supported<R>(g, m, d.n_paths, maxd) && env_on("LTE_SFBC_TXCH_FUSE", true);
-  // the merged link noise (launch_npow_sfbc_merged): the fused TX, then one
-  // noise draw per RX sample in the fused receiver -- only when nothing
-  // observes the received streams or noise powers in between
-  const bool zn0_ = coded && (d.bps == 4 || d.bps == 6) && !a->cap_llr && (m.res & 1) == 0 && m.n_dsc <= m.res &&
-                    env_on("LTE_DEMAP_IN_DEMATCH", true);
-  const bool sfbc_merge = sfbc_fuse && !a->cap_signal_rx && !a->cap_noise_power && !a->cap_H && !a->cap_data_syms &&
-                          !(a->cap_bits_rx && !coded) && (zn0_ || !coded) && rx_sfbc_supported<R>(g, m) &&
-                          env_on("LTE_SFBC_RX_FUSE", true) && env_on("LTE_SFBC_LINK_MERGE", true);
-  if (sfbc_fuse) {
+  const bool sfbc_merge = path.sfbc_merge;
+  if (path.tx == MTX_SFBC) {
     TxLinkPower<R> lf{p->delays.p, c.coef.p, c.link_part.p, d.n_paths, maxd, 1};
     lf.merged = sfbc_merge ? 1 : 0;
     {
@@ -1732,21 +1889,22 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, int B, int n_snr, const 
     else
       LCHK(launch_link_noise_add<R>(s, g, m, B, c.link_part.p, c.link_sigma.p, c.y.p, p->fid.p, a->seed,
                                     c.pow_part.p, &npow_nblk));
-  } else if (flat_fuse) {
+  } else if (!path.ch_sep) {
     Timer t(p, KN_OFDM_TX);
     LCHK(launch_ofdm_txch_flat<R>(s, g, m, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, p->tx_map.p,
-                                  c.coef.p, c.y.p, c.pow_part.p, nch, B));
+                                  c.coef.p, c.y.p, c.pow_part.p, nch, B,
+                                  path.tx == MTX_FLAT_PR ? FLAT_PR : path.tx == MTX_FLAT_W ? FLAT_WAVE : FLAT_BLOCK));
   } else {
     if (c.x.alloc((size_t)d.max_frames * m.num_tx * p->L)) return fail(LTE_ENOMEM, "TX signal buffer");
     {
       Timer t(p, KN_OFDM_TX);
       LCHK(launch_ofdm_tx_mimo<R>(s, g, m, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, p->tx_map.p, c.x.p,
-                                  B, lp));
+                                  B, lp, path.tx == MTX_FRAME ? 1 : 0));
     }
     Timer t(p, KN_CHANNEL);
     LCHK(launch_channel_mimo<R>(s, g, m, B, np, ray ? p->delays.p : nullptr, c.coef.p, phases, c.gains.p, d.fs, c.x.p,
                                 c.y.p, link_noise ? 1 : 0, p->fid.p, a->seed, inj_lz, inj_lz_stride, c.link_part.p,
-                                c.link_sigma.p, c.pow_part.p, p->nblk, lp_fuse ? 1 : 0));
+                                c.link_sigma.p, c.pow_part.p, p->nblk, path.ch, path.lp_fuse ? 1 : 0));
   }
   if (!sfbc_merge) {
     Timer t(p, KN_CHANNEL);
@@ -1754,21 +1912,7 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, int B, int n_snr, const 
     LCHK(launch_npow_mimo<R>(s, B, m.num_rx, c.pow_part.p, npow_nblk, p->L, c.snr_lin.p, sfbc ? (double)m.num_tx : 1.0,
                              c.npow.p));
   }
-  // config 4 (SFBC on Philox draws, zn handoff or uncoded, no capture of the
-  // received grids / estimates / symbols): receiver + detector in one pass
-  const bool zn0 = coded && sfbc && (d.bps == 4 || d.bps == 6) && !a->cap_llr && (m.res & 1) == 0 &&
-                   m.n_dsc <= m.res && env_on("LTE_DEMAP_IN_DEMATCH", true);
-  // (a capture of the received bits needs the detector's decisions only
-  // uncoded: coded, they come from k_crc_count)
-  const bool rx_fuse = sfbc && !inj_z && !a->cap_H && !a->cap_data_syms && !(a->cap_bits_rx && !coded) &&
-                       (zn0 || !coded) &&
-                       rx_sfbc_supported<R>(g, m) && env_on("LTE_SFBC_RX_FUSE", true);
-  if (sfbc_merge && !rx_fuse) return fail(LTE_EINVAL, "merged link noise without the fused SFBC receiver");
-  // spatial multiplexing without a capture of H: the receiver hands over each
-  // estimation symbol's LS pilot estimates and the detector interpolates them
-  // per RE (the same mimo_interp), instead of a round trip of the interpolated
-  // H (num_tx x n_dsc per RX and symbol) through HBM
-  const bool h_pilots = !sfbc && !a->cap_H && env_on("LTE_SPATIAL_HP", true);
+  const bool rx_fuse = path.rx == MRX_SFBC, h_pilots = path.h_pilots, zn = path.zn;
   if (rx_fuse) {
     Timer t(p, KN_RX_CHEST);
     LCHK(launch_rx_sfbc<R>(s, g, m, coded ? 1 : 0, B, c.y.p, c.npow.p, p->fid.p, a->seed, c.snr_lin.p, p->pw.p,
@@ -1779,8 +1923,15 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, int B, int n_snr, const 
         c.H.alloc((size_t)d.max_frames * m.num_rx * m.n_est * m.num_tx * (h_pilots ? m.maxP : m.n_dsc)))
       return fail(LTE_ENOMEM, "received grids / estimates");
     Timer t(p, KN_RX_CHEST);
-    LCHK(launch_rx_fft_mimo<R>(s, g, m, B, c.y.p, c.npow.p, p->fid.p, a->seed, inj_z, inj_z_stride, c.Ym.p, c.H.p,
-                               h_pilots ? 1 : 0));
+    if (path.rx == MRX_FFT_W) {
+      if constexpr (std::is_same_v<R, double>)
+        LCHK(launch_rx_fft_mimo_w(s, g, m, B, c.y.p, c.npow.p, p->fid.p, a->seed, inj_z, inj_z_stride, c.Ym.p, c.H.p));
+      else
+        return fail(LTE_EINVAL, "the wave receiver runs in float64 plans only");
+    } else {
+      LCHK(launch_rx_fft_mimo<R>(s, g, m, B, c.y.p, c.npow.p, p->fid.p, a->seed, inj_z, inj_z_stride, c.Ym.p, c.H.p,
+                                 h_pilots ? 1 : 0));
+    }
   }
   V* cap_syms_dev = nullptr;
   uint8_t* cap_bits_dev = nullptr;
@@ -1792,10 +1943,6 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, int B, int n_snr, const 
     if (p->cap_bits.alloc((size_t)B * d.n_bits)) return fail(LTE_ENOMEM, "capture");
     cap_bits_dev = p->cap_bits.p;
   }
-  // coded SFBC 16/64-QAM without an LLR capture: the detector hands over the
-  // combined symbols and each RE pair's sigma^2_eff, k_dematch_zn demaps (as
-  // the SISO chain does; LTE_DEMAP_IN_DEMATCH=0 keeps the LLR round trip)
-  const bool zn = zn0;
   if (!rx_fuse) {
     Timer t(p, KN_RX_DATA);
     if (sfbc)
@@ -1804,7 +1951,7 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, int B, int n_snr, const 
                               zn ? zn_z<R>(p) : nullptr, zn ? zn_nv<R>(p) : nullptr));
     else
       LCHK(launch_det_spatial<R>(s, g, m, B, c.Ym.p, c.H.p, p->nvar.p, p->pw.p, p->PW, d.n_bits, p->frame_err.p,
-                                 cap_syms_dev, cap_bits_dev, h_pilots ? 1 : 0));
+                                 cap_syms_dev, cap_bits_dev, h_pilots ? 1 : 0, path.det_stage ? 1 : 0));
   }
   if (coded) {
     {
@@ -1981,43 +2128,16 @@ static int run_bf(lte_plan* p, const lte_run_args* a, int B, int n_snr, const st
 
 
 
-// TX with the channel fused in (TxChannelT): SISO / SIMO Rayleigh (SC-FDM
-// precoding included), delays within the CP, no TX / RX stream capture; static
-// taps (fD = 0) or per-symbol Taylor sets while mimo_taylor_ok (3 km/h at
-// 20 MHz: |w| S / 2 = 1.2e-3).
-// LTE_TXCH_FUSE=0 selects the separate TX and channel kernels (A/B and
-// parity tests).
-static bool txch_fusable(const lte_plan* p, const lte_run_args* a, bool coded) {
-  const lte_plan_desc& d = p->d;
-  if (d.channel != LTE_CH_RAYLEIGH || d.num_rx < 1 || p->mimo || p->bf) return false;
-  if (d.fD != 0.0 && !mimo_taylor_ok(d.fD, d.fs, d.N + d.cp_len)) return false;
-  if (a->in_signal || a->cap_signal_tx || a->cap_signal_rx) return false;
-  if (const char* e = std::getenv("LTE_TXCH_FUSE"))
-    if (std::atoi(e) == 0) return false;
-  return txch_supported(p->grid, d.n_paths, *std::max_element(d.delays, d.delays + d.n_paths));
-}
-
-
-
-// Coded TX + channel with one slot per frame (k_ofdm_txf) when its LDS fits
-// (coded streams staged once per frame); LTE_TX_FRAME=0 keeps one slot per
-// OFDM symbol (k_ofdm_tx<.., CH>, A/B and parity tests).
-static bool tx_per_frame(const lte_plan* p) {
-  if (const char* e = std::getenv("LTE_TX_FRAME"))
-    if (std::atoi(e) == 0) return false;
-  const int spw = 256 / (p->grid.N >> 3);
-  const size_t el = p->f64 ? 16 : 8;
-  return (size_t)spw * (p->grid.N * el + (size_t)p->enc_words * 4) <= 65536;
-}
-
 // Fading taps, fused TX + channel, first-samples power fix-up and noise power.
 template <class R>
-static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, int B, bool coded, const R* inj_ph,
-                    int64_t inj_ph_stride, cx<R>* cap_tx_syms, cx<R>* x_out, TxChannelT<R>* ch_out) {
+static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const SisoPath& path, int B, bool coded,
+                    const R* inj_ph, int64_t inj_ph_stride, cx<R>* cap_tx_syms, cx<R>* x_out, TxChannelT<R>* ch_out) {
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
   const int maxd = *std::max_element(d.delays, d.delays + d.n_paths);
-  if (c.xh.alloc((size_t)d.max_frames * p->n_sym * 2 * std::max(maxd, 1))) return fail(LTE_ENOMEM, "tx channel");
+  // each symbol's head / tail TX samples for k_chan_fix (none when the TX forms the head power itself)
+  if (path.ch_fix && c.xh.alloc((size_t)d.max_frames * p->n_sym * 2 * std::max(maxd, 1)))
+    return fail(LTE_ENOMEM, "tx channel");
   const int rx = d.num_rx;
   const bool tv = d.fD != 0.0;   // time-varying taps: per-symbol Taylor sets
   if (tv && c.tcoef.alloc((size_t)d.max_frames * rx * d.n_paths * p->n_sym * mimo_ncf<R>()))
@@ -2038,62 +2158,40 @@ static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, int B, bo
   for (int i = 0; i < d.n_paths; ++i) ch.delays[i] = d.delays[i];
   ch.coef = c.coef.p;
   ch.y = c.y.p;
-  ch.xh = c.xh.p;
+  ch.xh = path.ch_fix ? c.xh.p : nullptr;
   ch.pow_part = c.pow_part.p;
   ch.x_out = x_out;
   if (ch_out) *ch_out = ch;
   {
     Timer t(p, KN_OFDM_TX, s);
-    if (coded && tx_per_frame(p))
+    if (path.tx == TX_FRAME) {
       LCHK(launch_ofdm_txf<R>(s, p->grid, p->enc.p, p->enc_words, p->tx_map.p, p->txf_map.p, p->txf_re.p, B,
                               cap_tx_syms, ch));
-    else
+    } else if (path.tx == TX_SYM_CH) {
       LCHK(launch_ofdm_tx_ch<R>(s, p->grid, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, p->tx_map.p, B,
-                                cap_tx_syms, ch, (d.sc_fdm && !coded) ? 1 : 0));
+                                cap_tx_syms, ch, (d.sc_fdm && !coded) ? 1 : 0, path.tx_stage ? 1 : 0));
+    } else if constexpr (std::is_same_v<R, double>) {   // the wave-private transmitters (lte_wave.hip)
+      if (path.tx == TX_FRAME_W)
+        LCHK(launch_ofdm_txf_w(s, p->grid, p->enc.p, p->enc_words, p->tx_map.p, B, cap_tx_syms, ch,
+                               path.tx_stage ? 1 : 0));
+      else
+        LCHK(launch_ofdm_tx_simo_w(s, p->grid, p->pw.p, p->PW, B, cap_tx_syms, ch));
+    } else {
+      return fail(LTE_EINVAL, "the wave transmitters run in float64 plans only");
+    }
   }
   {
     Timer t(p, KN_CHANNEL, s);
-    bool fix_fused = false;   // config 3's wave TX formed the head samples' power itself
-    if constexpr (std::is_same_v<R, double>)
-      fix_fused = !(coded && tx_per_frame(p)) && tx_simo_w_fuses_fix(p->grid, coded ? 1 : 0,
-                                                                     (d.sc_fdm && !coded) ? 1 : 0, ch);
-    if (!fix_fused) LCHK(launch_chan_fix<R>(s, p->grid, B, ch));
+    if (path.ch_fix) LCHK(launch_chan_fix<R>(s, p->grid, B, ch));
     LCHK(launch_npow<R>(s, B, rx, ch.pow_part, p->n_sym, p->L, c.snr_lin.p, c.npow.p));
   }
   return LTE_OK;
 }
 
-// Coded SISO 16/64-QAM without an LLR capture: k_rx_data hands over the
-// equalised symbol and sigma^2_eff per RE and k_dematch_zn demaps while it
-// builds the decoder rows, instead of a round trip of bps LLRs per RE.  The
-// (z, nv) arrays live in the LLR buffer ([max_frames][n_re] z, then
-// [max_frames][n_re] nv: 3 R per RE).  LTE_DEMAP_IN_DEMATCH=0 keeps the LLR path.
-static bool demap_in_dematch(const lte_plan* p, const lte_run_args* a) {
-  const lte_plan_desc& d = p->d;
-  if (d.chain != LTE_CHAIN_CODED || p->mimo || p->bf || (d.bps != 4 && d.bps != 6) || a->cap_llr) return false;
-  if (const char* e = std::getenv("LTE_DEMAP_IN_DEMATCH"))
-    if (std::atoi(e) == 0) return false;
-  return true;
-}
-
-// Fused SISO receiver (k_rx_frame): one RX, coded or uncoded, no SC-FDM.
-// LTE_RX_FUSE=0 selects k_rx_chest + k_rx_data (A/B and parity tests).
-static bool rx_fusable(const lte_plan* p, const lte_plan_desc& d) {
-  if (const char* e = std::getenv("LTE_RX_FUSE"))
-    if (std::atoi(e) == 0) return false;
-  return rx_frame_supported(p->grid, d.chain, d.num_rx, (d.sc_fdm && d.chain == LTE_CHAIN_UNCODED) ? 1 : 0);
-}
-// Fused SIMO MRC receiver (k_rx_frame_simo), same switch.
-static bool rx_simo_fusable(const lte_plan* p, const lte_plan_desc& d) {
-  if (const char* e = std::getenv("LTE_RX_FUSE"))
-    if (std::atoi(e) == 0) return false;
-  return d.chain == LTE_CHAIN_SIMO && rx_frame_simo_supported(p->grid, d.num_rx);
-}
-
 // SISO / SIMO chains (uncoded, coded, MRC) in precision R.
 template <class R>
-static int run_siso(lte_plan* p, const lte_run_args* a, int B, int n_snr, const std::vector<double>& snr_lin,
-                    const uint32_t* inj_bits, int64_t inj_bits_stride) {
+static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, int B, int n_snr,
+                    const std::vector<double>& snr_lin, const uint32_t* inj_bits, int64_t inj_bits_stride) {
   using V = cx<R>;
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
@@ -2122,17 +2220,7 @@ static int run_siso(lte_plan* p, const lte_run_args* a, int B, int n_snr, const 
                                 &inj_z_stride);
     if (e != LTE_OK) return e;
   }
-  // TX + static-tap channel in one kernel (the received stream is written once)
-  const bool fuse = do_tx && do_ch && txch_fusable(p, a, coded);
-  // SIMO into the paired receiver (config 3), opt-in (LTE_SIMO_XHAND=1): the
-  // TX hands over its symbols and the receiver applies each RX's taps
-  // (TxChannelT::x_out), one stream through HBM instead of num_rx.  Measured
-  // slower (profiles/r6_simo_xhand_ab.md: TX 16.1 -> 12.9 ms, receiver 27.7 ->
-  // 43.3 ms per 65 536 frames: the taps cost the VALU-bound receiver more than
-  // the streams cost the HBM)
-  const bool xhand = fuse && do_rx && d.fD == 0.0 && d.chain == LTE_CHAIN_SIMO &&
-                     rx_simo_fusable(p, d) && rx_simo2_ok(g, rx, a->cap_H != nullptr, a->cap_pilot_stats != nullptr) &&
-                     env_on("LTE_RXS_PAIRS", true) && env_on("LTE_SIMO_XHAND", false);
+  const bool fuse = path.fused(), xhand = path.xhand;
   TxChannelT<R> xch{};
   if (do_tx || a->bits) {
     Timer t(p, KN_PAYLOAD);
@@ -2150,14 +2238,14 @@ static int run_siso(lte_plan* p, const lte_run_args* a, int B, int n_snr, const 
       cts = c.captx.p;
     }
     if (fuse) {
-      const int e = run_txch<R>(p, s, a, B, coded, inj_ph, inj_ph_stride, cts, xhand ? c.x.p : nullptr, &xch);
+      const int e = run_txch<R>(p, s, a, path, B, coded, inj_ph, inj_ph_stride, cts, xhand ? c.x.p : nullptr, &xch);
       if (e != LTE_OK) return e;
     } else {
       Timer t(p, KN_OFDM_TX);
       // SC-FDM precodes the uncoded SISO / SIMO transmitters only: simulate_siso_coded
       // builds its own grids without the precoder (core/ofdm_core.py:1062-1099)
       LCHK(launch_ofdm_tx<R>(s, g, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, p->tx_map.p, c.x.p, B, cts,
-                             (d.sc_fdm && !coded) ? 1 : 0));
+                             (d.sc_fdm && !coded) ? 1 : 0, path.tx_stage ? 1 : 0));
     }
   } else {
     const R* in = static_cast<const R*>(a->in_signal);
@@ -2182,10 +2270,7 @@ static int run_siso(lte_plan* p, const lte_run_args* a, int B, int n_snr, const 
                            ray ? *std::max_element(d.delays, d.delays + d.n_paths) : 0));
     LCHK(launch_npow<R>(s, B, rx, c.pow_part.p, channel_nblk(p->L), p->L, c.snr_lin.p, c.npow.p));
   }
-  // SISO receiver fused (estimation + data path per frame) unless LTE_RX_FUSE=0
-  const bool rxf = do_rx && rx_fusable(p, d);
-  const bool rxs = do_rx && !rxf && rx_simo_fusable(p, d);
-  if (do_rx && !rxf && !rxs) {
+  if (path.rx == RX_CHEST_DATA) {
     Timer t(p, KN_RX_CHEST);
     LCHK(launch_rx_chest<R>(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, a->seed, inj_z, inj_z_stride, c.H.p,
                             c.pstats.p));
@@ -2200,22 +2285,37 @@ static int run_siso(lte_plan* p, const lte_run_args* a, int B, int n_snr, const 
     if (p->cap_bits.alloc((size_t)B * d.n_bits)) return fail(LTE_ENOMEM, "capture");
     cap_bits_dev = p->cap_bits.p;
   }
-  const bool zn = demap_in_dematch(p, a);
+  const bool zn = path.zn;
   if (coded && !zn && c.llr.alloc((size_t)d.max_frames * p->n_re_bits)) return fail(LTE_ENOMEM, "LLR buffer");
-  if (rxf) {
+  if (path.rx == RX_FRAME_W) {
+    Timer t(p, KN_RX_DATA);
+    if constexpr (std::is_same_v<R, double>)
+      LCHK(launch_rx_frame_w(s, g, ray ? 1 : 0, B, ysrc, yfs, c.npow.p, c.snr_lin.p, p->fid.p, a->seed, inj_z,
+                             inj_z_stride, reinterpret_cast<R*>(zn_z<R>(p)), zn_nv<R>(p), cap_syms_dev,
+                             a->cap_H ? c.H.p : nullptr, a->cap_pilot_stats ? c.pstats.p : nullptr));
+    else
+      return fail(LTE_EINVAL, "the wave receivers run in float64 plans only");
+  } else if (path.rx == RX_SIMO_W) {
+    Timer t(p, KN_RX_DATA);
+    if constexpr (std::is_same_v<R, double>)
+      LCHK(launch_rx_frame_simo_w(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, a->seed, inj_z, inj_z_stride,
+                                  p->pw.p, p->PW, d.n_bits, p->frame_err.p, cap_syms_dev, cap_bits_dev));
+    else
+      return fail(LTE_EINVAL, "the wave receivers run in float64 plans only");
+  } else if (path.rx == RX_FRAME) {
     Timer t(p, KN_RX_DATA);
     LCHK(launch_rx_frame<R>(s, g, d.chain, ray ? 1 : 0, B, ysrc, yfs, c.npow.p, c.snr_lin.p, p->fid.p, a->seed, inj_z,
                             inj_z_stride, p->pw.p, p->PW, d.n_bits, p->frame_err.p,
                             zn ? reinterpret_cast<R*>(zn_z<R>(p)) : c.llr.p, cap_syms_dev,
                             coded ? nullptr : cap_bits_dev, zn ? zn_nv<R>(p) : nullptr,
                             a->cap_H ? c.H.p : nullptr, a->cap_pilot_stats ? c.pstats.p : nullptr));
-  } else if (rxs) {
+  } else if (path.rx == RX_SIMO || path.rx == RX_SIMO2) {
     Timer t(p, KN_RX_DATA);
     LCHK(launch_rx_frame_simo<R>(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, a->seed, inj_z, inj_z_stride,
                                  p->pw.p, p->PW, d.n_bits, p->frame_err.p, cap_syms_dev, cap_bits_dev,
                                  a->cap_H ? c.H.p : nullptr, a->cap_pilot_stats ? c.pstats.p : nullptr,
-                                 xhand ? &xch : nullptr));
-  } else if (do_rx) {
+                                 path.rx == RX_SIMO2 ? 1 : 0, xhand ? &xch : nullptr));
+  } else if (path.rx == RX_CHEST_DATA) {
     Timer t(p, KN_RX_DATA);
     LCHK(launch_rx_data<R>(s, g, d.chain, ray ? 1 : 0, B, rx, ysrc, yrs, yfs, c.H.p, c.npow.p, c.snr_lin.p, p->fid.p,
                            a->seed, inj_z, inj_z_stride, p->pw.p, p->PW, d.n_bits, p->frame_err.p,
@@ -2353,22 +2453,52 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
   p->evuse.clear();
   if (logmap_on() && (d.chain == LTE_CHAIN_CODED || d.chain == LTE_CHAIN_SFBC_CODED) && !p->f64)
     return fail(LTE_EUNSUP, "exact log-MAP decoding runs in float64 plans only");
+  const Knobs knobs = read_knobs();   // the environment switches, once per run
   if (!p->mimo && !p->bf) {
-    const int e = p->f64 ? run_siso<double>(p, a, B, n_snr, sl, inj_bits, inj_bits_stride)
-                         : run_siso<float>(p, a, B, n_snr, sl, inj_bits, inj_bits_stride);
+    const SisoPath path = select_siso(p, a, knobs);
+    const int e = p->f64 ? run_siso<double>(p, a, path, B, n_snr, sl, inj_bits, inj_bits_stride)
+                         : run_siso<float>(p, a, path, B, n_snr, sl, inj_bits, inj_bits_stride);
     HIPCHK(hipStreamSynchronize(s));
     return e;
   }
   if (stages != LTE_STAGE_ALL) return fail(LTE_EUNSUP, "multi-antenna chains run all stages");
   if (p->mimo)
-    return p->f64 ? run_mimo<double>(p, a, B, n_snr, sl, inj_bits, inj_bits_stride)
-                  : run_mimo<float>(p, a, B, n_snr, sl, inj_bits, inj_bits_stride);
+    return p->f64 ? run_mimo<double>(p, a, select_mimo<double>(p, a, knobs), B, n_snr, sl, inj_bits, inj_bits_stride)
+                  : run_mimo<float>(p, a, select_mimo<float>(p, a, knobs), B, n_snr, sl, inj_bits, inj_bits_stride);
   // beamforming chain: noise scale sqrt(noise_variance / 2), noise_variance =
   // 10 ** (-snr_db / 10) (core/ofdm_core.py:2397-2399)
   std::vector<double> sig(B);
   for (int b = 0; b < B; ++b) sig[b] = std::sqrt(std::pow(10.0, -a->snr_db[b] / 10.0) / 2.0);
   return p->f64 ? run_bf<double>(p, a, B, n_snr, sig, inj_bits, inj_bits_stride)
                 : run_bf<float>(p, a, B, n_snr, sig, inj_bits, inj_bits_stride);
+}
+
+// The kernel path lte_run would take for (plan, args) under the current
+// environment, as one "key=value ..." line: the same select_* call, nothing
+// launched or allocated.  Returns the line's length (it is cut to len - 1).
+int lte_run_path(const lte_plan* p, const lte_run_args* a, char* buf, int len) {
+  if (!p || !a || !buf || len < 1) return fail(LTE_EINVAL, "null argument");
+  const Knobs knobs = read_knobs();
+  int n;
+  if (p->bf) {
+    n = std::snprintf(buf, len, "tx=none rx=k_bf");
+  } else if (!p->mimo) {
+    const SisoPath s = select_siso(p, a, knobs);
+    n = std::snprintf(buf, len, "tx=%s tx_stage=%d ch_fix=%d rx=%s xhand=%d dematch=%s", SISO_TX_NAME[s.tx], s.tx_stage,
+                      s.ch_fix, SISO_RX_NAME[s.rx], s.xhand,
+                      p->d.chain != LTE_CHAIN_CODED || s.rx == RX_NONE ? "none" : s.zn ? "zn" : "llr");
+  } else {
+    const MimoPath s = p->f64 ? select_mimo<double>(p, a, knobs) : select_mimo<float>(p, a, knobs);
+    char ch[48];   // the channel pass: fused into the TX, k_channel_mimo, or k_channel_tay with its form
+    if (s.ch_sep && s.ch.tay)
+      std::snprintf(ch, sizeof ch, "k_channel_tay,J=%d,G=%d,econ=%d", s.ch.J, s.ch.G, s.ch.econ);
+    else
+      std::snprintf(ch, sizeof ch, "%s", s.ch_sep ? "k_channel_mimo" : "fused");
+    n = std::snprintf(buf, len, "tx=%s lp_fuse=%d ch=%s link_merge=%d rx=%s h_pilots=%d det_stage=%d dematch=%s",
+                      MIMO_TX_NAME[s.tx], s.lp_fuse, ch, s.sfbc_merge, MIMO_RX_NAME[s.rx], s.h_pilots, s.det_stage,
+                      p->d.chain != LTE_CHAIN_SFBC_CODED ? "none" : s.zn ? "zn" : "llr");
+  }
+  return n < len ? n : len - 1;
 }
 
 // ------------------------------------------------------------------ stage entry points

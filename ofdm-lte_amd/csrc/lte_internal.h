@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "../../include/lte_phy.h"
 #include "lte_common.h"
+#include "lte_knobs.h"
 
 namespace lte {
 
@@ -70,8 +71,9 @@ int launch_encode(hipStream_t s, const uint32_t* pw, int PW, int KWmax, uint32_t
 // float (fast mode); explicit instances in lte_kernels.hip.
 template <class R>
 int launch_ofdm_tx(hipStream_t s, const Grid& g, int coded, const uint32_t* pw, int PW, const uint32_t* enc,
-                   int enc_words, const int32_t* tx_map, cx<R>* x, int B, cx<R>* cap_syms = nullptr,
-                   int sc_fdm = 0);
+                   int enc_words, const int32_t* tx_map, cx<R>* x, int B, cx<R>* cap_syms, int sc_fdm, int stage);
+// stage: the coded stream staged in LDS per slot (k_ofdm_tx, with or without the channel)
+bool tx_stage_supported(const Grid& g, int coded, int enc_words);
 template <class R>
 int launch_fading(hipStream_t s, int B, int num_rx, int n_paths, const R* gains_dev, const uint64_t* fid,
                   uint64_t seed, const R* inj_ph, int64_t inj_stride, R* phases, cx<R>* coef);
@@ -123,7 +125,7 @@ int launch_jakes_sets(hipStream_t s, int B, int n_paths, int n_sym, int sym_len,
 template <class R>
 int launch_ofdm_tx_ch(hipStream_t s, const Grid& g, int coded, const uint32_t* pw, int PW, const uint32_t* enc,
                       int enc_words, const int32_t* tx_map, int B, cx<R>* cap_syms, const TxChannelT<R>& ch,
-                      int sc_fdm = 0);
+                      int sc_fdm, int stage);
 template <class R>
 int launch_chan_fix(hipStream_t s, const Grid& g, int B, const TxChannelT<R>& ch);
 // coded TX + channel with one slot per frame (the frame's coded streams staged
@@ -135,12 +137,11 @@ int launch_ofdm_txf(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_w
                     const int32_t* txf_map, const int32_t* txf_re, int B, cx<R>* cap_syms,
                     const TxChannelT<R>& ch);
 // wave-private f64 coded TX + static taps (lte_wave.hip), N = 2048, SISO, four
-// paths with every delay <= 64: launch_ofdm_txf's outputs; it dispatches to
-// it with LTE_TX_WAVE=1 (off by default)
+// paths with every delay <= 64: launch_ofdm_txf's outputs (Knobs::tx_wave, off
+// by default).  stage: the coded streams staged in the wave's LDS
 bool txf_w_supported(const Grid& g, int f64, int n_paths, int max_delay, int num_rx, int tv);
-int tx_wave_enabled();
 int launch_ofdm_txf_w(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_words, const int32_t* tx_map, int B,
-                      double2* cap_syms, const TxChannelT<double>& ch);
+                      double2* cap_syms, const TxChannelT<double>& ch, int stage);
 // the lane order: for each OFDM symbol a permutation of its Nd data REs over
 // the N/2 TX slots, greedy per 32-slot group (one ds_read_b32 lane group) so
 // that each of the bps coded-bit gathers sees as few distinct words per LDS
@@ -166,10 +167,9 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
 // sigma^2_eff per (frame, group, data subcarrier); H / pstats: optional captures.
 bool rx_frame_supported(const Grid& g, int chain, int num_rx, int sc_fdm);
 // wave-private f64 coded receiver (lte_wave.hip): k_rx_frame's outputs (ZN demap:
-// equalised symbols zo + sigma^2_eff nv_out) for N = 2048; launch_rx_frame
-// dispatches to it with LTE_RX_WAVE=1 (off by default)
+// equalised symbols zo + sigma^2_eff nv_out) for N = 2048 (Knobs::rx_wave, off
+// by default)
 bool rx_frame_w_supported(const Grid& g, int chain, int f64);
-int rx_wave_enabled();
 int launch_rx_frame_w(hipStream_t s, const Grid& g, int rayleigh, int B, const double2* y, int64_t y_frame_stride,
                       const double* npow, const double* snr_lin, const uint64_t* fid, uint64_t seed,
                       const double* inj_z, int64_t inj_stride, double* zo, double* nv_out, double2* cap_syms,
@@ -181,15 +181,16 @@ int launch_rx_frame(hipStream_t s, const Grid& g, int chain, int rayleigh, int B
                     R* llr, cx<R>* cap_syms, uint8_t* cap_bits, R* nv_out, cx<R>* H, R* pstats);
 // Fused SIMO MRC receiver (uncoded, 2..RXS_MAXRX RX): one slot per frame walks
 // its symbols, every RX's estimate in registers; H / pstats: optional captures
-// [B][num_rx][n_grp][N] / [B][num_rx][n_grp][2].
+// [B][num_rx][n_grp][N] / [B][num_rx][n_grp][2].  pairs: k_rx_frame_simo2
+// (rx_simo2_ok), else k_rx_frame_simo.
 constexpr int RXS_MAXRX = 4;
 bool rx_frame_simo_supported(const Grid& g, int num_rx);
 template <class R>
 int launch_rx_frame_simo(hipStream_t s, const Grid& g, int B, int num_rx, const cx<R>* y, int64_t y_rx_stride,
                          int64_t y_frame_stride, const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z,
                          int64_t inj_stride, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                         cx<R>* cap_syms, uint8_t* cap_bits, cx<R>* H, R* pstats,
-                         const TxChannelT<R>* xc = nullptr);
+                         cx<R>* cap_syms, uint8_t* cap_bits, cx<R>* H, R* pstats, int pairs,
+                         const TxChannelT<R>* xc);
 // the paired SIMO receiver applies (N = 1024, an even RX count, no H / pilot
 // statistics capture); xc->x_out (the TX's symbol handoff) needs it
 bool rx_simo2_ok(const Grid& g, int num_rx, bool H, bool pstats);
@@ -327,7 +328,8 @@ struct TxLinkPower {
 template <class R>
 int launch_ofdm_tx_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, const uint32_t* pw, int PW,
                         const uint32_t* enc, int enc_words, const int32_t* tx_map, cx<R>* x, int B,
-                        const TxLinkPower<R>& lp);
+                        const TxLinkPower<R>& lp, int per_frame);
+bool tx_mimo_frame_supported(const Grid& g, int coded, int enc_words);
 // per link path: f32 h(n) = A + B d + C d^2 around the centre of n's OFDM
 // symbol (fD != 0), or A (fD == 0); f64 A (fD == 0) or the phases (exact Jakes)
 template <class R>
@@ -337,10 +339,13 @@ int launch_fading_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, i
                        cx<R>* coef, R* phases);
 // TX + flat (AWGN) channel in one pass per (frame, symbol, RX): y [B][num_rx][L]
 // and pow_part [B][num_rx][nblk] (per OFDM symbol); coef from launch_fading_mimo
+enum FlatTx { FLAT_BLOCK, FLAT_PR, FLAT_WAVE };   // k_ofdm_txch_flat, its <.., PR> form, k_ofdm_txch_flat_w
+bool txch_flat_pr_supported(const Grid& g, const MimoGrid& m);
+bool txch_flat_w_supported(const Grid& g, const MimoGrid& m, int f64);
 template <class R>
 int launch_ofdm_txch_flat(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, const uint32_t* pw, int PW,
                           const uint32_t* enc, int enc_words, const int32_t* tx_map, const cx<R>* coef, cx<R>* y,
-                          R* pow_part, int nblk, int B);
+                          R* pow_part, int nblk, int B, FlatTx variant);
 // config 4: SFBC TX + static-tap Rayleigh links in one pass per frame (y gets
 // the faded RX signals, lp.part one power per link); then the link sigmas, the
 // combined link noise added to y and the RX power partials pow_part
@@ -368,12 +373,22 @@ int launch_npow_sfbc_merged(hipStream_t s, int B, int num_rx, int num_tx, const 
 template <class R>
 int launch_link_noise_add(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const R* link_part, R* link_sigma,
                           cx<R>* y, const uint64_t* fid, uint64_t seed, R* pow_part, int* pow_nblk);
+// the channel pass on the coefficient path: k_channel_tay (with its J samples
+// per thread, G RX per group, economised sets) or k_channel_mimo
+struct ChanMimoSel {
+  bool tay;
+  int J, G;
+  bool econ;
+};
+template <class R>
+ChanMimoSel channel_mimo_select(const MimoGrid& m, int n_paths, int sym_len, double fs, const Knobs& k);
 // phases / gains: exact-Jakes mode (m.exact_jakes) only
 template <class R>
 int launch_channel_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, int n_paths, const int32_t* delays,
                         const cx<R>* coef, const R* phases, const R* gains, double fs, const cx<R>* x, cx<R>* y,
                         int link_noise, const uint64_t* fid, uint64_t seed, const R* inj_lz, int64_t inj_lz_stride,
-                        R* link_part, R* link_sigma, R* pow_part, int nblk, int link_part_done = 0);
+                        R* link_part, R* link_sigma, R* pow_part, int nblk, const ChanMimoSel& sel,
+                        int link_part_done);
 // OFDM symbols (blocks of N + cp samples) of a stream: the power partials per
 // (frame, rx) the multi-antenna channel passes write
 int mimo_channel_nblk(int L, int sym_len);
@@ -389,15 +404,11 @@ template <class R>
 int launch_npow_mimo(hipStream_t s, int B, int num_rx, const R* pow_part, int nblk, int L, const R* snr_lin,
                      double div, R* npow);
 // wave-private f64 RX FFT + CRS pilot estimates (lte_wave.hip), N = 2048, the
-// pilot-estimate handoff: launch_rx_fft_mimo's outputs; it dispatches to it
-// unless LTE_MIMO_RX_WAVE=0
+// pilot-estimate handoff: launch_rx_fft_mimo's outputs (Knobs::mimo_rx_wave)
 bool rx_fft_mimo_w_supported(const Grid& g, const MimoGrid& m, int f64, int h_pilots);
-int mimo_rx_wave_enabled();
 bool rx_simo_w_supported(const Grid& g, int num_rx, int f64, bool H, bool pstats, bool xin);
-int simo_rx_wave_enabled();
-bool tx_simo_w_supported(const Grid& g, int f64, int coded, int sc_fdm, const TxChannelT<double>& ch);
-int simo_tx_wave_enabled();
-bool tx_simo_w_fuses_fix(const Grid& g, int coded, int sc_fdm, const TxChannelT<double>& ch);
+bool tx_simo_w_supported(const Grid& g, int f64, int coded, int sc_fdm, int n_paths, int max_delay, int num_rx,
+                         bool tv, bool xout);
 int launch_ofdm_tx_simo_w(hipStream_t s, const Grid& g, const uint32_t* pw, int PW, int B, double2* cap_syms,
                           const TxChannelT<double>& ch);
 int launch_rx_frame_simo_w(hipStream_t s, const Grid& g, int B, int num_rx, const double2* y, int64_t y_rx_stride,
@@ -413,7 +424,7 @@ template <class R>
 // interpolates them per RE with the same mimo_interp)
 int launch_rx_fft_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const cx<R>* y, const R* npow,
                        const uint64_t* fid, uint64_t seed, const R* inj_z, int64_t inj_stride, cx<R>* Y, cx<R>* H,
-                       int h_pilots = 0);
+                       int h_pilots);
 // config 4's receiver + SFBC detector in one pass per frame (k_rx_sfbc): the
 // outputs of launch_rx_fft_mimo + launch_det_sfbc (zn handoff or bit errors)
 // without Y / H in HBM
@@ -432,7 +443,8 @@ int launch_det_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, 
 template <class R>
 int launch_det_spatial(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const cx<R>* Y, const cx<R>* H,
                        const double* nvar, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                       cx<R>* cap_syms, uint8_t* cap_bits, int h_pilots = 0);
+                       cx<R>* cap_syms, uint8_t* cap_bits, int h_pilots, int stage);
+bool det_spatial_stage_supported(const MimoGrid& m, int f64, int n_sym, int B, int h_pilots);
 // SFBCAlamouti.encode (decode = 0: a = symbols -> o0 = TX0, o1 = TX1) / .decode
 // (decode = 1: a = rx, h0 / h1 the per-SC estimates -> o0), float64 [n] complex, n even
 int launch_sfbc_stage(hipStream_t s, int decode, int64_t n, const double* a, const double* h0, const double* h1,

@@ -6,7 +6,6 @@
 #include "lte_common.h"
 #include "lte_internal.h"
 #include "lte_dev.h"
-#include <cstdlib>
 
 namespace lte {
 
@@ -371,27 +370,27 @@ __global__ __launch_bounds__(WG) void k_ofdm_tx(Grid g, const uint32_t* __restri
   }
 }
 
-// LDS bytes of the coded stream staged per slot (0: not staged).
-// LTE_TX_STAGE=0 gathers the coded bits through L1 / L2 instead (A/B knob).
-static size_t tx_enc_shm(int coded, int spw, int enc_words) {
+// LDS bytes of the coded stream staged per slot (0: not staged; Knobs::tx_stage
+// off gathers the coded bits through L1 / L2 instead).
+static size_t tx_enc_shm(int coded, int spw, int enc_words, int stage) {
   const size_t e = (size_t)spw * enc_words * sizeof(uint32_t);
-  static const int on = [] {
-    const char* v = std::getenv("LTE_TX_STAGE");
-    return v ? std::atoi(v) : 1;
-  }();
-  return coded && on && e <= 32768 ? e : 0;
+  return coded && stage && e <= 32768 ? e : 0;
+}
+bool tx_stage_supported(const Grid& g, int coded, int enc_words) {
+  return tx_enc_shm(coded, WG / (g.N >> 3), enc_words, 1) > 0;
 }
 
 template <class R>
 int launch_ofdm_tx(hipStream_t s, const Grid& g, int coded, const uint32_t* pw, int PW, const uint32_t* enc,
-                   int enc_words, const int32_t* tx_map, cx<R>* x, int B, cx<R>* cap_syms, int sc_fdm) {
+                   int enc_words, const int32_t* tx_map, cx<R>* x, int B, cx<R>* cap_syms, int sc_fdm, int stage) {
   const int spw = WG / (g.N >> 3);
   const int64_t total = (int64_t)B * g.n_sym;
   if (total > 0x7FFFFFFF - spw || (g.bps != 2 && g.bps != 4 && g.bps != 6)) return (int)hipErrorInvalidValue;
+  if (stage && !tx_stage_supported(g, coded, enc_words)) return (int)hipErrorInvalidValue;
   if (sc_fdm && (coded || !GridT<R>::chirp(g) || !GridT<R>::bhat(g) || 2 * g.Nd > g.N))
     return (int)hipErrorInvalidValue;
   const int blocks = (int)((total + spw - 1) / spw);
-  const size_t enc_shm = tx_enc_shm(coded, spw, enc_words);
+  const size_t enc_shm = tx_enc_shm(coded, spw, enc_words, stage);
   const int stage_enc = enc_shm > 0;
   const size_t shm = (sc_fdm ? 2 : 1) * spw * g.N * sizeof(cx<R>) + enc_shm;
 #define LTE_TX(C_, B_, S_)                                                                                      \
@@ -457,7 +456,7 @@ static void ofdm_tx_ch_go(hipStream_t s, int blocks, size_t shm, const Grid& g, 
 template <class R>
 int launch_ofdm_tx_ch(hipStream_t s, const Grid& g, int coded, const uint32_t* pw, int PW, const uint32_t* enc,
                       int enc_words, const int32_t* tx_map, int B, cx<R>* cap_syms, const TxChannelT<R>& ch,
-                      int sc_fdm) {
+                      int sc_fdm, int stage) {
   const int spw = WG / (g.N >> 3);
   const int64_t total = (int64_t)B * g.n_sym;
   if (sc_fdm && (coded || !GridT<R>::chirp(g) || !GridT<R>::bhat(g) || 2 * g.Nd > g.N))
@@ -465,12 +464,9 @@ int launch_ofdm_tx_ch(hipStream_t s, const Grid& g, int coded, const uint32_t* p
   if (!txch_supported(g, ch.n_paths, ch.max_delay) || total > 0x7FFFFFFF - spw ||
       (g.bps != 2 && g.bps != 4 && g.bps != 6))
     return (int)hipErrorInvalidValue;
-  if constexpr (sizeof(R) == 8) {   // config 3: the wave-private TX (lte_wave.hip; LTE_SIMO_TX_WAVE=0: this kernel)
-    if (simo_tx_wave_enabled() && tx_simo_w_supported(g, 1, coded, sc_fdm, ch))
-      return launch_ofdm_tx_simo_w(s, g, pw, PW, B, cap_syms, ch);
-  }
+  if (stage && !tx_stage_supported(g, coded, enc_words)) return (int)hipErrorInvalidValue;
   const int blocks = (int)((total + spw - 1) / spw);
-  const size_t enc_shm = tx_enc_shm(coded, spw, enc_words);
+  const size_t enc_shm = tx_enc_shm(coded, spw, enc_words, stage);
   const int stage_enc = enc_shm > 0;
   const size_t shm = (sc_fdm ? 2 : 1) * (size_t)spw * g.N * sizeof(cx<R>) + enc_shm;
 #define LTE_TXC2(C_, B_, S_, CH_) \
@@ -502,9 +498,6 @@ int launch_ofdm_tx_ch(hipStream_t s, const Grid& g, int coded, const uint32_t* p
 #endif
 #ifndef LTE_LDS_PROBE   // timing probes of the per-RE LDS accesses (A/B builds only)
 #define LTE_LDS_PROBE 0
-#endif
-#ifndef TXF_STAGE   // 1: the frame's coded streams staged in LDS; 0: bit gathers through L1 / L2
-#define TXF_STAGE 1
 #endif
 // Lane order (txf_re, plan_txf_lane_order): slot s = tid + q T of symbol l
 // carries RE txf_re[l][s] and reads its coded-bit sources from the slot-ordered
@@ -630,10 +623,6 @@ int launch_ofdm_txf(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_w
                     const TxChannelT<R>& ch) {
   const int spw = WG / (g.N >> 3);
   if (!txch_supported(g, ch.n_paths, ch.max_delay) || (g.bps != 2 && g.bps != 4 && g.bps != 6)) return (int)hipErrorInvalidValue;
-  if constexpr (sizeof(R) == 8)
-    if (!txf_map && txf_w_supported(g, 1, ch.n_paths, ch.max_delay, ch.num_rx, ch.tcoef != nullptr) &&
-        tx_wave_enabled())
-      return launch_ofdm_txf_w(s, g, enc, enc_words, tx_map, B, cap_syms, ch);
   const size_t shm = (size_t)spw * g.N * sizeof(cx<R>) + (TXF_STAGE ? (size_t)spw * enc_words * sizeof(uint32_t) : 0);
   if (shm > 65536) return (int)hipErrorInvalidValue;
   // symbol pairs (LTE_TXF_SP = 2): two grids and one staged copy per frame
@@ -1573,10 +1562,6 @@ int launch_rx_frame(hipStream_t s, const Grid& g, int chain, int rayleigh, int B
                     const R* inj_z, int64_t inj_stride, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
                     R* llr, cx<R>* cap_syms, uint8_t* cap_bits, R* nv_out, cx<R>* H, R* pstats) {
   if (!rx_frame_supported(g, chain, 1, 0) || (nv_out && chain != LTE_CHAIN_CODED)) return (int)hipErrorInvalidValue;
-  if constexpr (sizeof(R) == 8)
-    if (nv_out && rx_frame_w_supported(g, chain, 1) && rx_wave_enabled())
-      return launch_rx_frame_w(s, g, rayleigh, B, y, y_frame_stride, npow, snr_lin, fid, seed, inj_z, inj_stride,
-                               llr, nv_out, cap_syms, H, pstats);
   const int spw = WG / (g.N >> 3);
   const int blocks = (B + spw - 1) / spw;
   const size_t shm = (size_t)spw * (g.N + g.Np) * sizeof(cx<R>);
@@ -1945,16 +1930,11 @@ template <class R>
 int launch_rx_frame_simo(hipStream_t s, const Grid& g, int B, int num_rx, const cx<R>* y, int64_t y_rx_stride,
                          int64_t y_frame_stride, const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z,
                          int64_t inj_stride, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                         cx<R>* cap_syms, uint8_t* cap_bits, cx<R>* H, R* pstats, const TxChannelT<R>* xc) {
+                         cx<R>* cap_syms, uint8_t* cap_bits, cx<R>* H, R* pstats, int pairs,
+                         const TxChannelT<R>* xc) {
   if (!rx_frame_simo_supported(g, num_rx)) return (int)hipErrorInvalidValue;
-  if constexpr (sizeof(R) == 8) {   // config 3: the wave-private receiver (lte_wave.hip)
-    if (simo_rx_wave_enabled() &&
-        rx_simo_w_supported(g, num_rx, 1, H != nullptr, pstats != nullptr, xc && xc->x_out))
-      return launch_rx_frame_simo_w(s, g, B, num_rx, y, y_rx_stride, y_frame_stride, npow, fid, seed, inj_z, inj_stride,
-                                    pw, PW, n_bits, frame_err, cap_syms, cap_bits);
-  }
-  const char* pe = std::getenv("LTE_RXS_PAIRS");   // 0: one slot per frame with T threads, the RX in sequence (A/B)
-  if (rx_simo2_ok(g, num_rx, H != nullptr, pstats != nullptr) && (!pe || std::atoi(pe) != 0)) {
+  if (pairs) {   // k_rx_frame_simo2
+    if (!rx_simo2_ok(g, num_rx, H != nullptr, pstats != nullptr)) return (int)hipErrorInvalidValue;
     const bool xin = xc && xc->x_out;
     const size_t shm2 = (2 * (size_t)g.N + RXS_MAXRX * g.Np + (xin ? g.N : 0)) * sizeof(cx<R>);
     const TxChannelT<R> xcv = xin ? *xc : TxChannelT<R>{};
@@ -2042,9 +2022,9 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
 // explicit instances of the precision-templated launchers (lte_capi.hip)
 #define LTE_INST(R)                                                                                                   \
   template int launch_ofdm_tx<R>(hipStream_t, const Grid&, int, const uint32_t*, int, const uint32_t*, int,          \
-                                 const int32_t*, cx<R>*, int, cx<R>*, int);                                         \
+                                 const int32_t*, cx<R>*, int, cx<R>*, int, int);                                    \
   template int launch_ofdm_tx_ch<R>(hipStream_t, const Grid&, int, const uint32_t*, int, const uint32_t*, int,       \
-                                    const int32_t*, int, cx<R>*, const TxChannelT<R>&, int);                        \
+                                    const int32_t*, int, cx<R>*, const TxChannelT<R>&, int, int);                   \
   template int launch_chan_fix<R>(hipStream_t, const Grid&, int, const TxChannelT<R>&);                             \
   template int launch_ofdm_txf<R>(hipStream_t, const Grid&, const uint32_t*, int, const int32_t*, const int32_t*,   \
                                   const int32_t*, int, cx<R>*, const TxChannelT<R>&);                                \
@@ -2061,7 +2041,7 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
                                  const uint32_t*, int, int, uint32_t*, R*, cx<R>*, uint8_t*, int, R*);              \
   template int launch_rx_frame_simo<R>(hipStream_t, const Grid&, int, int, const cx<R>*, int64_t, int64_t, const R*,  \
                                        const uint64_t*, uint64_t, const R*, int64_t, const uint32_t*, int, int,       \
-                                       uint32_t*, cx<R>*, uint8_t*, cx<R>*, R*, const TxChannelT<R>*);               \
+                                       uint32_t*, cx<R>*, uint8_t*, cx<R>*, R*, int, const TxChannelT<R>*);          \
   template int launch_rx_frame<R>(hipStream_t, const Grid&, int, int, int, const cx<R>*, int64_t, const R*, const R*, \
                                   const uint64_t*, uint64_t, const R*, int64_t, const uint32_t*, int, int, uint32_t*, \
                                   R*, cx<R>*, uint8_t*, R*, cx<R>*, R*);

@@ -526,30 +526,25 @@ bool txch_flat_w_supported(const Grid& g, const MimoGrid& m, int f64) {
          m.rank >= 1 && m.rank <= 4 && g.cp >= 0 && g.cp <= 512;
 }
 
-// Opt-in (profiles/r6_mimo_tx_wave/): the TX itself runs 22.5 against 23.3 ms
-// per 32 768 config-5 frames, but the receiver that follows it loses as much
-// (26.8-27.1 against 26.4-26.5 ms), so config 5 does not move.
-#ifndef LTE_MIMO_TX_WAVE
-#define LTE_MIMO_TX_WAVE 0
-#endif
+// FLAT_PR: spatial, one slot per (frame, symbol) over the receive antennas
+bool txch_flat_pr_supported(const Grid& g, const MimoGrid& m) {
+  return m.mode == MIMO_SPATIAL && g.N == 2048 && m.n_dsc <= 4 * (g.N >> 3);
+}
 
 template <class R>
 int launch_ofdm_txch_flat(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, const uint32_t* pw, int PW,
                           const uint32_t* enc, int enc_words, const int32_t* tx_map, const cx<R>* coef, cx<R>* y,
-                          R* pow_part, int nblk, int B) {
+                          R* pow_part, int nblk, int B, FlatTx variant) {
   const int spw = MWG / (g.N >> 3);
-  // LTE_TXCH_PR=1 (A/B, off by default): spatial, one slot per (frame, symbol)
-  // over the receive antennas -- 25.0 vs 23.9 ms per 32 768 config-5 frames
-  // (the saved bit gathers do not pay for a quarter of the slots)
-  const char* pre = std::getenv("LTE_TXCH_PR");
-  const bool pr = m.mode == MIMO_SPATIAL && g.N == 2048 && m.n_dsc <= 4 * (g.N >> 3) && pre && std::atoi(pre) != 0;
+  const bool pr = variant == FLAT_PR;
+  if (pr && !txch_flat_pr_supported(g, m)) return (int)hipErrorInvalidValue;
   const int64_t total = (int64_t)B * g.n_sym * (pr ? 1 : m.num_rx);
   if (total > 0x7FFFFFFF - spw || (g.bps != 2 && g.bps != 4 && g.bps != 6) || (g.N >> 3) < 64 || nblk < g.n_sym ||
       m.num_tx > 4)
     return (int)hipErrorInvalidValue;
-  if constexpr (sizeof(R) == 8) {   // the wave-private kernel (LTE_MIMO_TX_WAVE=1)
-    const char* we = std::getenv("LTE_MIMO_TX_WAVE");
-    if ((we ? std::atoi(we) != 0 : LTE_MIMO_TX_WAVE) && !pr && txch_flat_w_supported(g, m, 1)) {
+  if (variant == FLAT_WAVE) {   // the wave-private kernel
+    if constexpr (sizeof(R) == 8) {
+      if (!txch_flat_w_supported(g, m, 1)) return (int)hipErrorInvalidValue;
       const int64_t waves = (int64_t)B * m.num_rx;
       if (waves > 0x7FFFFFFF - TXMW_WAVES) return (int)hipErrorInvalidValue;
       const unsigned wb = (unsigned)((waves + TXMW_WAVES - 1) / TXMW_WAVES);
@@ -566,6 +561,7 @@ int launch_ofdm_txch_flat(hipStream_t s, const Grid& g, const MimoGrid& m, int c
 #undef LTE_TXFW
       return (int)hipGetLastError();
     }
+    return (int)hipErrorInvalidValue;
   }
   const int blocks = (int)((total + spw - 1) / spw);
   const size_t enc_shm = (size_t)spw * enc_words * sizeof(uint32_t);
@@ -624,10 +620,15 @@ __global__ __launch_bounds__(MWG) void k_link_power_fix(int B, int num_rx, int n
   lp.part[(size_t)bl * lp.nblk + l] += pwr;
 }
 
+// one slot per frame: the coded streams staged (they fit 32 KB per block), N = 2048
+bool tx_mimo_frame_supported(const Grid& g, int coded, int enc_words) {
+  return coded && (size_t)(MWG / (g.N >> 3)) * enc_words * sizeof(uint32_t) <= 32768 && g.N == 2048;
+}
+
 template <class R>
 int launch_ofdm_tx_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, const uint32_t* pw, int PW,
                         const uint32_t* enc, int enc_words, const int32_t* tx_map, cx<R>* x, int B,
-                        const TxLinkPower<R>& lp) {
+                        const TxLinkPower<R>& lp, int per_frame) {
   const int spw = MWG / (g.N >> 3);
   const int64_t total = (int64_t)B * g.n_sym * m.num_tx;
   if (total > 0x7FFFFFFF - spw || (g.bps != 2 && g.bps != 4 && g.bps != 6)) return (int)hipErrorInvalidValue;
@@ -636,9 +637,9 @@ int launch_ofdm_tx_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int cod
   const size_t enc_shm = (size_t)spw * enc_words * sizeof(uint32_t);
   const int stage_enc = coded && enc_shm <= 32768;
   const size_t shm = spw * g.N * sizeof(cx<R>) + (stage_enc ? enc_shm : 0);
-  // coded frames: one slot per frame over its (symbol, TX) pairs (LTE_TXM_FRAME=0: one per pair)
-  const char* pfe = std::getenv("LTE_TXM_FRAME");
-  const bool pf = stage_enc && g.N == 2048 && !(pfe && std::atoi(pfe) == 0);
+  // coded frames: one slot per frame over its (symbol, TX) pairs (per_frame = 0: one per pair)
+  if (per_frame && !tx_mimo_frame_supported(g, coded, enc_words)) return (int)hipErrorInvalidValue;
+  const bool pf = per_frame != 0;
   const int blocks = pf ? (B + spw - 1) / spw : (int)((total + spw - 1) / spw);
 #define LTE_TXM(M_, C_, B_)                                                                                          \
   do {                                                                                                               \
@@ -1650,8 +1651,6 @@ size_t channel_tay_lds(const MimoGrid& m, int np) {
 // sinusoid W = max |w_m| / fs, so |c5| D^5 / 16 <= 5.657 (W D)^5 / 1920 with D
 // the half symbol (3 km/h at 20 MHz: W D = 1.245e-3, 2.5 % inside the bound)
 static bool channel_tay_econ(const MimoGrid& m, int sym_len, double fs) {
-  if (const char* e = std::getenv("LTE_CHT_ECON"))
-    if (std::atoi(e) == 0) return false;
   double w = 0.0;
   for (int k = 0; k < 16; ++k) w = std::max(w, std::fabs(m.jw[k]));
   const double x = w / fs * 0.5 * (sym_len - 1);
@@ -1660,30 +1659,44 @@ static bool channel_tay_econ(const MimoGrid& m, int sym_len, double fs) {
 
 int mimo_channel_nblk(int L, int sym_len) { return (L + sym_len - 1) / sym_len; }
 
-// k_channel_tay's launch: G receive antennas per group (a divisor of num_rx);
+// Which kernel launch_channel_mimo runs on the coefficient path, and
+// k_channel_tay's form: G receive antennas per group (a divisor of num_rx);
 // J (samples per thread per pass, 1..3) the one covering a symbol with the
 // fewest idle lanes (20 MHz: 3 -> 2304 lanes for 2192 samples)
 template <class R>
-static void launch_channel_tay(hipStream_t s, int B, int nch, int L, const MimoGrid& m, int np, int sym_len,
-                               double fs, const int32_t* delays, const cx<R>* coef, const cx<R>* x, cx<R>* y,
-                               const R* link_sigma, const uint64_t* fid, uint64_t seed, const R* inj_lz,
-                               int64_t inj_lz_stride, R* pow_part) {
-  int J = 1;
+ChanMimoSel channel_mimo_select(const MimoGrid& m, int np, int sym_len, double fs, const Knobs& k) {
+  ChanMimoSel c{};
+  c.tay = !m.exact_jakes && k.chm_tay && channel_tay_lds<R>(m, np) <= 32768;
+  if (!c.tay) return c;
+  c.J = 1;
   long best = -1;
   for (int j = 1; j <= 3; ++j) {
     const long cover = (long)((sym_len + j * MWG - 1) / (j * MWG)) * j * MWG;
-    if (best < 0 || cover <= best) { best = cover; J = j; }
+    if (best < 0 || cover <= best) { best = cover; c.J = j; }
   }
+  // receive antennas per group: a divisor of num_rx, at most 4
+  c.G = m.num_rx <= 4 ? m.num_rx : m.num_rx % 4 == 0 ? 4 : m.num_rx % 3 == 0 ? 3 : m.num_rx % 2 == 0 ? 2 : 1;
+  // A/B overrides (LTE_CHT_J in 1..3; LTE_CHT_G a divisor of num_rx up to 4)
+  if (k.cht_j) c.J = k.cht_j;
+  if (k.cht_g >= 1 && k.cht_g <= 4 && m.num_rx % k.cht_g == 0) c.G = k.cht_g;
+  // the economised degree-4 sets (f64 Taylor path, J = 3)
+  c.econ = sizeof(R) == 8 && m.n_cs > 1 && c.J == 3 && k.cht_econ && channel_tay_econ(m, sym_len, fs);
+  return c;
+}
+template ChanMimoSel channel_mimo_select<float>(const MimoGrid&, int, int, double, const Knobs&);
+template ChanMimoSel channel_mimo_select<double>(const MimoGrid&, int, int, double, const Knobs&);
+
+template <class R>
+static int launch_channel_tay(hipStream_t s, int B, int nch, int L, const MimoGrid& m, int np, int sym_len,
+                              double fs, const int32_t* delays, const cx<R>* coef, const cx<R>* x, cx<R>* y,
+                              const R* link_sigma, const uint64_t* fid, uint64_t seed, const R* inj_lz,
+                              int64_t inj_lz_stride, R* pow_part, const ChanMimoSel& sel) {
+  const int J = sel.J, G = sel.G;
   const bool tay = m.n_cs > 1;
   const size_t shm = channel_tay_lds<R>(m, np);
-  // receive antennas per group: a divisor of num_rx, at most 4
-  int G = m.num_rx <= 4 ? m.num_rx : m.num_rx % 4 == 0 ? 4 : m.num_rx % 3 == 0 ? 3 : m.num_rx % 2 == 0 ? 2 : 1;
-  // A/B overrides (LTE_CHT_J in 1..3; LTE_CHT_G a divisor of num_rx up to 4)
-  if (const char* e = std::getenv("LTE_CHT_J")) J = std::min(3, std::max(1, std::atoi(e)));
-  if (const char* e = std::getenv("LTE_CHT_G")) {
-    const int g = std::atoi(e);
-    if (g >= 1 && g <= 4 && m.num_rx % g == 0) G = g;
-  }
+  if (m.exact_jakes || shm > 32768 || J < 1 || J > 3 || G < 1 || G > 4 || m.num_rx % G != 0 ||
+      (sel.econ && !(sizeof(R) == 8 && tay && J == 3 && channel_tay_econ(m, sym_len, fs))))
+    return (int)hipErrorInvalidValue;
 #define LTE_CHT(J_, G_, T_, E_)                                                                                      \
   do {                                                                                                               \
     if (link_sigma)                                                                                                  \
@@ -1709,24 +1722,27 @@ static void launch_channel_tay(hipStream_t s, int B, int nch, int L, const MimoG
     if (J == 1) LTE_CHT_G(1, T_, false); else if (J == 2) LTE_CHT_G(2, T_, false); else LTE_CHT_G(3, T_, false);     \
   } while (0)
   if constexpr (sizeof(R) == 8) {   // the economised degree-4 sets (f64 Taylor path, J = 3)
-    if (tay && J == 3 && channel_tay_econ(m, sym_len, fs)) {
+    if (sel.econ) {
       LTE_CHT_G(3, true, true);
-      return;
+      return (int)hipSuccess;
     }
   }
   if (tay) LTE_CHT_J(true); else LTE_CHT_J(false);
 #undef LTE_CHT_J
 #undef LTE_CHT_G
 #undef LTE_CHT
+  return (int)hipSuccess;
 }
 
 template <class R>
 int launch_channel_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, int n_paths, const int32_t* delays,
                         const cx<R>* coef, const R* phases, const R* gains, double fs, const cx<R>* x, cx<R>* y,
                         int link_noise, const uint64_t* fid, uint64_t seed, const R* inj_lz, int64_t inj_lz_stride,
-                        R* link_part, R* link_sigma, R* pow_part, int nblk, int link_part_done) {
+                        R* link_part, R* link_sigma, R* pow_part, int nblk, const ChanMimoSel& sel,
+                        int link_part_done) {
   const int sym_len = g.N + g.cp;
   if (m.num_rx > MC_MAXRX) return (int)hipErrorInvalidValue;
+  int tay_err = 0;
   const int nch = mimo_channel_nblk(g.L, sym_len);
   if (nch > nblk) return (int)hipErrorInvalidValue;   // partial buffers are sized for nblk blocks
   const R* ph = m.exact_jakes ? phases : nullptr;
@@ -1737,9 +1753,7 @@ int launch_channel_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, 
   // per-link vl); measured J = 1 / 2 / 3 / 5 at 20 MHz, f64 config 5 channel
   // 6.0 / 6.0 / 6.8 / 11.2 ms and 3 km/h 26.9 / 19.3 / 27.1 / 41.9 ms per 8192
   // frames; f32 4.2 / 3.1 / 3.0 / 3.2 and 15.9 / 11.0 / 9.6 / 11.3 ms
-  // the coefficient path runs k_channel_tay (LTE_CHM_TAY=0: k_channel_mimo, for A/B)
-  const char* tye = std::getenv("LTE_CHM_TAY");
-  const bool tay_on = !(tye && std::atoi(tye) == 0);
+  // the coefficient path runs k_channel_tay (sel.tay = 0: k_channel_mimo, for A/B)
   const int jn = (sym_len + MWG - 1) / MWG;
   const int jmax = sizeof(R) == 8 ? 2 : 3;
   const int J = jn <= 1 ? 1 : jn <= 2 || jmax == 2 ? 2 : 3;
@@ -1759,9 +1773,9 @@ int launch_channel_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, 
       hipLaunchKernelGGL(k_link_sigma<R>, dim3((nl + 255) / 256), dim3(256), 0, s, nl, link_part, nch, g.L,        \
                          link_sigma);                                                                              \
     }                                                                                                              \
-    if (!(EX_) && tay_on && channel_tay_lds<R>(m, n_paths) <= 32768)                                               \
-      launch_channel_tay<R>(s, B, nch, g.L, m, n_paths, sym_len, fs, delays, coef, x, y,                           \
-                            link_noise ? link_sigma : nullptr, fid, seed, inj_lz, inj_lz_stride, pow_part);        \
+    if (sel.tay)                                                                                                   \
+      tay_err = launch_channel_tay<R>(s, B, nch, g.L, m, n_paths, sym_len, fs, delays, coef, x, y, link_noise ? link_sigma : nullptr, \
+                                      fid, seed, inj_lz, inj_lz_stride, pow_part, sel);                            \
     else                                                                                                           \
       hipLaunchKernelGGL((k_channel_mimo<R, J_, EX_, G_>), dim3(nch * B), dim3(MWG), 0, s, g.L, m.num_rx,         \
                          m.num_tx, n_paths, m.n_cs, sym_len, delays, coef, ph, gains, fs, m, x, y,                 \
@@ -1780,6 +1794,7 @@ int launch_channel_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, 
 #undef LTE_CHM
 #undef LTE_CHM_EX
 #undef LTE_CHM_EXG
+  if (tay_err) return tay_err;
   return (int)hipGetLastError();
 }
 
@@ -1973,9 +1988,6 @@ template <class R>
 int launch_rx_fft_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const cx<R>* y, const R* npow,
                        const uint64_t* fid, uint64_t seed, const R* inj_z, int64_t inj_stride, cx<R>* Y, cx<R>* H,
                        int h_pilots) {
-  if constexpr (sizeof(R) == 8)
-    if (rx_fft_mimo_w_supported(g, m, 1, h_pilots) && mimo_rx_wave_enabled())
-      return launch_rx_fft_mimo_w(s, g, m, B, y, npow, fid, seed, inj_z, inj_stride, Y, H);
   const int spw = MWG / (g.N >> 3);
   const int64_t total = (int64_t)B * m.num_rx;
   if (total > 0x7FFFFFFF - spw) return (int)hipErrorInvalidValue;
@@ -2570,23 +2582,24 @@ void k_det_spatial(Grid g, MimoGrid m, int B, const cx<R>* __restrict__ Y,
   }
 }
 
-static int env_flag(const char* name, int dflt) {
-  const char* e = std::getenv(name);
-  return e ? std::atoi(e) : dflt;
+// the pilot estimates staged in LDS per (frame, symbol)
+bool det_spatial_stage_supported(const MimoGrid& m, int f64, int n_sym, int B, int h_pilots) {
+  return h_pilots && (size_t)m.num_rx * m.num_tx * m.maxP * (f64 ? 16 : 8) <= 32768 && (int64_t)B * n_sym < 0x7FFFFFFF;
 }
 
 template <class R>
 int launch_det_spatial(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const cx<R>* Y, const cx<R>* H,
                        const double* nvar, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                       cx<R>* cap_syms, uint8_t* cap_bits, int h_pilots) {
+                       cx<R>* cap_syms, uint8_t* cap_bits, int h_pilots, int stage) {
   if (m.num_tx < 1 || m.num_tx > DMAX || m.num_rx < 1 || m.num_rx > DMAX || m.rank < 1 || m.rank > m.num_rx ||
       m.rank > m.num_tx || !m.W)
     return (int)hipErrorInvalidValue;
   const int64_t n = (int64_t)B * g.n_sym * m.n_dsc;
   const dim3 grid((unsigned)((n + MWG - 1) / MWG));
-  // the pilot estimates staged per (frame, symbol) (LTE_DSP_STAGE=0: gathered per RE)
+  // the pilot estimates staged per (frame, symbol) (stage = 0: gathered per RE)
   const size_t hshm = (size_t)m.num_rx * m.num_tx * m.maxP * sizeof(cx<R>);
-  const bool stg = h_pilots && hshm <= 32768 && (int64_t)B * g.n_sym < 0x7FFFFFFF && env_flag("LTE_DSP_STAGE", 1);
+  if (stage && !det_spatial_stage_supported(m, sizeof(R) == 8, g.n_sym, B, h_pilots)) return (int)hipErrorInvalidValue;
+  const bool stg = stage != 0;
   const dim3 sgrid((unsigned)((int64_t)B * g.n_sym));
 #define LTE_DSP(B_, S_)                                                                                            \
   do {                                                                                                             \
@@ -2699,15 +2712,15 @@ int launch_det_stage(hipStream_t s, int det, int NR, int NT, int R, int bps, int
                                         const uint64_t*, uint64_t, R*, int*);                                      \
   template bool sfbc_txch_supported<R>(const Grid&, const MimoGrid&, int, int);                                   \
   template int launch_ofdm_tx_mimo<R>(hipStream_t, const Grid&, const MimoGrid&, int, const uint32_t*, int,       \
-                                      const uint32_t*, int, const int32_t*, cx<R>*, int, const TxLinkPower<R>&);   \
+                                      const uint32_t*, int, const int32_t*, cx<R>*, int, const TxLinkPower<R>&, int); \
   template int launch_ofdm_txch_flat<R>(hipStream_t, const Grid&, const MimoGrid&, int, const uint32_t*, int,     \
-                                        const uint32_t*, int, const int32_t*, const cx<R>*, cx<R>*, R*, int, int); \
+                                        const uint32_t*, int, const int32_t*, const cx<R>*, cx<R>*, R*, int, int, FlatTx); \
   template int launch_fading_mimo<R>(hipStream_t, const Grid&, const MimoGrid&, int, int, int, const R*, double,   \
                                      double, const uint64_t*, uint64_t, const R*, int64_t, const R*, int64_t,      \
                                      cx<R>*, R*);                                                                  \
   template int launch_channel_mimo<R>(hipStream_t, const Grid&, const MimoGrid&, int, int, const int32_t*,         \
                                       const cx<R>*, const R*, const R*, double, const cx<R>*, cx<R>*, int,         \
-                                      const uint64_t*, uint64_t, const R*, int64_t, R*, R*, R*, int, int);    \
+                                      const uint64_t*, uint64_t, const R*, int64_t, R*, R*, R*, int, const ChanMimoSel&, int); \
   template int launch_link_stats<R>(hipStream_t, const Grid&, const MimoGrid&, int, int, const int32_t*,           \
                                     const cx<R>*, const R*, const R*, double, const cx<R>*, const R*,              \
                                     const uint64_t*, uint64_t, const R*, int64_t, R*, int, R*);                    \
@@ -2722,7 +2735,7 @@ int launch_det_stage(hipStream_t s, int det, int NR, int NT, int R, int bps, int
                                   const cx<R>*, const R*, const uint32_t*, int, int, uint32_t*, R*, cx<R>*,        \
                                   uint8_t*, cx<R>*, R*);                                                           \
   template int launch_det_spatial<R>(hipStream_t, const Grid&, const MimoGrid&, int, const cx<R>*, const cx<R>*,   \
-                                     const double*, const uint32_t*, int, int, uint32_t*, cx<R>*, uint8_t*, int);
+                                     const double*, const uint32_t*, int, int, uint32_t*, cx<R>*, uint8_t*, int, int);
 LTE_MIMO_INST(float)
 LTE_MIMO_INST(double)
 #undef LTE_MIMO_INST

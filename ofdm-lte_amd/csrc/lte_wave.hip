@@ -636,10 +636,11 @@ bool rx_simo_w_supported(const Grid& g, int num_rx, int f64, bool H, bool pstats
 // Wave-private uncoded OFDM TX + static-tap SIMO channel (float64, N = 1024:
 // config 3; k_ofdm_tx<.., CH = 1>'s outputs plus k_chan_fix's): as built
 // (TXSW_HALF and TXSW_FRAME, the defaults) one wave64 per frame walking its
-// OFDM symbols in order, no block barrier; it writes no xh head / tail samples
-// (ChainBufs::xh stays unused on this path) and k_chan_fix does not run after
-// it (tx_simo_w_fuses_fix).  With TXSW_FRAME=0 it is one wave per (frame, OFDM
-// symbol) that leaves xh for k_chan_fix.
+// OFDM symbols in order, no block barrier, with each symbol's head power
+// fused in: it neither reads nor writes the xh head / tail samples (the run
+// allocates none and passes a null xh) and k_chan_fix does not run after it
+// (select_siso's ch_fix).  Built with TXSW_FRAME=0 it is one wave per (frame,
+// OFDM symbol) that leaves xh for k_chan_fix.
 // Per symbol: lane c, register q builds bin k = 64 q + c from
 // Grid::kinfo (a data RE's BPS payload bits -> qam_point, a pilot, or 0);
 // wfft::fft1024<INV> and the output scale give x[64 q + c], which is staged in
@@ -666,9 +667,6 @@ bool rx_simo_w_supported(const Grid& g, int num_rx, int f64, bool H, bool pstats
 // pinned against the oracle by tests/test_gpu_profiles.py.
 #ifndef TXSW_HALF
 #define TXSW_HALF 1
-#endif
-#ifndef TXSW_FRAME
-#define TXSW_FRAME 1
 #endif
 static_assert(!TXSW_FRAME || TXSW_HALF, "the per-frame form uses the window");
 constexpr int TXSW_WAVES = 2;
@@ -856,43 +854,14 @@ void k_ofdm_tx_simo_w(Grid g, const uint32_t* __restrict__ pw, int PW, int B, do
 #endif
 }
 
-bool tx_simo_w_supported(const Grid& g, int f64, int coded, int sc_fdm, const TxChannelT<double>& ch) {
-  return f64 && !coded && !sc_fdm && g.N == 1024 && g.kinfo && g.pilots64 && !ch.tcoef && !ch.x_out &&
-         ch.n_paths >= 1 && ch.n_paths <= TXCH_MAXP && ch.max_delay >= 0 && ch.max_delay <= g.cp && g.cp < 1024 &&
-         ch.num_rx >= 1 && (g.bps == 2 || g.bps == 4 || g.bps == 6) &&
-         (!TXSW_HALF || (ch.max_delay <= 64 && g.cp <= 512 && ch.num_rx <= 4));
+// tv: per-symbol Taylor sets (TxChannelT::tcoef); xout: the symbol handoff (TxChannelT::x_out)
+bool tx_simo_w_supported(const Grid& g, int f64, int coded, int sc_fdm, int n_paths, int max_delay, int num_rx,
+                         bool tv, bool xout) {
+  return f64 && !coded && !sc_fdm && g.N == 1024 && g.kinfo && g.pilots64 && !tv && !xout &&
+         n_paths >= 1 && n_paths <= TXCH_MAXP && max_delay >= 0 && max_delay <= g.cp && g.cp < 1024 &&
+         num_rx >= 1 && (g.bps == 2 || g.bps == 4 || g.bps == 6) &&
+         (!TXSW_HALF || (max_delay <= 64 && g.cp <= 512 && num_rx <= 4));
 }
-// the wave TX also forms the head samples' power (TXSW_FRAME): k_chan_fix must not run
-bool tx_simo_w_fuses_fix(const Grid& g, int coded, int sc_fdm, const TxChannelT<double>& ch) {
-  return TXSW_FRAME && simo_tx_wave_enabled() && tx_simo_w_supported(g, 1, coded, sc_fdm, ch);
-}
-
-// Which wave-private kernels run by default (same-box A/B, profiles/r6_wave_ab.md):
-// the config-5 RX (k_rx_fft_mimo_w) beats its block kernel; the config-2 RX and
-// TX do not (2 waves per SIMD at most with a symbol in registers, against 3 for
-// the block kernels; the noise, the coded-bit gathers and the taps, not the
-// FFT, set their time), so they are opt-in.  Env LTE_RX_WAVE / LTE_TX_WAVE /
-// LTE_MIMO_RX_WAVE = 0 / 1 override.
-#ifndef LTE_RX_WAVE
-#define LTE_RX_WAVE 0
-#endif
-#ifndef LTE_MIMO_RX_WAVE
-#define LTE_MIMO_RX_WAVE 1
-#endif
-static int env_or(const char* name, int dflt) {
-  const char* e = std::getenv(name);
-  return e ? std::atoi(e) : dflt;
-}
-int rx_wave_enabled() { return env_or("LTE_RX_WAVE", LTE_RX_WAVE); }
-int mimo_rx_wave_enabled() { return env_or("LTE_MIMO_RX_WAVE", LTE_MIMO_RX_WAVE); }
-#ifndef LTE_SIMO_RX_WAVE
-#define LTE_SIMO_RX_WAVE 1
-#endif
-int simo_rx_wave_enabled() { return env_or("LTE_SIMO_RX_WAVE", LTE_SIMO_RX_WAVE); }
-#ifndef LTE_SIMO_TX_WAVE
-#define LTE_SIMO_TX_WAVE 1
-#endif
-int simo_tx_wave_enabled() { return env_or("LTE_SIMO_TX_WAVE", LTE_SIMO_TX_WAVE); }
 
 template <int BPS, int NP>
 static void tx_simo_w_go(hipStream_t s, unsigned blocks, const Grid& g, const uint32_t* pw, int PW, int B,
@@ -909,7 +878,8 @@ static void tx_simo_w_np(hipStream_t s, unsigned blocks, const Grid& g, const ui
 }
 int launch_ofdm_tx_simo_w(hipStream_t s, const Grid& g, const uint32_t* pw, int PW, int B, double2* cap_syms,
                           const TxChannelT<double>& ch) {
-  if (!tx_simo_w_supported(g, 1, 0, 0, ch)) return (int)hipErrorInvalidValue;
+  if (!tx_simo_w_supported(g, 1, 0, 0, ch.n_paths, ch.max_delay, ch.num_rx, ch.tcoef != nullptr, ch.x_out != nullptr))
+    return (int)hipErrorInvalidValue;
   const int64_t waves = TXSW_FRAME ? (int64_t)B : (int64_t)B * g.n_sym;
   if (waves > 0x7FFFFFFF - TXSW_WAVES) return (int)hipErrorInvalidValue;
   const unsigned blocks = (unsigned)((waves + TXSW_WAVES - 1) / TXSW_WAVES);
@@ -951,14 +921,6 @@ int launch_rx_frame_w(hipStream_t s, const Grid& g, int rayleigh, int B, const d
   return (int)hipGetLastError();
 }
 
-#ifndef LTE_TX_WAVE
-#define LTE_TX_WAVE 0
-#endif
-#ifndef TXW_STAGE_DEFAULT   // 1: the coded streams staged in the wave's LDS (LTE_TXW_STAGE overrides)
-#define TXW_STAGE_DEFAULT 0
-#endif
-int tx_wave_enabled() { return env_or("LTE_TX_WAVE", LTE_TX_WAVE); }
-
 template <int BPS, bool STAGE>
 static int txf_w_go(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_words, const int32_t* tx_map, int B,
                     double2* cap_syms, const TxChannelT<double>& ch) {
@@ -972,10 +934,8 @@ static int txf_w_go(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_w
 }
 
 int launch_ofdm_txf_w(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_words, const int32_t* tx_map, int B,
-                      double2* cap_syms, const TxChannelT<double>& ch) {
+                      double2* cap_syms, const TxChannelT<double>& ch, int stage) {
   if (!txf_w_supported(g, 1, ch.n_paths, ch.max_delay, ch.num_rx, ch.tcoef != nullptr)) return (int)hipErrorInvalidValue;
-  const char* e = std::getenv("LTE_TXW_STAGE");
-  const bool stage = e ? std::atoi(e) != 0 : TXW_STAGE_DEFAULT;
   if (stage) {
     if (g.bps == 2) return txf_w_go<2, true>(s, g, enc, enc_words, tx_map, B, cap_syms, ch);
     if (g.bps == 4) return txf_w_go<4, true>(s, g, enc, enc_words, tx_map, B, cap_syms, ch);

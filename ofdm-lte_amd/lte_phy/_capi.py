@@ -68,6 +68,7 @@ _SIGS = {
     'lte_plan_info': (ctypes.c_int, [ctypes.c_void_p, P(c_i64)]),
     'lte_plan_precision': (ctypes.c_int, [ctypes.c_void_p]),
     'lte_run': (ctypes.c_int, [ctypes.c_void_p, P(RunArgs)]),
+    'lte_run_path': (ctypes.c_int, [ctypes.c_void_p, P(RunArgs), ctypes.c_char_p, ctypes.c_int]),
     'lte_timing_enable': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'lte_timing_read': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, P(c_f64), P(c_i64),
                                        ctypes.c_int]),

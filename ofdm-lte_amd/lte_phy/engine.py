@@ -15,6 +15,12 @@ import numpy as np
 from . import _capi as C
 
 
+class RunResult(dict):
+    """Plan.run's outputs by name (counts, frame_errors, the captures); .path:
+    the kernel path the run took (lte_run_path) as a dict of its fields."""
+    path = None
+
+
 class Plan:
     def __init__(self, *, N, Nc, cp_len, bps, n_sym, chain, channel, num_rx=1, delays=(), gains=(), fD=0.0,
                  fs=0.0, n_bits, turbo_iters=8, max_frames=1, cell_id=0, num_tx=1, rank=0, detector=0,
@@ -85,9 +91,30 @@ class Plan:
             pass
 
     # ------------------------------------------------------------------
-    def run(self, snr_db, *, snr_index=None, n_snr=1, seed=0, frame_ids=None, frame_id0=0, bits=None,
-            bits_broadcast=False, phases=None, phases_broadcast=False, noise=None, noise_broadcast=False,
-            stages=C.STAGE_ALL, in_signal=None, capture=(), link_noise=None, link_h=None, link_broadcast=False):
+    def run(self, snr_db, **kw):
+        """One batch through lte_run (keywords: _args) -> RunResult."""
+        a, out, keep = self._args(snr_db, **kw)
+        C.check(C.load().lte_run(self.h, ctypes.byref(a)))
+        out.path = self._path(a)
+        del keep
+        return out
+
+    def path(self, snr_db, **kw):
+        """The kernel path run(snr_db, **kw) would take under the current
+        environment switches, without running anything."""
+        a, _, keep = self._args(snr_db, **kw)
+        p = self._path(a)
+        del keep
+        return p
+
+    def _path(self, a):
+        buf = ctypes.create_string_buffer(256)
+        C.check(C.load().lte_run_path(self.h, ctypes.byref(a), buf, len(buf)))
+        return dict(kv.split('=', 1) for kv in buf.value.decode().split())
+
+    def _args(self, snr_db, *, snr_index=None, n_snr=1, seed=0, frame_ids=None, frame_id0=0, bits=None,
+              bits_broadcast=False, phases=None, phases_broadcast=False, noise=None, noise_broadcast=False,
+              stages=C.STAGE_ALL, in_signal=None, capture=(), link_noise=None, link_h=None, link_broadcast=False):
         snr = np.ascontiguousarray(np.atleast_1d(snr_db), dtype=np.float64)   # float64 as the reference (ABI 3)
         B = len(snr)
         a = C.RunArgs()
@@ -132,7 +159,7 @@ class Plan:
             a.link_h_stride = 0 if link_broadcast else lh.size // B
         counts = np.zeros((max(1, n_snr), 4), dtype=np.uint64)
         a.counts = C.ptr(counts, C.U64)
-        out = {'counts': counts}
+        out = RunResult(counts=counts)
         ferr = np.zeros(B, dtype=np.uint32)
         a.frame_errors = C.ptr(ferr, C.U32)
         out['frame_errors'] = ferr
@@ -178,9 +205,7 @@ class Plan:
             # void* fields take the address; typed fields a ctypes pointer
             setattr(a, field, arr.ctypes.data if ct is None else C.ptr(arr, ct))
             out[name] = arr
-        C.check(C.load().lte_run(self.h, ctypes.byref(a)))
-        del keep
-        return out
+        return a, out, keep
 
     # ------------------------------------------------------------------
     def timing(self, on=True):
@@ -214,6 +239,11 @@ def get_plan(**kw):
     else:
         _CACHE.move_to_end(key)
     return p
+
+
+def path_diff(a, b):
+    """The fields in which two runs' kernel paths (RunResult.path) differ."""
+    return {k for k in set(a) | set(b) if a.get(k) != b.get(k)}
 
 
 def clear_cache():

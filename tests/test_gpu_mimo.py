@@ -24,6 +24,12 @@ def C():
     return _capi
 
 
+def path_diff(a, b):
+    """The fields in which two runs' kernel paths (Plan.run(...).path) differ."""
+    from lte_phy.engine import path_diff as diff
+    return diff(a, b)
+
+
 def _state():
     return np.array(np.random.get_state()[1][:8], dtype=np.uint32)
 
@@ -188,6 +194,9 @@ def test_flat_channel_fused_tx(C, prec, mode, monkeypatch):
         monkeypatch.setenv('LTE_MIMO_FLAT_FUSE', fuse)
         outs.append(plan.run(snrs, seed=33, capture=('signal_rx', 'data_syms')))
     a, b = outs
+    # the switch moved the transmitter and the channel pass, nothing else
+    assert path_diff(a.path, b.path) == {'tx', 'ch'}, (a.path, b.path)
+    assert (a.path['tx'], a.path['ch'], b.path['tx']) == ('k_ofdm_txch_flat', 'fused', 'k_ofdm_tx_mimo')
     y0, y1 = a['signal_rx'].astype(np.complex128), b['signal_rx'].astype(np.complex128)
     assert np.linalg.norm(y0 - y1) / np.linalg.norm(y1) < (1e-14 if prec == 'f64' else 2e-6)
     z0, z1 = a['data_syms'].astype(np.complex128), b['data_syms'].astype(np.complex128)
@@ -212,6 +221,8 @@ def test_link_power_in_tx_matches_separate_pass(C, prec, monkeypatch):
         monkeypatch.setenv('LTE_MIMO_LP_FUSE', fuse)
         outs.append(plan.run(snrs, seed=21, capture=('signal_rx',)))
     a, b = outs
+    assert path_diff(a.path, b.path) == {'lp_fuse'}, (a.path, b.path)
+    assert (a.path['lp_fuse'], b.path['lp_fuse'], b.path['tx']) == ('1', '0', 'k_ofdm_tx_mimo_frame')
     y0, y1 = a['signal_rx'].astype(np.complex128), b['signal_rx'].astype(np.complex128)
     assert np.linalg.norm(y0 - y1) / np.linalg.norm(y1) < (1e-15 if prec == 'f64' else 1e-6)
     assert np.array_equal(a['frame_errors'], b['frame_errors']) and np.array_equal(a['crc_ok'], b['crc_ok'])
@@ -239,6 +250,10 @@ def test_sfbc_txch_fused_matches_separate_kernels(C, prec, coded, nrx, monkeypat
         monkeypatch.setenv('LTE_SFBC_TXCH_FUSE', fuse)
         outs.append(plan.run(snrs, seed=27, frame_id0=1000, capture=('signal_rx',)))
     a, b = outs
+    # the switch moved the transmitter and the channel pass (the separate TX then also forms the link power)
+    assert path_diff(a.path, b.path) == {'tx', 'ch', 'lp_fuse'}, (a.path, b.path)
+    assert (a.path['tx'], a.path['ch']) == ('k_ofdm_txch_sfbc', 'fused')
+    assert b.path['tx'] == ('k_ofdm_tx_mimo_frame' if coded else 'k_ofdm_tx_mimo')
     y0, y1 = a['signal_rx'].astype(np.complex128), b['signal_rx'].astype(np.complex128)
     assert y0.shape == (6, nrx, plan.L)
     assert np.linalg.norm(y0 - y1) / np.linalg.norm(y1) < (1e-14 if prec == 'f64' else 1e-6)
@@ -279,6 +294,8 @@ def test_sfbc_rx_fused_matches_separate_kernels(C, prec, coded, nrx, chan, monke
         monkeypatch.setenv('LTE_SFBC_RX_FUSE', fuse)
         outs.append(plan.run(snrs, seed=31, frame_id0=4242, capture=cap))
     a, b = outs
+    assert path_diff(a.path, b.path) == {'rx'}, (a.path, b.path)
+    assert (a.path['rx'], b.path['rx']) == ('k_rx_sfbc', 'k_rx_fft_mimo')
     if coded:
         assert np.array_equal(a['crc_ok'], b['crc_ok'])
         if prec == 'f64':
@@ -314,6 +331,9 @@ def test_spatial_pilot_handoff_matches_interpolated_h(C, prec, chan, det, monkey
         monkeypatch.setenv('LTE_SPATIAL_HP', hp)
         outs.append(plan.run(snrs, seed=17, frame_id0=777))
     a, b = outs
+    # the handoff and, with it, the detector's staging of the handed-over estimates
+    assert path_diff(a.path, b.path) == {'h_pilots', 'det_stage'}, (a.path, b.path)
+    assert (a.path['h_pilots'], b.path['h_pilots'], a.path['rx']) == ('1', '0', 'k_rx_fft_mimo')
     assert 0 < int(a['counts'][:, 0].sum())
     if prec == 'f64':
         assert np.array_equal(a['frame_errors'], b['frame_errors'])
@@ -346,6 +366,8 @@ def test_wave_mimo_receiver_matches_block_receiver(C, chan, det, inject, monkeyp
         monkeypatch.setenv('LTE_MIMO_RX_WAVE', wave)
         outs.append(plan.run(snrs, seed=17, frame_id0=777, **kw))
     a, b = outs
+    assert path_diff(a.path, b.path) == {'rx'}, (a.path, b.path)
+    assert (a.path['rx'], b.path['rx']) == ('k_rx_fft_mimo_w', 'k_rx_fft_mimo')
     assert 0 < int(a['counts'][:, 0].sum())
     assert np.array_equal(a['frame_errors'], b['frame_errors'])
     assert np.array_equal(a['counts'], b['counts'])
@@ -374,6 +396,8 @@ def test_wave_mimo_tx_matches_block_tx(C, det, inject, rank, monkeypatch):
         monkeypatch.setenv('LTE_MIMO_TX_WAVE', wave)
         outs.append(plan.run(snrs, seed=19, frame_id0=555, **kw))
     a, b = outs
+    assert path_diff(a.path, b.path) == {'tx'}, (a.path, b.path)
+    assert (a.path['tx'], b.path['tx']) == ('k_ofdm_txch_flat_w', 'k_ofdm_txch_flat')
     assert 0 < int(a['counts'][:, 0].sum())
     assert np.array_equal(a['frame_errors'], b['frame_errors'])
     assert np.array_equal(a['counts'], b['counts'])
@@ -460,5 +484,7 @@ def test_sfbc_demap_in_dematch_matches_llr_path(C, monkeypatch, mod, prec):
     a = plan.run(snr, seed=0x5EED, frame_id0=5)
     monkeypatch.setenv('LTE_DEMAP_IN_DEMATCH', '1')
     b = plan.run(snr, seed=0x5EED, frame_id0=5)
+    assert path_diff(a.path, b.path) == {'dematch'}, (a.path, b.path)
+    assert (a.path['dematch'], b.path['dematch'], b.path['rx']) == ('llr', 'zn', 'k_rx_fft_mimo')
     assert np.array_equal(a['crc_ok'], b['crc_ok']) and np.array_equal(a['counts'], b['counts'])
     assert np.array_equal(a['frame_errors'], b['frame_errors'])

@@ -25,6 +25,12 @@ def C():
     return _capi
 
 
+def path_diff(a, b):
+    """The fields in which two runs' kernel paths (Plan.run(...).path) differ."""
+    from lte_phy.engine import path_diff as diff
+    return diff(a, b)
+
+
 TOL_FFT = {'f64': 1e-14, 'f32': 2e-6}
 
 
@@ -416,6 +422,8 @@ def test_fused_tx_channel_matches_separate_kernels(C, monkeypatch, chain, prec):
     monkeypatch.setenv('LTE_TXCH_FUSE', '1')
     b = plan.run(snr, seed=0x5EED, frame_id0=77, capture=cap)
     f64 = prec == 'f64'
+    # the switch moved the transmitter (and with it k_chan_fix), nothing else
+    assert path_diff(a.path, b.path) == {'tx', 'ch_fix'} and a.path['tx'] == 'k_ofdm_tx', (a.path, b.path)
     assert np.max(np.abs(b['noise_power'] / a['noise_power'] - 1)) < (1e-13 if f64 else 2e-6)
     assert np.max(np.abs(b['H'] - a['H'])) < (1e-12 if f64 else 1e-4) * np.max(np.abs(a['H']))
     if coded:
@@ -452,6 +460,8 @@ def test_fused_receiver_matches_separate_kernels(C, monkeypatch, chain, bw, mod,
         runs[fuse] = (plan.run(snr, seed=0x5EED, frame_id0=3, capture=cap),
                       plan.run(snr, seed=0x5EED, frame_id0=3))
     (a, a0), (b, b0) = runs['0'], runs['1']
+    for r, q in ((a, b), (a0, b0)):   # the switch moved the receiver, nothing else
+        assert path_diff(r.path, q.path) == {'rx'} and q.path['rx'] == 'k_rx_frame', (r.path, q.path)
     tol = 1e-13 if prec == 'f64' else 1e-5
     for k in ('H', 'pilot_stats', 'data_syms'):
         assert np.max(np.abs(b[k] - a[k])) <= tol * np.max(np.abs(a[k])), k
@@ -491,6 +501,8 @@ def test_wave_receiver_matches_block_receiver(C, monkeypatch, mod, chan, inject)
         runs[wave] = (plan.run(snr, seed=0x5EED, frame_id0=3, capture=('H', 'pilot_stats', 'data_syms'), **kw),
                       plan.run(snr, seed=0x5EED, frame_id0=3, **kw))
     (a, a0), (b, b0) = runs['0'], runs['1']
+    for r, q in ((a, b), (a0, b0)):
+        assert path_diff(r.path, q.path) == {'rx'} and q.path['rx'] == 'k_rx_frame_w', (r.path, q.path)
     for k in ('H', 'pilot_stats', 'data_syms'):
         assert np.max(np.abs(b[k] - a[k])) <= 1e-12 * np.max(np.abs(a[k])), k
     for r, s in ((a, b), (a0, b0)):
@@ -524,6 +536,8 @@ def test_simo_symbol_handoff_matches_rx_streams(C, monkeypatch, prec, inject):
         runs[xh] = (plan.run(snr, seed=0x5EED, frame_id0=11, capture=('data_syms', 'bits_rx', 'noise_power'), **kw),
                     plan.run(snr, seed=0x5EED, frame_id0=11, **kw))
     (a, a0), (b, b0) = runs['0'], runs['1']
+    for r, q in ((a, b), (a0, b0)):
+        assert path_diff(r.path, q.path) == {'xhand'} and q.path['rx'] == 'k_rx_frame_simo2', (r.path, q.path)
     tol = 1e-12 if prec == 'f64' else 1e-5
     assert np.array_equal(a['noise_power'], b['noise_power'])   # the TX forms the powers either way
     assert np.max(np.abs(b['data_syms'] - a['data_syms'])) <= tol * np.max(np.abs(a['data_syms']))
@@ -558,6 +572,9 @@ def test_fused_simo_receiver_matches_separate_kernels(C, monkeypatch, bw, mod, n
         runs[fuse] = (plan.run(snr, seed=0x5EED, frame_id0=11, capture=cap),
                       plan.run(snr, seed=0x5EED, frame_id0=11))
     (a, a0), (b, b0) = runs['0'], runs['1']
+    for r, q in ((a, b), (a0, b0)):
+        assert path_diff(r.path, q.path) == {'rx'} and r.path['rx'] == 'k_rx_chest+k_rx_data', (r.path, q.path)
+    assert b.path['rx'] == 'k_rx_frame_simo'   # (the H capture keeps the paired / wave receivers out)
     tol = 1e-13 if prec == 'f64' else 1e-5
     for k in ('H', 'pilot_stats', 'data_syms'):
         assert np.max(np.abs(b[k] - a[k])) <= tol * np.max(np.abs(a[k])), k
@@ -589,6 +606,8 @@ def test_simo_receiver_rx_pairs_match_sequential(C, monkeypatch, nrx, mod, prec)
         monkeypatch.setenv('LTE_RXS_PAIRS', pairs)
         runs[pairs] = plan.run(snr, seed=0x5EED, frame_id0=77, capture=cap)
     a, b = runs['0'], runs['1']
+    assert path_diff(a.path, b.path) == {'rx'}, (a.path, b.path)
+    assert (a.path['rx'], b.path['rx']) == ('k_rx_frame_simo', 'k_rx_frame_simo2')
     if prec == 'f64':
         assert np.array_equal(a['data_syms'], b['data_syms'])
         assert np.array_equal(a['bits_rx'], b['bits_rx'])
@@ -603,9 +622,10 @@ def test_simo_receiver_rx_pairs_match_sequential(C, monkeypatch, nrx, mod, prec)
                                           (3, 'QPSK', 'Vehicular_A')])
 def test_wave_simo_tx_matches_block_tx(C, monkeypatch, nrx, mod, prof):
     """10 MHz SIMO TX + static taps, float64: the wave-private TX
-    (k_ofdm_tx_simo_w: one wave per frame walking its symbols, wfft::fft1024<INV>,
-    half a symbol at a time in an LDS window for every RX's taps, each symbol's
-    head-sample power formed in the kernel so that k_chan_fix does not run; the
+    (k_ofdm_tx_simo_w: one wave per frame walking its OFDM symbols in order,
+    wfft::fft1024<INV>, half a symbol at a time in an LDS window for every RX's
+    taps, each symbol's head-sample power fused in from the previous symbol's
+    kept tail, so that no xh hand-off is written and k_chan_fix does not run; the
     default) against k_ofdm_tx + k_chan_fix (LTE_SIMO_TX_WAVE=0) on the same
     frames (both against the oracle: tests/test_gpu_profiles.py): identical
     transmitted symbols;
@@ -626,6 +646,10 @@ def test_wave_simo_tx_matches_block_tx(C, monkeypatch, nrx, mod, prof):
         runs[wave] = (plan.run(snr, seed=0x5EED, frame_id0=91, capture=cap),
                       plan.run(snr, seed=0x5EED, frame_id0=91))
     (a, a0), (b, b0) = runs['0'], runs['1']
+    for r, q in ((a, b), (a0, b0)):   # the wave TX replaces k_ofdm_tx<.., CH> and k_chan_fix, nothing else
+        assert path_diff(r.path, q.path) == {'tx', 'ch_fix'}, (r.path, q.path)
+        assert (r.path['tx'], r.path['ch_fix']) == ('k_ofdm_tx_ch', '1')
+        assert (q.path['tx'], q.path['ch_fix']) == ('k_ofdm_tx_simo_w', '0')
     assert np.array_equal(a['tx_syms'], b['tx_syms'])
     assert np.max(np.abs(b['noise_power'] - a['noise_power']) / np.abs(a['noise_power'])) <= 1e-12
     assert np.max(np.abs(b['data_syms'] - a['data_syms'])) <= 1e-12 * np.max(np.abs(a['data_syms']))
@@ -661,6 +685,9 @@ def test_wave_simo_receiver_matches_block_receiver(C, monkeypatch, nrx, mod, inj
         runs[wave] = (plan.run(snr, seed=0x5EED, frame_id0=77, capture=('data_syms', 'bits_rx'), **kw),
                       plan.run(snr, seed=0x5EED, frame_id0=77, **kw))
     (a, a0), (b, b0) = runs['0'], runs['1']
+    for r, q in ((a, b), (a0, b0)):
+        assert path_diff(r.path, q.path) == {'rx'}, (r.path, q.path)
+        assert (r.path['rx'], q.path['rx']) == ('k_rx_frame_simo2', 'k_rx_frame_simo_w')
     assert np.max(np.abs(b['data_syms'] - a['data_syms'])) <= 1e-12 * np.max(np.abs(a['data_syms']))
     assert int(np.sum(a['bits_rx'] != b['bits_rx'])) <= 2
     assert abs(int(a0['counts'][:, 0].sum()) - int(b0['counts'][:, 0].sum())) <= 2
@@ -685,6 +712,8 @@ def test_frame_tx_matches_symbol_tx(C, monkeypatch, bw, mod, prec):
     a = plan.run(snr, seed=0x5EED, frame_id0=21, capture=cap)
     monkeypatch.setenv('LTE_TX_FRAME', '1')
     b = plan.run(snr, seed=0x5EED, frame_id0=21, capture=cap)
+    assert path_diff(a.path, b.path) == {'tx'}, (a.path, b.path)
+    assert (a.path['tx'], b.path['tx']) == ('k_ofdm_tx_ch', 'k_ofdm_txf')
     for k in cap:
         assert np.array_equal(a[k], b[k]), k
     assert np.array_equal(a['crc_ok'], b['crc_ok']) and np.array_equal(a['counts'], b['counts'])
@@ -713,6 +742,25 @@ def test_wave_tx_matches_block_tx(C, monkeypatch, mod):
     assert np.array_equal(a['tx_syms'], b['tx_syms'])
     for k in ('signal_rx', 'noise_power'):
         assert np.max(np.abs(b[k] - a[k])) <= 1e-12 * np.max(np.abs(a[k])), k
+    for k in cap + ('crc_ok', 'counts', 'frame_errors'):
+        assert np.array_equal(b[k], c[k]), k
+    assert np.array_equal(a['crc_ok'], b['crc_ok']) and np.array_equal(a['counts'], b['counts'])
+    assert np.array_equal(a['frame_errors'], b['frame_errors'])
+    # The signal_rx capture above keeps every fused transmitter out (txch_fusable:
+    # k_ofdm_tx + k_channel ran three times), so the same comparison once more on
+    # the captures the fused transmitters accept, where the path line shows that
+    # LTE_TX_WAVE moved the transmitter and LTE_TXW_STAGE only its staging.
+    cap = ('noise_power', 'tx_syms')
+    for wave, stage in (('0', '1'), ('1', '1'), ('1', '0')):
+        monkeypatch.setenv('LTE_TX_WAVE', wave)
+        monkeypatch.setenv('LTE_TXW_STAGE', stage)
+        runs[wave + stage] = plan.run(snr, seed=0x5EED, frame_id0=5, capture=cap)
+    a, b, c = runs['01'], runs['11'], runs['10']
+    assert path_diff(a.path, b.path) == {'tx'}, (a.path, b.path)
+    assert (a.path['tx'], b.path['tx']) == ('k_ofdm_txf', 'k_ofdm_txf_w')
+    assert path_diff(b.path, c.path) == {'tx_stage'}, (b.path, c.path)
+    assert np.array_equal(a['tx_syms'], b['tx_syms'])
+    assert np.max(np.abs(b['noise_power'] - a['noise_power'])) <= 1e-12 * np.max(np.abs(a['noise_power']))
     for k in cap + ('crc_ok', 'counts', 'frame_errors'):
         assert np.array_equal(b[k], c[k]), k
     assert np.array_equal(a['crc_ok'], b['crc_ok']) and np.array_equal(a['counts'], b['counts'])
@@ -765,6 +813,8 @@ def test_demap_in_dematch_matches_llr_path(C, monkeypatch, mod, prec):
     a = plan.run(snr, seed=0x5EED, frame_id0=5)
     monkeypatch.setenv('LTE_DEMAP_IN_DEMATCH', '1')
     b = plan.run(snr, seed=0x5EED, frame_id0=5)
+    assert path_diff(a.path, b.path) == {'dematch'}, (a.path, b.path)
+    assert (a.path['dematch'], b.path['dematch']) == ('llr', 'zn')
     assert np.array_equal(a['frame_errors'], b['frame_errors'])
     assert np.array_equal(a['crc_ok'], b['crc_ok'])
     assert 0 < int(np.sum(a['crc_ok'])) < B

@@ -180,7 +180,10 @@ def test_config4_merged_link_noise_same_distribution(C, monkeypatch):
         plan = _config_plan(4, len(snrs))
         out = plan.run(snrs, seed=91, frame_id0=10_000)
         res[merge] = out['frame_errors'].astype(np.float64)
+        res['path' + merge] = out.path
     engine.clear_cache()
+    assert engine.path_diff(res['path1'], res['path0']) == {'link_merge'}, (res['path1'], res['path0'])
+    assert (res['path1']['link_merge'], res['path0']['link_merge']) == ('1', '0')
     for k in range(3):
         sl = slice(683 * k, min(683 * (k + 1), 2048))
         a, b = res['1'][sl], res['0'][sl]

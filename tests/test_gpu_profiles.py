@@ -121,6 +121,72 @@ V_SIMO = [('a', {}, A_CAP), ('b_H', {}, A_CAP + ('H',)), ('b_H_sig', {}, A_CAP +
 
 
 # ---------------------------------------------------------------------------
+# The kernel path each test's docstring claims, per variant: (transmitter,
+# k_chan_fix runs, receiver) as lte_run_path names them (`Plan.run(...).path`),
+# asserted for every run of check_case.  'k_ofdm_tx' is the separate TX (then
+# k_channel), 'k_ofdm_tx_ch' the per-symbol k_ofdm_tx<.., CH>.
+_TX, _TXC, _TXF, _TXFW, _TXSW = 'k_ofdm_tx', 'k_ofdm_tx_ch', 'k_ofdm_txf', 'k_ofdm_txf_w', 'k_ofdm_tx_simo_w'
+_RXF, _RXFW, _RXSEP = 'k_rx_frame', 'k_rx_frame_w', 'k_rx_chest+k_rx_data'
+_RXS, _RXS2, _RXSW = 'k_rx_frame_simo', 'k_rx_frame_simo2', 'k_rx_frame_simo_w'
+
+
+def _siso(fused=True):
+    """Uncoded SISO: fused -> k_ofdm_tx<.., CH> + k_chan_fix unless a stream capture
+    / LTE_TXCH_FUSE=0 asks for k_ofdm_tx + k_channel; k_rx_frame unless LTE_RX_FUSE=0;
+    the 2048-point wave kernels are coded-only."""
+    on, off = ((_TXC, 1) if fused else (_TX, 0)), (_TX, 0)
+    return {'a': on + (_RXF,), 'b': off + (_RXF,), 'txch_fuse0': off + (_RXF,), 'rx_fuse0': on + (_RXSEP,),
+            'wave1': on + (_RXF,)}
+
+
+def _coded(fused=True, wave_tx=False, wave_rx=True):
+    """Coded SISO: k_ofdm_txf (LTE_TX_FRAME=0: k_ofdm_tx<.., CH>); wave_tx /
+    wave_rx: txf_w_supported / rx_frame_w_supported hold (the wave receiver also
+    needs the zn hand-off, that is no llr capture)."""
+    on, sym, off = ((_TXF, 1), (_TXC, 1), (_TX, 0)) if fused else ((_TX, 0),) * 3
+    w = (_TXFW, 1) if fused and wave_tx else on
+    return {'a': on + (_RXF,), 'a_nollr': on + (_RXF,), 'b': off + (_RXF,), 'tx_frame0': sym + (_RXF,),
+            'txch_fuse0': off + (_RXF,), 'rx_fuse0': on + (_RXSEP,), 'wave1_llr': w + (_RXF,),
+            'wave1_nollr': w + (_RXFW if wave_rx else _RXF,)}
+
+
+def _simo(tx=_TXSW, rx=_RXSW, rx_H=_RXS, rx_block=_RXS2):
+    """SIMO: tx the default transmitter (_TXSW: head power in-kernel, no
+    k_chan_fix; _TXC + k_chan_fix where tx_simo_w_supported refuses; _TX where
+    txch_supported does); rx the default receiver, rx_H with an H capture,
+    rx_block with LTE_SIMO_RX_WAVE=0."""
+    fix = {_TXSW: 0, _TXC: 1, _TX: 0}
+    on, blk, off = (tx, fix[tx]), ((_TXC, 1) if tx == _TXSW else (tx, fix[tx])), (_TX, 0)
+    return {'a': on + (rx,), 'b_H': on + (rx_H,), 'b_H_sig': off + (rx_H,), 'tx_wave0': blk + (rx,),
+            'rx_wave0': on + (rx_block,), 'txch_fuse0': off + (rx,), 'rx_fuse0': on + (_RXSEP,)}
+
+
+PATHS = {
+    'siso_pb20': _siso(), 'siso_vb20': _siso(), 'siso_bu20x': _siso(), 'siso_pa15': _siso(), 'siso_vb20_v3': _siso(),
+    'siso_vb20_v120': _siso(fused=False),                      # fD fails mimo_taylor_ok
+    'siso_pb20_cod': _coded(), 'siso_vb20_cod': _coded(), 'siso_vb20_v3_cod': _coded(),
+    'siso_bu20x_cod': _coded(wave_rx=False),                   # odd CP
+    'siso_pa15_cod': _coded(wave_tx=True),                     # 4 taps, max 13 <= 64
+    'siso_vb20_v120_cod': _coded(fused=False),
+    'simo_pb10': _simo(), 'simo_bu10': _simo(), 'simo_pb10x': _simo(),
+    'simo_vb10': _simo(tx=_TXC),                               # max delay 70 > 64
+    'simo_pb10hx': _simo(rx=_RXS2),                            # odd CP: no wave receiver
+    'simo_pb10_rx5': _simo(tx=_TXC, rx=_RXSEP, rx_H=_RXSEP, rx_block=_RXSEP),   # 5 RX > 4
+    'simo_pb10_rx3_15': _simo(rx_block=_RXS),                  # odd RX count: no pairs
+    'taps_0_1_63_64': _simo(), 'taps_single': _simo(),
+    'taps_0_65': _simo(tx=_TXC), 'taps_0_30_72': _simo(tx=_TXC),
+    'taps_0_73': _simo(tx=_TX), 'taps_nine': _simo(tx=_TX),   # txch_supported refuses
+    'taps_0_256': _siso(), 'taps_0_257': _siso(),
+    'siso_vb125': _siso(fused=False), 'siso_pa125h': _siso(fused=False), 'siso_vb125h': _siso(fused=False),   # N < 512
+    'siso_vb5': _siso(),
+}
+# float32: no wave kernel
+PATHS_F32 = {'siso_vb20': _siso(), 'siso_vb5': _siso(), 'siso_vb20_cod': _coded(wave_rx=False),
+             'simo_bu10': _simo(tx=_TXC, rx=_RXS2), 'simo_vb10': _simo(tx=_TXC, rx=_RXS2)}
+assert set(PATHS) == set(CASES)
+
+
+# ---------------------------------------------------------------------------
 # the oracle side (no GPU needed): computed once per case
 _ORACLE = {}
 _QS = {'QPSK': np.sqrt(2.0), '16-QAM': np.sqrt(10.0), '64-QAM': np.sqrt(42.0)}
@@ -322,6 +388,9 @@ def check_case(C, O, monkeypatch, name, variants, prec='f64'):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         r = plan.run(cs['snrs'], bits=dr['bits'], phases=dr['ph'], noise=dr['z'], capture=cap)
+        got, want = r.path, (PATHS if prec == 'f64' else PATHS_F32)[name][label]
+        assert (got['tx'], int(got['ch_fix']), got['rx']) == want, (name, prec, label, got)
+        assert got['dematch'] == ('none' if cs['chain'] != 'coded' else 'llr' if 'llr' in cap else 'zn'), (label, got)
         worst, worst_np = _compare(O, oc, r, cap, prec, f'{name}[{prec}]/{label}')
         print(f'profiles {name}[{prec}]/{label}: worst data_syms |d| / bound = {worst:.3g}, '
               f'noise_power rel err = {worst_np:.3g}')
@@ -435,8 +504,8 @@ def test_simo_bad_urban(C, oracle, monkeypatch):
 
 def test_simo_vehicular_b(C, oracle, monkeypatch):
     """max delay 70 > 64: tx_simo_w_supported refuses (TXSW_HALF window), so
-    k_ofdm_tx<double, 0, 4, false, 1, 1024, NP = 0> + k_chan_fix run
-    (tx_simo_w_fuses_fix must agree), then k_rx_frame_simo_w."""
+    k_ofdm_tx<double, 0, 4, false, 1, 1024, NP = 0> + k_chan_fix run, then
+    k_rx_frame_simo_w."""
     check_case(C, oracle, monkeypatch, 'simo_vb10', V_SIMO)
 
 
@@ -687,3 +756,30 @@ def test_simulate_siso_coded_ref_compat_r7_f32(C, golden_r7, name, ckw, prof, sn
         else:
             assert not r['crc_pass'] and int(g[k + '_crc'][0]) == 0, k
         assert np.array_equal(_state_head(), g[k + '_state'])
+
+
+# ---------------------------------------------------------------------------
+# 3. LTE_TX_STAGE is read per run, like every other switch
+def test_tx_stage_switch_is_read_per_run(C, oracle, monkeypatch):
+    """LTE_TX_STAGE=0, then unset, in one process on the coded per-symbol TX
+    (LTE_TX_FRAME=0, k_ofdm_tx<double, 1, ..>): the path goes from the coded
+    bits gathered through L1 / L2 to the stream staged in LDS, in that field
+    only, and both runs give the oracle's outcome."""
+    from lte_phy.engine import path_diff
+    oc = oracle_case(oracle, 'siso_pb20_cod')
+    plan, dr, cs = _plan(C, oc, 'f64'), oc['dr'], oc['cs']
+    for k in SWITCHES:
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv('LTE_TX_FRAME', '0')
+    runs = []
+    for stage in ('0', None):
+        if stage is None:
+            monkeypatch.delenv('LTE_TX_STAGE')
+        else:
+            monkeypatch.setenv('LTE_TX_STAGE', stage)
+        r = plan.run(cs['snrs'], bits=dr['bits'], phases=dr['ph'], noise=dr['z'], capture=A_CAP)
+        _compare(oracle, oc, r, A_CAP, 'f64', f'tx_stage={stage}')
+        runs.append(r.path)
+    assert runs[0]['tx'] == runs[1]['tx'] == _TXC
+    assert (runs[0]['tx_stage'], runs[1]['tx_stage']) == ('0', '1')
+    assert path_diff(*runs) == {'tx_stage'}

@@ -181,14 +181,21 @@ def test_channel_economised_sets_match_degree5(C, monkeypatch):
     import lte_phy
     rs = np.random.RandomState(7)
     xs = [(rs.randn(8 * 2192) + 1j * rs.randn(8 * 2192)) / np.sqrt(2) for _ in range(4)]
-    out = []
+    from lte_phy.engine import path_diff
+    from lte_phy.ofdm_core import _spatial_plan
+    plan = _spatial_plan(lte_phy.LTEConfig(bandwidth=20.0, modulation='64-QAM'), 'rayleigh_mp', 'Pedestrian_A', 3.0,
+                         2.0, 14, 14 * 999 * 6, 2)[0]
+    out, paths = [], []
     for econ in ('1', '0'):
         monkeypatch.setenv('LTE_CHT_ECON', econ)
+        paths.append(plan.path([10.0, 20.0]))   # the same links in a chain's plan: which channel kernel (nothing runs)
         cs = lte_phy.ChannelSimulator(channel_type='rayleigh_mp', snr_db=18.0, fs=30.72e6,
                                       itu_profile='Pedestrian_A', frequency_ghz=2.0, velocity_kmh=3.0,
                                       verbose=False, precision='f64')
         np.random.seed(99)
         ys, _ = cs.transmit_spatial_multiplexing(list(xs), num_rx=4)
         out.append(ys)
+    assert path_diff(*paths) == {'ch'}, paths
+    assert [p['ch'] for p in paths] == ['k_channel_tay,J=3,G=4,econ=1', 'k_channel_tay,J=3,G=4,econ=0']
     for a, b in zip(*out):
         assert np.linalg.norm(a - b) / np.linalg.norm(b) < 1e-14
