@@ -209,6 +209,22 @@ int lte_run(lte_plan *plan, const lte_run_args *args);
  * lp_fuse= ch= link_merge= rx= h_pilots= det_stage= dematch= (ch: fused,
  * k_channel_mimo or k_channel_tay,J=..,G=..,econ=..). */
 int lte_run_path(const lte_plan *plan, const lte_run_args *args, char *buf, int len);
+/* CRC early termination of the turbo decoder (ABI 3, additions; opt-in, off on
+ * a new plan; coded chains only: LTE_EINVAL otherwise).  With D(n) the
+ * decisions of a decode of n iterations, a code block stops at
+ * n* = min { n in 1..turbo_iters : the CRC-24 remainder of all K bits of D(n)
+ * is zero } (turbo_iters if none is, 0 for turbo_iters = 0) and the run
+ * returns D(n*).  The generator is gCRC24A for a transport block of one code
+ * block, gCRC24B for several.  D(n*) need not equal D(turbo_iters), and the
+ * all-zero word passes (zero-init CRC).  Max-log decoding only: lte_run
+ * refuses an early-stop plan with LTE_EUNSUP while lte_set_decoder_mode(0)
+ * holds.  lte_run_path appends " turbo=es" for such a plan. */
+int lte_plan_set_early_stop(lte_plan *plan, int on);
+int lte_plan_early_stop(const lte_plan *plan);   /* 1 / 0 */
+/* n* of the plan's last lte_run, [n_frames][n_cb] bytes (n = n_frames * n_cb);
+ * LTE_EINVAL when early stop is off, nothing has run since it was set, or n
+ * is not that run's size. */
+int lte_plan_turbo_iters_used(const lte_plan *plan, uint8_t *out, int64_t n);
 /* Per-kernel device time accumulated by lte_run while timing is on (HIP events
  * on the plan's stream).  names: comma-separated kernel names; ms/launches per
  * kernel in the same order.  n_max entries. */
@@ -278,6 +294,16 @@ int lte_bcjr_host(int K, int64_t ncb, const float *ls, const float *lp, const fl
 /* float64 turbo decode, bit-exact with turbo_decode (core/channel_coding/turbo_decoder.py:338-450):
  * the reference's unnormalised max-log recursion in its own operation order. */
 int lte_turbo_decode_host64(int K, int iters, int64_t ncb, const double *llr /*[ncb][3K+12]*/, uint8_t *bits);
+/* Turbo decode with CRC early termination (the rule at
+ * lte_plan_set_early_stop; same LLR layouts as the two entries above):
+ * crc_poly 0x1864CFB (gCRC24A) or 0x1800063 (gCRC24B); bits [ncb][K] = D(n*),
+ * iters_used [ncb] = n*.  K outside the 188 sizes, iters < 0, another
+ * crc_poly or a NULL pointer: LTE_EINVAL before the device is touched.
+ * LTE_EUNSUP under lte_set_decoder_mode(0). */
+int lte_turbo_decode_es_host64(int K, int iters, int64_t ncb, const double *llr /*[ncb][3K+12]*/, uint32_t crc_poly,
+                               uint8_t *bits, uint8_t *iters_used);
+int lte_turbo_decode_es_host(int K, int iters, int64_t ncb, const float *llr /*[ncb][3K+12]*/, uint32_t crc_poly,
+                             uint8_t *bits, uint8_t *iters_used);
 /* float64 single BCJR pass of any length n, a-posteriori output for every step:
  * LogMAPDecoder.decode (turbo_decoder.py:181-278) with return_extrinsic=False.
  * n = 0 is valid (nothing written), like the reference's zero-step recursion. */

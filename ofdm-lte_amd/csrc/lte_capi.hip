@@ -449,6 +449,11 @@ struct lte_plan {
   DBuf<int64_t> rows_dev;
   DBuf<uint32_t*> dec_ptrs;
   DBuf<int> kw_dev;
+  // CRC early termination (lte_plan_set_early_stop): per CB slot the iterations
+  // used [G][64] words; es_frames: frames of the last decoded run (0: none yet)
+  bool early_stop = false;
+  std::vector<DBuf<uint32_t>> es_used;
+  int es_frames = 0;
   // multi-antenna chains (lte_mimo.hip)
   bool mimo = false;
   // beamforming chain (lte_bf.hip)
@@ -506,6 +511,19 @@ template <> ChainBufs<double>& cbuf<double>(lte_plan* p) { return p->c64; }
 
 // chunk width of the plan's decoder rows (allocated for ceil(max_frames / 64) groups)
 int turbo_plan_ch(const lte_plan* p) { return turbo_chunk((p->d.max_frames + 63) / 64); }
+
+// the plan's decoder launch: turbo_iters iterations, or (early_stop) until each
+// code block's CRC-24 holds -- gCRC24A for a transport block of one code block,
+// gCRC24B for several (segmentation.py:74-263)
+int plan_launch_turbo(lte_plan* p, hipStream_t s, const std::vector<TurboJob>& jobs, int B, int f64) {
+  if (!p->early_stop) return launch_turbo_jobs(s, jobs.data(), p->C, p->d.turbo_iters, TM_DEC1, f64);
+  std::vector<uint32_t*> used(p->C);
+  std::vector<int> nv(p->C, B);
+  for (int r = 0; r < p->C; ++r) used[r] = p->es_used[r].p;
+  p->es_frames = B;
+  return launch_turbo_jobs_es(s, jobs.data(), used.data(), nv.data(), p->C, p->d.turbo_iters, f64,
+                              p->C == 1 ? CRC24A_POLY : CRC24B_POLY);
+}
 
 void collect_timing(lte_plan* p) {
   for (auto& u : p->evuse) {
@@ -1525,6 +1543,7 @@ int lte_plan_destroy(lte_plan* p) {
   p->frame_err.release(); p->frame_crc.release(); p->snr_idx.release(); p->nvar.release(); p->fid.release(); p->counts.release();
   p->cap_bits.release();
   for (auto& b : p->decb) b.release();
+  for (auto& b : p->es_used) b.release();
   p->rows_dev.release(); p->dec_ptrs.release(); p->kw_dev.release();
   p->m_np.release(); p->m_ppos.release(); p->m_pseg.release(); p->m_pval.release(); p->m_pval64.release();
   p->m_pig.release(); p->m_pig64.release(); p->m_W.release(); p->bf_cb.release();
@@ -1546,6 +1565,47 @@ int lte_plan_info(const lte_plan* p, int64_t* info) {
 int lte_plan_precision(const lte_plan* p) {
   if (!p) return fail(LTE_EINVAL, "null plan");
   return p->f64 ? LTE_PREC_F64 : LTE_PREC_F32;
+}
+
+int lte_plan_set_early_stop(lte_plan* p, int on) {
+  if (!p) return fail(LTE_EINVAL, "null plan");
+  if (p->d.chain != LTE_CHAIN_CODED && p->d.chain != LTE_CHAIN_SFBC_CODED)
+    return fail(LTE_EINVAL, "early stop applies to the coded chains only (nothing is decoded in this plan)");
+  if (on && p->es_used.empty()) {
+    std::vector<DBuf<uint32_t>> u(p->C);
+    const size_t G = ((size_t)p->d.max_frames + 63) / 64;
+    bool bad = false;
+    for (auto& b : u) bad |= b.alloc(G * 64) != 0;
+    if (bad) {
+      for (auto& b : u) b.release();
+      return fail(LTE_ENOMEM, "early-stop iteration counts");
+    }
+    p->es_used.swap(u);
+  }
+  if (on && p->d.turbo_iters > 255) return fail(LTE_EUNSUP, "early stop reports iterations as bytes: turbo_iters <= 255");
+  p->early_stop = on != 0;
+  p->es_frames = 0;
+  return LTE_OK;
+}
+
+int lte_plan_early_stop(const lte_plan* p) {
+  if (!p) return fail(LTE_EINVAL, "null plan");
+  return p->early_stop ? 1 : 0;
+}
+
+int lte_plan_turbo_iters_used(const lte_plan* p, uint8_t* out, int64_t n) {
+  if (!p || !out) return fail(LTE_EINVAL, "null argument");
+  if (!p->early_stop) return fail(LTE_EINVAL, "early stop is off for this plan");
+  if (p->es_frames <= 0) return fail(LTE_EINVAL, "no decoded run since early stop was set");
+  const int B = p->es_frames;
+  if (n != (int64_t)B * p->C)
+    return fail(LTE_EINVAL, "n must be n_frames * n_cb of the last run (" + std::to_string((int64_t)B * p->C) + ")");
+  std::vector<uint32_t> h(B);
+  for (int r = 0; r < p->C; ++r) {
+    HIPCHK(hipMemcpy(h.data(), p->es_used[r].p, (size_t)B * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; ++b) out[(size_t)b * p->C + r] = (uint8_t)h[b];
+  }
+  return LTE_OK;
 }
 
 int lte_timing_enable(lte_plan* p, int on) {
@@ -1971,7 +2031,7 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, in
     }
     {
       Timer t(p, KN_TURBO);
-      LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, sizeof(R) == 8 ? 1 : 0));
+      LCHK(plan_launch_turbo(p, s, jobs, B, sizeof(R) == 8 ? 1 : 0));
     }
     {
       Timer t(p, KN_CRC);
@@ -2343,7 +2403,7 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
     }
     {
       Timer t(p, KN_TURBO);
-      LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, sizeof(R) == 8 ? 1 : 0));
+      LCHK(plan_launch_turbo(p, s, jobs, B, sizeof(R) == 8 ? 1 : 0));
     }
     {
       Timer t(p, KN_CRC);
@@ -2453,6 +2513,8 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
   p->evuse.clear();
   if (logmap_on() && (d.chain == LTE_CHAIN_CODED || d.chain == LTE_CHAIN_SFBC_CODED) && !p->f64)
     return fail(LTE_EUNSUP, "exact log-MAP decoding runs in float64 plans only");
+  if (logmap_on() && p->early_stop)
+    return fail(LTE_EUNSUP, "CRC early termination runs the max-log decoders only (set_decoder_mode(True))");
   const Knobs knobs = read_knobs();   // the environment switches, once per run
   if (!p->mimo && !p->bf) {
     const SisoPath path = select_siso(p, a, knobs);
@@ -2498,6 +2560,8 @@ int lte_run_path(const lte_plan* p, const lte_run_args* a, char* buf, int len) {
                       MIMO_TX_NAME[s.tx], s.lp_fuse, ch, s.sfbc_merge, MIMO_RX_NAME[s.rx], s.h_pilots, s.det_stage,
                       p->d.chain != LTE_CHAIN_SFBC_CODED ? "none" : s.zn ? "zn" : "llr");
   }
+  // the decoder family is named only when it is not the default one
+  if (p->early_stop && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " turbo=es");
   return n < len ? n : len - 1;
 }
 
@@ -2825,9 +2889,11 @@ int lte_turbo_encode_host(int K, int64_t ncb, const uint8_t* bits, uint8_t* out)
 
 // Host-side layout conversion [ncb][3K+12] -> decoder rows, shared by the
 // turbo entry points.  T = float (fast mode) / double (the reference's precision).
+// es_used set (mode TM_DEC1): the early-stop decoder with generator es_poly
+// (CRC24A_POLY / CRC24B_POLY), the iterations used per code block to es_used.
 template <class T>
 static int turbo_host_run(int K, int iters, int64_t ncb, const T* llr, const T* ls, const T* lp, const T* la,
-                          int mode, uint8_t* bits, T* app) {
+                          int mode, uint8_t* bits, T* app, uint32_t es_poly = 0, uint8_t* es_used = nullptr) {
   int f1, f2;
   if (!qpp_lookup(K, &f1, &f2)) return fail(LTE_EINVAL, "Invalid interleaver size K=" + std::to_string(K));
   if (ncb < 0) return fail(LTE_EINVAL, "bad ncb");
@@ -2863,17 +2929,27 @@ static int turbo_host_run(int K, int iters, int64_t ncb, const T* llr, const T* 
     }
   }
   DBuf<T> db, dck;
-  DBuf<uint32_t> dbits;
+  DBuf<uint32_t> dbits, dused;
   const int KW = turbo_kw(K);
   if (db.alloc(h.size()) || dck.alloc((size_t)turbo_galloc(G) * turbo_nwin(K) * turbo_ck_rows(f64) * 64) ||
-      dbits.alloc((size_t)G * KW * 64))
+      dbits.alloc((size_t)G * KW * 64) || (es_used && dused.alloc((size_t)G * 64))) {
+    db.release(); dck.release(); dbits.release(); dused.release();
     return fail(LTE_ENOMEM, "turbo buffers");
+  }
   int rc = LTE_OK;
   std::vector<uint32_t> hb((size_t)G * KW * 64);
+  const TurboJob job{db.p, dck.p, dbits.p, K, f1, f2, G, ch};
+  const int nv = (int)ncb;
   if (hipMemcpy(db.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess ||
-      launch_turbo(nullptr, db.p, dck.p, dbits.p, K, f1, f2, iters, G, mode, f64, ch) ||
+      (es_used ? launch_turbo_jobs_es(nullptr, &job, &dused.p, &nv, 1, iters, f64, es_poly)
+               : launch_turbo_jobs(nullptr, &job, 1, iters, mode, f64)) ||
       hipDeviceSynchronize() != hipSuccess)
     rc = fail(LTE_EHIP, std::string("turbo failed: ") + hipGetErrorString(hipGetLastError()));
+  if (rc == LTE_OK && es_used) {
+    std::vector<uint32_t> hu((size_t)G * 64);
+    if (hipMemcpy(hu.data(), dused.p, hu.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(LTE_EHIP, "copy");
+    for (int64_t c = 0; c < ncb && rc == LTE_OK; ++c) es_used[c] = (uint8_t)hu[c];
+  }
   if (rc == LTE_OK) {
     if (mode == TM_APP) {
       if (hipMemcpy(h.data(), db.p, h.size() * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess)
@@ -2889,11 +2965,44 @@ static int turbo_host_run(int K, int iters, int64_t ncb, const T* llr, const T* 
         }
     }
   }
-  db.release(); dck.release(); dbits.release();
+  db.release(); dck.release(); dbits.release(); dused.release();
   return rc;
 }
 
+// argument checks of the early-stop entries, all before the device is touched;
+// crc_poly with its x^24 term (as lte_crc_host takes it) -> *poly without
+static int turbo_es_args(int K, int iters, int64_t ncb, const void* llr, uint32_t crc_poly, const uint8_t* bits,
+                         const uint8_t* used, uint32_t* poly) {
+  int f1, f2;
+  if (!qpp_lookup(K, &f1, &f2)) return fail(LTE_EINVAL, "Invalid interleaver size K=" + std::to_string(K));
+  if (iters < 0 || iters > 255) return fail(LTE_EINVAL, "iters must be in 0..255");
+  if (ncb < 0 || ncb > (int64_t)1 << 30) return fail(LTE_EINVAL, "bad ncb");
+  if (crc_poly != 0x1864CFBu && crc_poly != 0x1800063u)
+    return fail(LTE_EINVAL, "crc_poly must be gCRC24A (0x1864CFB) or gCRC24B (0x1800063)");
+  if (!llr || !bits || !used) return fail(LTE_EINVAL, "null argument");
+  if (logmap_on()) return fail(LTE_EUNSUP, "CRC early termination runs the max-log decoders only");
+  *poly = crc_poly & 0xFFFFFFu;
+  return LTE_OK;
+}
+
 extern "C" {
+
+int lte_turbo_decode_es_host(int K, int iters, int64_t ncb, const float* llr, uint32_t crc_poly, uint8_t* bits,
+                             uint8_t* iters_used) {
+  uint32_t poly;
+  const int rc = turbo_es_args(K, iters, ncb, llr, crc_poly, bits, iters_used, &poly);
+  if (rc) return rc;
+  return turbo_host_run<float>(K, iters, ncb, llr, nullptr, nullptr, nullptr, TM_DEC1, bits, nullptr, poly, iters_used);
+}
+
+int lte_turbo_decode_es_host64(int K, int iters, int64_t ncb, const double* llr, uint32_t crc_poly, uint8_t* bits,
+                               uint8_t* iters_used) {
+  uint32_t poly;
+  const int rc = turbo_es_args(K, iters, ncb, llr, crc_poly, bits, iters_used, &poly);
+  if (rc) return rc;
+  return turbo_host_run<double>(K, iters, ncb, llr, nullptr, nullptr, nullptr, TM_DEC1, bits, nullptr, poly,
+                                iters_used);
+}
 
 int lte_turbo_decode_host(int K, int iters, int64_t ncb, const float* llr, uint8_t* bits) {
   if (iters < 0 || (ncb > 0 && (!llr || !bits))) return fail(LTE_EINVAL, "bad arguments");

@@ -270,9 +270,14 @@ struct RowPtr {
 // MODE TM_FINAL: the decoder-1 a-posteriori pass that ends a decode; it also
 // packs the hard decisions L < 0 MSB-first into `bo` (words [kw][64 lanes]),
 // storing each word as the backward sweep reaches its bit 0 (no re-read pass).
-template <class T, int MODE, bool LM = false, int CH = TURBO_CH>
+// ES (the early-stop kernels, MODE TM_DEC1 only): the decoder-1 pass packs the
+// same decisions next to its extrinsic store -- its L is TM_FINAL's L, same
+// inputs, same operations -- and only lanes with `live` set store their words.
+template <class T, int MODE, bool LM = false, int CH = TURBO_CH, bool ES = false>
 __device__ __forceinline__ void half_pass(T* __restrict__ wbase, T* __restrict__ wck, int slot, int lane, int K,
-                                          int f1, int f2, bool first, uint32_t* __restrict__ bo = nullptr) {
+                                          int f1, int f2, bool first, uint32_t* __restrict__ bo = nullptr,
+                                          bool live = true) {
+  static_assert(!ES || MODE == TM_DEC1, "early stop packs in the decoder-1 pass");
   using TT = TurboT<T>;
   using DRow = RowPtr<T, RS * CH * (int)sizeof(T), LTE_TURBO_CPOL>;   // the block arrays' rows (CH groups side by side)
   constexpr int TSUB = TT::TSUB, SW = TW * TSUB, CK = TT::CK, CK0 = 8 - CK;   // CK0: first stored state
@@ -295,7 +300,7 @@ __device__ __forceinline__ void half_pass(T* __restrict__ wbase, T* __restrict__
   const bool use_la = !first;
   RowPtr<uint32_t> bout{};
   uint32_t acc = 0;
-  if (MODE == TM_FINAL) bout = RowPtr<uint32_t>{make_rsrc(bo, (uint32_t)(turbo_kw(K) * RS * 4)), 0, lane * 4};
+  if (MODE == TM_FINAL || ES) bout = RowPtr<uint32_t>{make_rsrc(bo, (uint32_t)(turbo_kw(K) * RS * 4)), 0, lane * 4};
 
   // ---------------- forward pass (alpha[0] = delta_0, turbo_decoder.py:214-218)
   T a[8];
@@ -467,6 +472,7 @@ __device__ __forceinline__ void half_pass(T* __restrict__ wbase, T* __restrict__
           const T L = bstep<T, LM>(b, c, A[j]);
           if (MODE == TM_DEC1) {
             LE.st(k, ((T)0.5 * L - la[i]) - ls[i]);
+            if constexpr (ES) acc |= (L < (T)0 ? 1u : 0u) << (31 - (k & 31));
           } else if (MODE == TM_DEC2) {
             dd = modsub(dd, tf2, K);
             pp = modsub(pp, dd, K);   // pp = pi(k)
@@ -481,10 +487,14 @@ __device__ __forceinline__ void half_pass(T* __restrict__ wbase, T* __restrict__
           }
         }
       }
-      if (MODE == TM_FINAL) {   // words start on sub-window boundaries (32 = 4 * TW)
+      if (MODE == TM_FINAL || ES) {   // words start on sub-window boundaries (32 = 4 * TW)
         const int k = k0 + m * TW;
         if ((k & 31) == 0) {
-          bout.st(k >> 5, acc);
+          if constexpr (ES) {
+            if (live) bout.st(k >> 5, acc);
+          } else {
+            bout.st(k >> 5, acc);
+          }
           acc = 0;
         }
       }
@@ -562,6 +572,95 @@ __global__ __launch_bounds__(256, 1) void k_turbo64_logmap(TurboJobs jobs, int i
   turbo_body<double, true, CH>(jobs, iters, mode);
 }
 
+// ---------------------------------------------------------------------------
+// CRC early termination (opt-in).  D(n), the decisions a decode
+// of n iterations returns, are the signs of TM_FINAL's L after n iterations;
+// the decoder-1 pass of iteration n + 1 computes that same L, so these kernels
+// pack it there (half_pass<.., ES>), and after the pass each lane that is not
+// done yet reads its own ceil(K / 32) packed words back as coalesced rows and
+// runs them through the CRC-24 register (slice-by-4 tables in LDS, filled once
+// per block).  Register 0 <=> the K bits are a multiple of the generator (the
+// last word's zero padding multiplies by a power of x, which is invertible).
+// A lane whose check holds is done: its words and its iteration count stay as
+// they are.  A wave whose 64 lanes are done returns.  Lanes past the job's
+// last code block are done from the start and store nothing.
+// One wave per block (64 threads), unlike the fixed decoders' four: a block's
+// registers are free for the next block only when its last wave has left, so
+// with four waves a block one straggler would hold three finished SIMDs idle
+// (measured at 22 dB on the config-2 plan: 247 ms with 256-thread blocks).
+struct TurboEs {
+  uint32_t* used[TURBO_MAX_JOBS];   // [G][64] iterations used, one word per lane
+  int nv[TURBO_MAX_JOBS];           // code blocks (valid lanes over all groups) of the job
+  uint32_t poly;                    // CRC-24 generator without x^24
+};
+
+template <class T, int CH>
+__device__ __forceinline__ void turbo_body_es(const TurboJobs& jobs, const TurboEs& es, int iters, uint32_t* crc_t) {
+  crc24_slice4_fill(crc_t, es.poly);
+  __syncthreads();   // the only barrier (one wave)
+  const int wg = blockIdx.x;
+  const int lane = threadIdx.x;
+  if (wg >= jobs.prefix[jobs.n]) return;
+  int r = 0;
+  while (wg >= jobs.prefix[r + 1]) ++r;
+  const TurboJob jb = jobs.j[r];
+  const int g = wg - jobs.prefix[r];
+  const int K = jb.K, kw = turbo_kw(K);
+  const int slot = g % CH;
+  T* base = reinterpret_cast<T*>(jb.blk) + turbo_elem<CH>(turbo_rows(K), g - slot, 0);
+  T* ck = reinterpret_cast<T*>(jb.ck) + turbo_elem<CH>(turbo_nwin(K) * TurboT<T>::CK, g - slot, 0);
+  uint32_t* bo = jb.bits + (size_t)g * kw * RS;
+  const RowPtr<uint32_t> words{make_rsrc(bo, (uint32_t)(kw * RS * 4)), 0, lane * 4};
+  const RowPtr<uint32_t> used{make_rsrc(es.used[r] + (size_t)g * RS, (uint32_t)(RS * 4)), 0, lane * 4};
+  bool done = g * RS + lane >= es.nv[r];
+  if (__builtin_amdgcn_ballot_w64(!done) == 0) return;
+  for (int it = 0;; ++it) {
+    // the decoder-1 pass of iteration it + 1 = the final pass after `it`
+    // iterations: from it = 1 on (and at it = iters, where the decode ends)
+    // its decisions are D(it)
+    const bool last = it == iters;
+    half_pass<T, TM_DEC1, false, CH, true>(base, ck, slot, lane, K, jb.f1, jb.f2, it == 0, bo,
+                                           !done && (it > 0 || last));
+    if (last) {
+      if (!done) used.st(0, (uint32_t)it);
+      return;
+    }
+    if (it > 0) {
+      uint32_t c = 0;
+#pragma unroll 4
+      for (int w = 0; w < kw; ++w) c = crc24_slice4(crc_t, c, words.ld(w));
+      if (!done && c == 0) {
+        used.st(0, (uint32_t)it);
+        done = true;
+      }
+      if (__builtin_amdgcn_ballot_w64(!done) == 0) return;
+    }
+    half_pass<T, TM_DEC2, false, CH>(base, ck, slot, lane, K, jb.f1, jb.f2, false);
+  }
+}
+
+template <int CH>
+__global__ __launch_bounds__(64, LTE_TURBO32_WAVES == 3 ? 2 : 1) void k_turbo_es(TurboJobs jobs, TurboEs es,
+                                                                                   int iters) {
+  __shared__ uint32_t crc_t[1024];
+#if LTE_TURBO32_WAVES == 2
+  asm volatile("" ::: "a47");
+#elif LTE_TURBO32_WAVES == 1
+  asm volatile("" ::: "a127");
+#endif
+  turbo_body_es<float, CH>(jobs, es, iters, crc_t);
+}
+
+template <int CH>
+__global__ __launch_bounds__(64, LTE_TURBO64_ONE_WAVE ? 1 : 2) void k_turbo64_es(TurboJobs jobs, TurboEs es,
+                                                                                   int iters) {
+  __shared__ uint32_t crc_t[1024];
+#if LTE_TURBO64_ONE_WAVE
+  asm volatile("" ::: "a31");
+#endif
+  turbo_body_es<double, CH>(jobs, es, iters, crc_t);
+}
+
 // decoder arithmetic of the f64 entry points and chains: max-log-MAP (the
 // reference's default, USE_MAX_LOG_MAP = True) or exact log-MAP
 static int g_logmap = 0;
@@ -591,6 +690,43 @@ int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int
       if (f64 && g_logmap) hipLaunchKernelGGL(k_turbo64_logmap<1>, grid, dim3(256), 0, s, J, iters, mode);
       else if (f64) hipLaunchKernelGGL(k_turbo64<1>, grid, dim3(256), 0, s, J, iters, mode);
       else hipLaunchKernelGGL(k_turbo<1>, grid, dim3(256), 0, s, J, iters, mode);
+    } else {
+      return (int)hipErrorInvalidValue;
+    }
+    const int e = (int)hipGetLastError();
+    if (e) return e;
+  }
+  return 0;
+}
+
+// the early-stop decoders: used[i] / nv[i] per job (TurboEs), poly CRC24A_POLY / CRC24B_POLY
+int launch_turbo_jobs_es(hipStream_t s, const TurboJob* jobs, uint32_t* const* used, const int* nv, int n, int iters,
+                         int f64, uint32_t poly) {
+  if (g_logmap || iters < 0) return (int)hipErrorInvalidValue;   // max-log only (the callers refuse it first)
+  for (int o = 0; o < n; o += TURBO_MAX_JOBS) {
+    TurboJobs J{};
+    TurboEs E{};
+    E.poly = poly;
+    J.n = n - o < TURBO_MAX_JOBS ? n - o : TURBO_MAX_JOBS;
+    J.prefix[0] = 0;
+    for (int i = 0; i < J.n; ++i) {
+      J.j[i] = jobs[o + i];
+      J.prefix[i + 1] = J.prefix[i] + jobs[o + i].G;
+      E.used[i] = used[o + i];
+      E.nv[i] = nv[o + i];
+    }
+    const int waves = J.prefix[J.n];
+    if (waves == 0) continue;
+    const int ch = J.j[0].ch;
+    for (int i = 1; i < J.n; ++i)
+      if (J.j[i].ch != ch) return (int)hipErrorInvalidValue;
+    const dim3 grid(waves), block(64);   // one wave per block (turbo_body_es)
+    if (ch == TURBO_CH) {
+      if (f64) hipLaunchKernelGGL(k_turbo64_es<TURBO_CH>, grid, block, 0, s, J, E, iters);
+      else hipLaunchKernelGGL(k_turbo_es<TURBO_CH>, grid, block, 0, s, J, E, iters);
+    } else if (ch == 1) {
+      if (f64) hipLaunchKernelGGL(k_turbo64_es<1>, grid, block, 0, s, J, E, iters);
+      else hipLaunchKernelGGL(k_turbo_es<1>, grid, block, 0, s, J, E, iters);
     } else {
       return (int)hipErrorInvalidValue;
     }

@@ -227,6 +227,13 @@ struct TurboJobs {
   int prefix[TURBO_MAX_JOBS + 1];
 };
 int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int mode, int f64);
+// Full decode with CRC early termination (k_turbo64_es / k_turbo_es, max-log
+// only): a code block stops after the first iteration n >= 1 whose decisions
+// have CRC-24 remainder zero over all K bits (poly: CRC24A_POLY / CRC24B_POLY).
+// used[i]: job i's iterations used, [G][64] words (lanes >= nv[i], the job's
+// code-block count, are never written, nor are their bits).
+int launch_turbo_jobs_es(hipStream_t s, const TurboJob* jobs, uint32_t* const* used, const int* nv, int n, int iters,
+                         int f64, uint32_t poly);
 // rate_dematching_turbo for any E (repeats summed in order): llr [ncb][E] -> out [ncb][n_out]
 int launch_rate_dematch(hipStream_t s, const double* llr, int E, int Ncb, int n_out, const int32_t* src0, int64_t ncb,
                         double* out);

@@ -296,6 +296,30 @@ def turbo_decode_batch(llrs, K, num_iterations=8, precision=None):
     return out
 
 
+def turbo_decode_early_stop(llr, K, max_iterations=8, crc='24B', *, precision=None):
+    """Turbo decode with CRC early termination on the GPU (not a reference
+    name, so not in __all__).  With D(n) = turbo_decode(llr, K, n), the decode
+    stops at n* = the first n in 1..max_iterations for which the CRC-24
+    remainder of all K bits of D(n) is zero (crc '24A' / '24B'), or at
+    max_iterations, and returns (D(n*), n*).  D(n*) is not always
+    D(max_iterations), and the all-zero word passes (zero-init CRC).  llr
+    [3K+12] -> (bits [K], int), or [ncb][3K+12] -> (bits [ncb, K], uint8 [ncb]).
+    Float64 unless precision='f32'; max-log-MAP only."""
+    polys = {'24A': CRC24A_POLYNOMIAL, '24B': CRC24B_POLYNOMIAL}
+    if crc not in polys:
+        raise ValueError(f"crc must be '24A' or '24B', got {crc!r}")
+    C.device_init()
+    prec = C.precision(precision)
+    a = np.asarray(llr)
+    dt, ct, f = (np.float64, C.F64, C.load().lte_turbo_decode_es_host64) if prec == 'f64' else \
+        (np.float32, C.F32, C.load().lte_turbo_decode_es_host)
+    L = np.ascontiguousarray(a, dtype=dt).reshape(-1, 3 * K + 12)
+    bits = np.zeros((L.shape[0], K), dtype=np.uint8)
+    used = np.zeros(L.shape[0], dtype=np.uint8)
+    C.check(f(K, int(max_iterations), L.shape[0], C.ptr(L, ct), polys[crc], C.ptr(bits, C.U8), C.ptr(used, C.U8)))
+    return (bits[0], int(used[0])) if a.ndim == 1 else (bits, used)
+
+
 class LogMAPDecoder:
     """turbo_decoder.py:118-335: one BCJR pass of the 8-state RSC over any
     length (tail steps included), float64 on the GPU (lte_bcjr_host64), max*

@@ -24,7 +24,7 @@ class RunResult(dict):
 class Plan:
     def __init__(self, *, N, Nc, cp_len, bps, n_sym, chain, channel, num_rx=1, delays=(), gains=(), fD=0.0,
                  fs=0.0, n_bits, turbo_iters=8, max_frames=1, cell_id=0, num_tx=1, rank=0, detector=0,
-                 precoder=(), sc_fdm=0, bf_adaptive=0, no_equalization=0, precision=None):
+                 precoder=(), sc_fdm=0, bf_adaptive=0, no_equalization=0, precision=None, early_stop=False):
         C.device_init()
         d = C.PlanDesc()
         d.N, d.Nc, d.cp_len, d.bps, d.n_sym = N, Nc, cp_len, bps, n_sym
@@ -81,6 +81,11 @@ class Plan:
         self.cp_len, self.channel = int(cp_len), int(channel)
         self.n_paths, self.max_delay = len(delays), int(max(delays)) if len(delays) else 0
         self.pilots_per_tx = -(-self.Np // min(max(1, self.num_tx), 4))
+        # CRC early termination of the turbo decoder (lte_plan_set_early_stop; coded
+        # chains only): run() then also returns 'turbo_iters_used' [B, n_cb]
+        self.early_stop = bool(early_stop)
+        if self.early_stop:
+            C.check(C.load().lte_plan_set_early_stop(h, 1))
 
     def __del__(self):
         try:
@@ -96,6 +101,10 @@ class Plan:
         a, out, keep = self._args(snr_db, **kw)
         C.check(C.load().lte_run(self.h, ctypes.byref(a)))
         out.path = self._path(a)
+        if self.early_stop and (a.stages & C.STAGE_RX):
+            used = np.zeros((a.n_frames, self.n_cb), dtype=np.uint8)
+            C.check(C.load().lte_plan_turbo_iters_used(self.h, C.ptr(used, C.U8), used.size))
+            out['turbo_iters_used'] = used
         del keep
         return out
 
@@ -229,6 +238,7 @@ _CACHE_MAX = 8
 
 def get_plan(**kw):
     kw['precision'] = C.precision_of(kw.get('precision'))   # resolved now: part of the cache key
+    kw['early_stop'] = bool(kw.get('early_stop', False))   # likewise: an early-stop plan is never a fixed one
     key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple, np.ndarray)) else v) for k, v in kw.items()))
     p = _CACHE.get(key)
     if p is None:

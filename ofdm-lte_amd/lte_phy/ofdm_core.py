@@ -505,7 +505,7 @@ class OFDMSimulator:
     def Nd(self):
         return len(self.grid._data)
 
-    def _plan(self, chain, n_sym, n_bits, num_rx=1, max_frames=1, iters=8):
+    def _plan(self, chain, n_sym, n_bits, num_rx=1, max_frames=1, iters=8, early_stop=False):
         """SC-FDM (enable_sc_fdm / mode 'sc-fdm') reaches the uncoded SISO / SIMO
         transmitters and the SISO receiver; simulate_siso_coded ignores it, as
         the reference does (lte_plan_desc.sc_fdm, include/lte_phy.h)."""
@@ -517,7 +517,8 @@ class OFDMSimulator:
         return get_plan(N=cfg.N, Nc=cfg.Nc, cp_len=cfg.cp_length, bps=cfg.bits_per_symbol, n_sym=n_sym,
                         chain=chain, channel=ch.kind, num_rx=num_rx, delays=tuple(ch.delays),
                         gains=tuple(ch.gains), fD=ch.fD, fs=cfg.fs, n_bits=n_bits, turbo_iters=iters,
-                        max_frames=max_frames, sc_fdm=sc, no_equalization=noeq, precision=self.precision)
+                        max_frames=max_frames, sc_fdm=sc, no_equalization=noeq, precision=self.precision,
+                        early_stop=early_stop)
 
     def _ref_draws(self, L, num_rx=1):
         """Exactly the global-RNG consumption of one reference simulate_* call:
@@ -655,12 +656,13 @@ class OFDMSimulator:
         return res
 
     # -------------------------------------------------------------- SFBC (config 4)
-    def _sfbc_plan(self, n_sym, n_bits, num_rx, coded=False, max_frames=1, iters=8):
+    def _sfbc_plan(self, n_sym, n_bits, num_rx, coded=False, max_frames=1, iters=8, early_stop=False):
         cfg, ch = self.config, self.channels[0]
         return get_plan(N=cfg.N, Nc=cfg.Nc, cp_len=cfg.cp_length, bps=cfg.bits_per_symbol, n_sym=n_sym,
                         chain=C.CHAIN_SFBC_CODED if coded else C.CHAIN_SFBC, channel=ch.kind, num_rx=num_rx,
                         num_tx=2, delays=tuple(ch.delays), gains=tuple(ch.gains), fD=ch.fD, fs=cfg.fs,
-                        n_bits=n_bits, turbo_iters=iters, max_frames=max_frames, precision=self.precision)
+                        n_bits=n_bits, turbo_iters=iters, max_frames=max_frames, precision=self.precision,
+                        early_stop=early_stop)
 
     def _simulate_sfbc(self, bits, snr_db, num_rx, mode):
         """simulate_miso (core/ofdm_core.py:1850-2047) / simulate_mimo (:2049-2258)
@@ -786,7 +788,7 @@ class OFDMSimulator:
                  n_bits: Optional[int] = None, frames_per_call: int = 4096, rank: int = 0, world_size: int = 1,
                  turbo_iters: int = 8, mimo: Optional[str] = None, velocity_kmh: float = 3,
                  frequency_ghz: float = 2.0, spatial: Optional[Dict] = None,
-                 beamforming: Optional[Dict] = None) -> Dict:
+                 beamforming: Optional[Dict] = None, early_stop: bool = False) -> Dict:
         """Device-resident Monte-Carlo BER/BLER grid (SNR x trials).  Frame
         (s, t) has global id s*num_trials + t; all randomness is Philox keyed by
         (seed, id), so results are identical for any sharding.  With
@@ -801,7 +803,18 @@ class OFDMSimulator:
         {'num_tx': 4, 'num_rx': 4, 'rank': 4, 'detector': 'MMSE', 'pmi': 0}.
         mimo='beamforming': simulate_beamforming's frequency-domain chain, H ~
         CN(0, 1) per frame; `beamforming` overrides {'num_tx': 4, 'num_rx': 1,
-        'update_mode': 'adaptive'}."""
+        'update_mode': 'adaptive'}.
+
+        early_stop=True (coded, mimo None or 'sfbc'): the turbo decoder stops each
+        code block at the first iteration n* in 1..turbo_iters whose decisions
+        pass the block's CRC-24 (turbo_iters if none does) and returns those
+        decisions -- not always the ones turbo_iters iterations give.  The result
+        then also holds 'turbo_iters_hist' (uint64 [S, turbo_iters + 1]: this
+        rank's code blocks by n* per SNR point; all-reduce it like `counts`) and
+        'turbo_iters_mean' [S]."""
+        if early_stop and not (coded and mimo in (None, 'sfbc')):
+            raise ValueError("early_stop needs a coded chain (coded=True with mimo=None or mimo='sfbc'): "
+                             "nothing is decoded here")
         snrs = np.atleast_1d(np.asarray(snr_range, dtype=np.float64))
         S, T = len(snrs), int(num_trials)
         cfg = self.config
@@ -809,7 +822,8 @@ class OFDMSimulator:
             res = self.Nd & ~1
             if coded:
                 nb = int(n_bits or 27760)
-                plan = self._sfbc_plan(0, nb, num_rx, coded=True, max_frames=frames_per_call, iters=turbo_iters)
+                plan = self._sfbc_plan(0, nb, num_rx, coded=True, max_frames=frames_per_call, iters=turbo_iters,
+                                       early_stop=early_stop)
             else:
                 nb = int(n_bits or SLOT_SIZE * res * cfg.bits_per_symbol)
                 plan = self._sfbc_plan(int(np.ceil(nb / (res * cfg.bits_per_symbol))), nb, num_rx,
@@ -839,7 +853,8 @@ class OFDMSimulator:
             raise ValueError(f"unknown mimo mode {mimo!r}")
         elif coded:
             nb = int(n_bits or 27760)
-            plan = self._plan(C.CHAIN_CODED, 0, nb, max_frames=frames_per_call, iters=turbo_iters)
+            plan = self._plan(C.CHAIN_CODED, 0, nb, max_frames=frames_per_call, iters=turbo_iters,
+                              early_stop=early_stop)
         else:
             nb = int(n_bits or SLOT_SIZE * self.Nd * cfg.bits_per_symbol)
             n_sym = int(np.ceil(nb / (self.Nd * cfg.bits_per_symbol)))
@@ -847,16 +862,24 @@ class OFDMSimulator:
             plan = self._plan(chain, n_sym, nb, num_rx=num_rx, max_frames=frames_per_call)
         ids = np.array([s * T + t for s in range(S) for t in trial_shard(T, rank, world_size)], dtype=np.uint64)
         counts = np.zeros((S, 4), dtype=np.uint64)
+        hist = np.zeros((S, int(turbo_iters) + 1), dtype=np.uint64) if early_stop else None
         for i in range(0, len(ids), frames_per_call):
             chunk = ids[i:i + frames_per_call]
             si = (chunk // T).astype(np.int32)
             r = plan.run(snrs[si], snr_index=si, n_snr=S, seed=seed, frame_ids=chunk)
             counts += r['counts']
+            if early_stop:
+                used = r['turbo_iters_used']
+                np.add.at(hist, (np.repeat(si, used.shape[1]), used.ravel()), 1)
         with np.errstate(divide='ignore', invalid='ignore'):
             ber = counts[:, 0] / np.maximum(counts[:, 1], 1)
             bler = counts[:, 2] / np.maximum(counts[:, 3], 1)
-        return {'snr_db': snrs, 'counts': counts, 'ber': ber, 'bler': bler, 'bit_errors': counts[:, 0],
-                'bits': counts[:, 1], 'block_errors': counts[:, 2], 'blocks': counts[:, 3], 'plan': plan}
+        out = {'snr_db': snrs, 'counts': counts, 'ber': ber, 'bler': bler, 'bit_errors': counts[:, 0],
+               'bits': counts[:, 1], 'block_errors': counts[:, 2], 'blocks': counts[:, 3], 'plan': plan}
+        if early_stop:
+            out['turbo_iters_hist'] = hist
+            out['turbo_iters_mean'] = (hist * np.arange(hist.shape[1])).sum(axis=1) / np.maximum(hist.sum(axis=1), 1)
+        return out
 
 
 def _spatial_plan(config, channel_type, itu_profile, velocity_kmh, frequency_ghz, n_sym, n_bits, max_frames=1,
