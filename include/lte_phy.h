@@ -225,6 +225,53 @@ int lte_plan_early_stop(const lte_plan *plan);   /* 1 / 0 */
  * LTE_EINVAL when early stop is off, nothing has run since it was set, or n
  * is not that run's size. */
 int lte_plan_turbo_iters_used(const lte_plan *plan, uint8_t *out, int64_t n);
+/* HARQ retransmissions with soft combining (ABI 3, additions; coded SISO chain
+ * LTE_CHAIN_CODED only: any other chain LTE_EUNSUP).  A HARQ plan sends each
+ * transport block up to max_tx times; transmission t is rate matched with
+ * redundancy version rv_seq[t] (each 0..3; LTE's order is 0, 2, 3, 1) to G
+ * coded bits (0: 3K + 12 per code block, what a plain plan sends).  G > 0 is
+ * split over the C code blocks as 36.212 5.1.4.1.2 with one layer: G' = G / bps,
+ * gamma = G' mod C, E_r = bps * floor(G' / C) for r <= C - gamma - 1, else
+ * bps * ceil(G' / C); G % bps == 0 and bps <= E_r <= 3 K_r + 18 are required
+ * (no repetition inside one transmission), else LTE_EINVAL.  Bit selection is
+ * the reference's rate_match_turbo: window start [0, Ncb/4, Ncb/2, 3Ncb/4][rv],
+ * Ncb = 3 (K + 6).
+ * Round t = one lte_run: same payload, CRC, segmentation and encoding as round
+ * 0; the channel and noise Philox streams are keyed by
+ * seed_t = seed + t * 0x9E3779B97F4A7C15 (mod 2^64), the payload stream keeps
+ * seed; injected phases / noise are the caller's per round.  The rate
+ * dematched LLRs of round t are added to the soft rows of the rounds before
+ * (in round order, in the plan's arithmetic; a position no round has covered
+ * is exactly 0), decoded with turbo_iters iterations and checked (CRC-24A).  A
+ * frame is acknowledged in the first round whose CRC passes: tx_used = that
+ * round + 1 and its frame_errors / frame_crc_ok stay latched; never
+ * acknowledged: tx_used = max_tx, crc_ok 0, the last round's errors.  After
+ * round t, counts / frame_errors / frame_crc_ok describe the state after t + 1
+ * transmissions.  Captures are that round's own; cap_bits_rx holds the last
+ * decode performed for the frame.  From round 1 on, 64-frame decoder groups
+ * whose frames are all acknowledged are not decoded again (LTE_HARQ_SKIP=0
+ * decodes them all the same; so does lte_set_decoder_mode(0)).
+ * max_tx = 1, G = 0: a plain coded plan, bit for bit. */
+typedef struct { int32_t max_tx; int32_t rv_seq[8]; int64_t G; } lte_harq_desc;
+int lte_plan_create_harq(const lte_plan_desc *desc, const lte_harq_desc *harq, lte_plan **out);
+/* The next lte_run is transmission t.  t = 0 starts a new process (soft rows
+ * zeroed, acknowledgements cleared); t >= 1 must be the last completed round
+ * + 1 and < max_tx, and that run must bring round 0's n_frames and frame ids
+ * (LTE_EINVAL otherwise).  A new plan is at round 0, and lte_run without
+ * set_round runs round 0 again.  lte_run_path appends
+ * " harq=t<t>,rv<rv>,skip=<0|1>" for a HARQ plan.  lte_plan_set_early_stop on a
+ * HARQ plan: LTE_EUNSUP. */
+int lte_plan_harq_set_round(lte_plan *plan, int t);
+/* tx_used of the process's frames after any round, out [n] with n = n_frames. */
+int lte_plan_harq_tx_used(const lte_plan *plan, uint8_t *out, int64_t n);
+/* info [n]: max_tx, round of the last run (-1: none), its rv, decoder groups it
+ * skipped, G (as sent: the sum of E_r), n_cb, E_0 .. E_{n_cb-1}; entries past n
+ * are dropped.  Returns the full length 6 + n_cb. */
+int lte_plan_harq_info(const lte_plan *plan, int64_t *info, int n);
+/* The split alone (host only, no device): K [C] and E [C] of a transport block
+ * of n_bits payload bits (+ 24 CRC) sent in G coded bits at bps bits per
+ * symbol; returns C, or LTE_EINVAL (bad G, or n_max < C). */
+int lte_harq_code_block_bits(int32_t n_bits, int32_t bps, int64_t G, int32_t *K, int32_t *E, int32_t n_max);
 /* Per-kernel device time accumulated by lte_run while timing is on (HIP events
  * on the plan's stream).  names: comma-separated kernel names; ms/launches per
  * kernel in the same order.  n_max entries. */

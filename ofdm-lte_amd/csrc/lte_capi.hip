@@ -385,9 +385,9 @@ int upload(DBuf<T>& d, const std::vector<T>& h) {
 }
 
 const char* KNAMES[] = {"payload", "encode", "ofdm_tx", "fading", "channel", "rx_chest", "rx_data",
-                        "dematch", "turbo",   "crc_count", "accumulate", "capture"};
+                        "dematch", "turbo",   "crc_count", "accumulate", "capture", "harq"};
 enum { KN_PAYLOAD, KN_ENCODE, KN_OFDM_TX, KN_FADING, KN_CHANNEL, KN_RX_CHEST, KN_RX_DATA, KN_DEMATCH, KN_TURBO,
-       KN_CRC, KN_ACC, KN_CAP, KN_COUNT };
+       KN_CRC, KN_ACC, KN_CAP, KN_HARQ, KN_COUNT };
 
 }  // namespace
 
@@ -454,6 +454,23 @@ struct lte_plan {
   bool early_stop = false;
   std::vector<DBuf<uint32_t>> es_used;
   int es_frames = 0;
+  // HARQ (lte_plan_create_harq).  tx_map / rx_map hold one map per distinct rv
+  // of rv_seq back to back (n_re_bits entries each, hq_slot[rv] its index).
+  // hq_round: the next lte_run's transmission; hq_done: last completed round
+  // (-1: none in this process); hq_fids: round 0's frame ids.  Per frame
+  // [max_frames]: tx_used, latched errors / verdict (a passing verdict is the
+  // acknowledgement); hq_skip [G]: 1 = every frame of the group is acknowledged
+  // (k_harq_latch)
+  bool harq = false;
+  lte_harq_desc hq{};
+  int hq_slot[4] = {0, 0, 0, 0};
+  int hq_round = 0, hq_done = -1;
+  int hq_last[3] = {-1, 0, 0};       // last run: round, rv, decoder groups skipped
+  std::vector<uint64_t> hq_fids;
+  DBuf<uint32_t> hq_tx_used, hq_err, hq_crc, hq_skip;
+  std::vector<uint32_t> hq_skip_h;   // hq_skip after the last round
+  DBuf<int32_t> hq_zmap;             // decoder input rows (r << 24 | row) rv_seq[0]'s map leaves unwritten
+  int hq_nz = 0;
   // multi-antenna chains (lte_mimo.hip)
   bool mimo = false;
   // beamforming chain (lte_bf.hip)
@@ -1087,10 +1104,32 @@ void lte::plan_txf_lane_order(const std::vector<int32_t>& tx_map, const std::vec
 
 extern "C" {
 
+// The HARQ split of G coded bits over the code blocks (36.212 5.1.4.1.2, one
+// layer); G = 0 keeps the reference's 3K + 12.  E_r within [bps, 3K_r + 18]:
+// no repetition inside one transmission.
+static int harq_split(std::vector<CbInfo>& cbs, int bps, int64_t G) {
+  if (G == 0) return LTE_OK;
+  const int C = (int)cbs.size();
+  if (G < 0 || G % bps) return fail(LTE_EINVAL, "HARQ: G must be a non-negative multiple of bps");
+  const int64_t Gp = G / bps, gamma = Gp % C;
+  for (int r = 0; r < C; ++r) {
+    const int64_t E = bps * (r <= C - gamma - 1 ? Gp / C : (Gp + C - 1) / C);
+    if (E < bps || E > 3LL * cbs[r].K + 18)
+      return fail(LTE_EINVAL, "HARQ: G gives code block " + std::to_string(r) + " E = " + std::to_string(E) +
+                                  " outside [bps, 3K + 18] (K = " + std::to_string(cbs[r].K) + ")");
+    cbs[r].E = (int)E;
+  }
+  return LTE_OK;
+}
+
 static int plan_coded_maps(lte_plan* p, const Knobs& k) {
   const lte_plan_desc& d = p->d;
   if (!segmentation_plan(d.n_bits + 24, p->cbs)) return fail(LTE_EINVAL, "No valid interleaver size");
   p->C = (int)p->cbs.size();
+  if (p->harq) {
+    const int e = harq_split(p->cbs, d.bps, p->hq.G);
+    if (e) return e;
+  }
   int Kmax = 0;
   std::vector<int> Eoff(p->C + 1, 0);
   for (int r = 0; r < p->C; ++r) {
@@ -1109,8 +1148,6 @@ static int plan_coded_maps(lte_plan* p, const Knobs& k) {
   const int rows_rx = (ncs_rx + Nd - 1) / Nd;
   const int n_re = p->n_sym * Nd;
   p->n_re_bits = n_re * bps;
-  std::vector<std::vector<RmSrc>> rs(p->C);
-  for (int r = 0; r < p->C; ++r) rm_source(p->cbs[r].K, 0, p->cbs[r].E, rs[r]);
   auto locate = [&](int e, int& r, int& i) {
     r = 0;
     while (e >= Eoff[r + 1]) ++r;
@@ -1124,47 +1161,81 @@ static int plan_coded_maps(lte_plan* p, const Knobs& k) {
     layers = std::max(layers, (p->cbs[r].E + ncb - 1) / ncb);
   }
   p->n_layers = layers;
-  std::vector<int32_t> txm(p->n_re_bits), rxm((size_t)layers * p->n_re_bits, -1);
-  for (int re = 0; re < n_re; ++re) {
-    // TX: interleaved position re <- padded coded symbol q (ofdm_core.py:1046-1060)
-    const int c = re / rows, rr = re % rows;
-    const int q = rr * Nd + c;
-    for (int m = 0; m < bps; ++m) {
-      int32_t v;
-      if (q >= ncs_tx) v = -2;
-      else {
-        const int e = q * bps + m;
-        if (e >= p->coded_len) v = -1;
+  // one (tx_map, rx_map) pair per redundancy version in use, back to back: a
+  // plain plan's rv 0, a HARQ plan's distinct rv_seq entries in order of first use
+  std::vector<int> rvs;
+  for (int t = 0; t < (p->harq ? p->hq.max_tx : 1); ++t) {
+    const int rv = p->harq ? p->hq.rv_seq[t] : 0;
+    if (std::find(rvs.begin(), rvs.end(), rv) == rvs.end()) {
+      p->hq_slot[rv] = (int)rvs.size();
+      rvs.push_back(rv);
+    }
+  }
+  const size_t nmap = rvs.size();
+  std::vector<int32_t> txm(nmap * p->n_re_bits), rxm(nmap * layers * p->n_re_bits, -1);
+  for (size_t mi = 0; mi < nmap; ++mi) {
+    std::vector<std::vector<RmSrc>> rs(p->C);
+    for (int r = 0; r < p->C; ++r) rm_source(p->cbs[r].K, rvs[mi], p->cbs[r].E, rs[r]);
+    int32_t* const txo = txm.data() + mi * p->n_re_bits;
+    int32_t* const rxo = rxm.data() + mi * layers * p->n_re_bits;
+    for (int re = 0; re < n_re; ++re) {
+      // TX: interleaved position re <- padded coded symbol q (ofdm_core.py:1046-1060)
+      const int c = re / rows, rr = re % rows;
+      const int q = rr * Nd + c;
+      for (int m = 0; m < bps; ++m) {
+        int32_t v;
+        if (q >= ncs_tx) v = -2;
         else {
-          int r, i;
-          locate(e, r, i);
-          const RmSrc s = rs[r][i];
-          v = s.stream < 0 ? -1 : ((r * 3 + s.stream) * p->EW) * 32 + s.idx;
+          const int e = q * bps + m;
+          if (e >= p->coded_len) v = -1;
+          else {
+            int r, i;
+            locate(e, r, i);
+            const RmSrc s = rs[r][i];
+            v = s.stream < 0 ? -1 : ((r * 3 + s.stream) * p->EW) * 32 + s.idx;
+          }
         }
+        txo[(size_t)re * bps + m] = v;
       }
-      txm[(size_t)re * bps + m] = v;
+      // RX: de-interleave (ofdm_core.py:1176-1197) then rate dematch rows
+      int qr = -1;
+      if (re < rows_rx * Nd) {
+        const int c2 = re / rows_rx, r2 = re % rows_rx;
+        qr = r2 * Nd + c2;
+        if (qr >= ncs_rx) qr = -1;
+      }
+      for (int m = 0; m < bps; ++m) {
+        if (qr < 0) continue;
+        const int e = qr * bps + m;
+        if (e >= p->coded_len) continue;
+        int r, i;
+        locate(e, r, i);
+        const int K = p->cbs[r].K;
+        const RmSrc s = rs[r][i];
+        int row = -1;
+        if (s.stream == 0) row = (int)(s.idx < K + 3 ? trow_ls(K, s.idx) : trow_ls2t(K, s.idx - K - 3));
+        else if (s.stream == 1) row = (int)trow_lp(K, 1, s.idx);
+        else if (s.stream == 2) row = (int)trow_lp(K, 2, s.idx);
+        if (row >= 0) rxo[(size_t)(i / (3 * (K + 6))) * p->n_re_bits + (size_t)re * bps + m] = (r << 24) | row;
+      }
     }
-    // RX: de-interleave (ofdm_core.py:1176-1197) then rate dematch rows
-    int qr = -1;
-    if (re < rows_rx * Nd) {
-      const int c2 = re / rows_rx, r2 = re % rows_rx;
-      qr = r2 * Nd + c2;
-      if (qr >= ncs_rx) qr = -1;
-    }
-    for (int m = 0; m < bps; ++m) {
-      if (qr < 0) continue;
-      const int e = qr * bps + m;
-      if (e >= p->coded_len) continue;
-      int r, i;
-      locate(e, r, i);
+  }
+  if (p->harq) {   // the rows round 0 has to zero: every decoder input row its map (slot 0) does not write
+    std::vector<int32_t> zm;
+    std::vector<std::vector<char>> hit(p->C);
+    for (int r = 0; r < p->C; ++r) hit[r].assign((size_t)turbo_rows(p->cbs[r].K), 0);
+    for (int t = 0; t < p->n_re_bits; ++t)
+      if (rxm[t] >= 0) hit[rxm[t] >> 24][rxm[t] & 0xFFFFFF] = 1;
+    for (int r = 0; r < p->C; ++r) {
       const int K = p->cbs[r].K;
-      const RmSrc s = rs[r][i];
-      int row = -1;
-      if (s.stream == 0) row = (int)(s.idx < K + 3 ? trow_ls(K, s.idx) : trow_ls2t(K, s.idx - K - 3));
-      else if (s.stream == 1) row = (int)trow_lp(K, 1, s.idx);
-      else if (s.stream == 2) row = (int)trow_lp(K, 2, s.idx);
-      if (row >= 0) rxm[(size_t)(i / (3 * (K + 6))) * p->n_re_bits + (size_t)re * bps + m] = (r << 24) | row;
+      auto need = [&](int64_t row) {
+        if (!hit[r][row]) zm.push_back((r << 24) | (int32_t)row);
+      };
+      for (int i = 0; i < K + 3; ++i) { need(trow_ls(K, i)); need(trow_lp(K, 1, i)); need(trow_lp(K, 2, i)); }
+      for (int j = 0; j < 3; ++j) need(trow_ls2t(K, j));
     }
+    p->hq_nz = (int)zm.size();
+    if (upload(p->hq_zmap, zm)) return fail(LTE_ENOMEM, "map upload failed");
   }
   p->qstride = Kmax + 32;
   std::vector<uint16_t> qm((size_t)p->C * p->qstride, 0);
@@ -1177,7 +1248,7 @@ static int plan_coded_maps(lte_plan* p, const Knobs& k) {
   // instruction but not the kernel time (15.34 ms with it, 15.17 without,
   // DESIGN.md §5 round 4), and its greedy search costs plan-create time on every
   // plan-cache miss.  LTE_TXF_LANE_ORDER=1 turns it on.
-  if (p->res == p->Nd && d.N >= 512 && p->Nd <= d.N / 2 && k.txf_lane_order) {
+  if (p->res == p->Nd && d.N >= 512 && p->Nd <= d.N / 2 && k.txf_lane_order && !p->harq) {
     std::vector<int32_t> tfm, tfr;
     plan_txf_lane_order(txm, p->gh.data, p->n_sym, Nd, bps, d.N / 2, tfm, tfr, p->txf_model);
     if (k.txf_lane_order_report)
@@ -1386,9 +1457,18 @@ static int plan_alloc(lte_plan* p) {
   return LTE_OK;
 }
 
-int lte_plan_create(const lte_plan_desc* desc, lte_plan** out) {
+// lte_plan_create (harq null) / lte_plan_create_harq
+static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte_plan** out) {
   if (!desc || !out) return fail(LTE_EINVAL, "null argument");
   const lte_plan_desc& d = *desc;
+  if (harq) {
+    if (d.chain != LTE_CHAIN_CODED)
+      return fail(LTE_EUNSUP, "HARQ runs on the coded SISO chain (LTE_CHAIN_CODED) only");
+    if (harq->max_tx < 1 || harq->max_tx > 8) return fail(LTE_EINVAL, "HARQ: max_tx must be in 1..8");
+    for (int t = 0; t < harq->max_tx; ++t)
+      if (harq->rv_seq[t] < 0 || harq->rv_seq[t] > 3) return fail(LTE_EINVAL, "HARQ: rv_seq entries must be in 0..3");
+    if (harq->G < 0) return fail(LTE_EINVAL, "HARQ: G must be >= 0");
+  }
   if (d.N < 128 || d.N > 2048 || (d.N & (d.N - 1))) return fail(LTE_EUNSUP, "N must be a power of two in [128, 2048]");
   if (d.Nc <= 0 || d.Nc >= d.N || d.cp_len < 0 || d.cp_len > d.N) return fail(LTE_EINVAL, "bad Nc / cp_len");
   if (d.bps != 2 && d.bps != 4 && d.bps != 6) return fail(LTE_EINVAL, "Unsupported modulation");
@@ -1430,6 +1510,10 @@ int lte_plan_create(const lte_plan_desc* desc, lte_plan** out) {
   p->d.num_tx = num_tx;
   p->mimo = mimo;
   p->f64 = d.precision != LTE_PREC_F32;
+  if (harq) {
+    p->harq = true;
+    p->hq = *harq;
+  }
   const bool coded = d.chain == LTE_CHAIN_CODED || d.chain == LTE_CHAIN_SFBC_CODED;
   if (coded && d.turbo_iters < 0) { delete p; return fail(LTE_EINVAL, "bad turbo_iters"); }
   int rc = plan_tables(p);
@@ -1528,8 +1612,37 @@ int lte_plan_create(const lte_plan_desc* desc, lte_plan** out) {
   rc = plan_alloc(p);
   if (rc) { lte_plan_destroy(p); return rc; }
   if (p->counts.alloc(4 * 64)) { lte_plan_destroy(p); return fail(LTE_ENOMEM, "counts"); }
+  if (p->harq) {
+    const size_t B = (size_t)d.max_frames;
+    if (p->hq_tx_used.alloc(B) || p->hq_err.alloc(B) || p->hq_crc.alloc(B) ||
+        p->hq_skip.alloc((B + 63) / 64) || hipMemset(p->hq_tx_used.p, 0, B * sizeof(uint32_t)) != hipSuccess) {
+      lte_plan_destroy(p);
+      return fail(LTE_ENOMEM, "HARQ state");
+    }
+  }
   *out = p;
   return LTE_OK;
+}
+
+int lte_plan_create(const lte_plan_desc* desc, lte_plan** out) { return plan_create(desc, nullptr, out); }
+
+int lte_plan_create_harq(const lte_plan_desc* desc, const lte_harq_desc* harq, lte_plan** out) {
+  if (!harq) return fail(LTE_EINVAL, "null argument");
+  return plan_create(desc, harq, out);
+}
+
+int lte_harq_code_block_bits(int32_t n_bits, int32_t bps, int64_t G, int32_t* K, int32_t* E, int32_t n_max) {
+  if (!K || !E) return fail(LTE_EINVAL, "null argument");
+  if (n_bits < 1) return fail(LTE_EINVAL, "Bits array cannot be empty");
+  if (bps != 2 && bps != 4 && bps != 6) return fail(LTE_EINVAL, "Unsupported modulation");
+  std::vector<CbInfo> cbs;
+  if (!segmentation_plan(n_bits + 24, cbs)) return fail(LTE_EINVAL, "No valid interleaver size");
+  const int rc = harq_split(cbs, bps, G);
+  if (rc) return rc;
+  const int C = (int)cbs.size();
+  if (n_max < C) return fail(LTE_EINVAL, "n_max is smaller than the " + std::to_string(C) + " code blocks");
+  for (int r = 0; r < C; ++r) { K[r] = cbs[r].K; E[r] = cbs[r].E; }
+  return C;
 }
 
 int lte_plan_destroy(lte_plan* p) {
@@ -1544,6 +1657,8 @@ int lte_plan_destroy(lte_plan* p) {
   p->cap_bits.release();
   for (auto& b : p->decb) b.release();
   for (auto& b : p->es_used) b.release();
+  p->hq_zmap.release();
+  p->hq_tx_used.release(); p->hq_err.release(); p->hq_crc.release(); p->hq_skip.release();
   p->rows_dev.release(); p->dec_ptrs.release(); p->kw_dev.release();
   p->m_np.release(); p->m_ppos.release(); p->m_pseg.release(); p->m_pval.release(); p->m_pval64.release();
   p->m_pig.release(); p->m_pig64.release(); p->m_W.release(); p->bf_cb.release();
@@ -1569,6 +1684,7 @@ int lte_plan_precision(const lte_plan* p) {
 
 int lte_plan_set_early_stop(lte_plan* p, int on) {
   if (!p) return fail(LTE_EINVAL, "null plan");
+  if (p->harq) return fail(LTE_EUNSUP, "CRC early termination is not combined with HARQ");
   if (p->d.chain != LTE_CHAIN_CODED && p->d.chain != LTE_CHAIN_SFBC_CODED)
     return fail(LTE_EINVAL, "early stop applies to the coded chains only (nothing is decoded in this plan)");
   if (on && p->es_used.empty()) {
@@ -1606,6 +1722,40 @@ int lte_plan_turbo_iters_used(const lte_plan* p, uint8_t* out, int64_t n) {
     for (int b = 0; b < B; ++b) out[(size_t)b * p->C + r] = (uint8_t)h[b];
   }
   return LTE_OK;
+}
+
+int lte_plan_harq_set_round(lte_plan* p, int t) {
+  if (!p) return fail(LTE_EINVAL, "null plan");
+  if (!p->harq) return fail(LTE_EINVAL, "not a HARQ plan");
+  if (t < 0 || t >= p->hq.max_tx)
+    return fail(LTE_EINVAL, "HARQ: round " + std::to_string(t) + " outside 0..max_tx-1 (max_tx = " +
+                                std::to_string(p->hq.max_tx) + ")");
+  if (t > 0 && t != p->hq_done + 1)
+    return fail(LTE_EINVAL, "HARQ: round " + std::to_string(t) + " must follow the last completed round (" +
+                                std::to_string(p->hq_done) + ")");
+  p->hq_round = t;
+  return LTE_OK;
+}
+
+int lte_plan_harq_tx_used(const lte_plan* p, uint8_t* out, int64_t n) {
+  if (!p || !out) return fail(LTE_EINVAL, "null argument");
+  if (!p->harq) return fail(LTE_EINVAL, "not a HARQ plan");
+  if (p->hq_done < 0) return fail(LTE_EINVAL, "HARQ: no completed round");
+  if (n != (int64_t)p->hq_fids.size())
+    return fail(LTE_EINVAL, "n must be the process's n_frames (" + std::to_string(p->hq_fids.size()) + ")");
+  std::vector<uint32_t> h((size_t)n);
+  HIPCHK(hipMemcpy(h.data(), p->hq_tx_used.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  for (int64_t b = 0; b < n; ++b) out[b] = (uint8_t)h[b];
+  return LTE_OK;
+}
+
+int lte_plan_harq_info(const lte_plan* p, int64_t* info, int n) {
+  if (!p || !info) return fail(LTE_EINVAL, "null argument");
+  if (!p->harq) return fail(LTE_EINVAL, "not a HARQ plan");
+  std::vector<int64_t> v = {p->hq.max_tx, p->hq_last[0], p->hq_last[1], p->hq_last[2], p->coded_len, p->C};
+  for (int r = 0; r < p->C; ++r) v.push_back(p->cbs[r].E);
+  for (int i = 0; i < n && i < (int)v.size(); ++i) info[i] = v[i];
+  return (int)v.size();
 }
 
 int lte_timing_enable(lte_plan* p, int on) {
@@ -1743,6 +1893,7 @@ struct SisoPath {
   SisoRx rx;
   bool xhand;      // the TX hands its symbols to the paired receiver (TxChannelT::x_out)
   bool zn;         // (z, nv) hand-off to k_dematch_zn instead of LLRs
+  bool hq_skip;    // HARQ round >= 1: the skip-aware decoders (k_turbo*_skip)
   bool fused() const { return tx != TX_NONE && tx != TX_SYM; }
 };
 
@@ -1771,6 +1922,7 @@ static SisoPath select_siso(const lte_plan* p, const lte_run_args* a, const Knob
   const int maxd = fuse ? *std::max_element(d.delays, d.delays + d.n_paths) : 0;
   // receiver: fused (estimation + data path per frame) unless LTE_RX_FUSE=0
   s.zn = k.demap_in_dematch && demap_in_dematch(p, a);
+  s.hq_skip = p->harq && p->hq_round >= 1 && do_rx && k.harq_skip && !logmap_on();
   const bool rx_fuse = do_rx && k.rx_fuse;
   const bool rxf = rx_fuse && rx_fusable(p);
   const bool rxs = rx_fuse && !rxf && rx_simo_fusable(p);
@@ -2191,7 +2343,8 @@ static int run_bf(lte_plan* p, const lte_run_args* a, int B, int n_snr, const st
 // Fading taps, fused TX + channel, first-samples power fix-up and noise power.
 template <class R>
 static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const SisoPath& path, int B, bool coded,
-                    const R* inj_ph, int64_t inj_ph_stride, cx<R>* cap_tx_syms, cx<R>* x_out, TxChannelT<R>* ch_out) {
+                    uint64_t cseed, const int32_t* tx_map, const R* inj_ph, int64_t inj_ph_stride,
+                    cx<R>* cap_tx_syms, cx<R>* x_out, TxChannelT<R>* ch_out) {
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
   const int maxd = *std::max_element(d.delays, d.delays + d.n_paths);
@@ -2204,7 +2357,7 @@ static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const Sis
     return fail(LTE_ENOMEM, "tx channel");
   {
     Timer t(p, KN_FADING, s);
-    LCHK(launch_fading<R>(s, B, rx, d.n_paths, c.gains.p, p->fid.p, a->seed, inj_ph, inj_ph_stride, c.phases.p,
+    LCHK(launch_fading<R>(s, B, rx, d.n_paths, c.gains.p, p->fid.p, cseed, inj_ph, inj_ph_stride, c.phases.p,
                           c.coef.p));
     if (tv)   // one (frame, RX) at a time: phases / sets are [B][rx][path]
       LCHK(launch_jakes_sets<R>(s, B * rx, d.n_paths, p->n_sym, d.N + d.cp_len, c.phases.p, c.gains.p, d.fD, d.fs,
@@ -2225,14 +2378,14 @@ static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const Sis
   {
     Timer t(p, KN_OFDM_TX, s);
     if (path.tx == TX_FRAME) {
-      LCHK(launch_ofdm_txf<R>(s, p->grid, p->enc.p, p->enc_words, p->tx_map.p, p->txf_map.p, p->txf_re.p, B,
+      LCHK(launch_ofdm_txf<R>(s, p->grid, p->enc.p, p->enc_words, tx_map, p->txf_map.p, p->txf_re.p, B,
                               cap_tx_syms, ch));
     } else if (path.tx == TX_SYM_CH) {
-      LCHK(launch_ofdm_tx_ch<R>(s, p->grid, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, p->tx_map.p, B,
+      LCHK(launch_ofdm_tx_ch<R>(s, p->grid, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, tx_map, B,
                                 cap_tx_syms, ch, (d.sc_fdm && !coded) ? 1 : 0, path.tx_stage ? 1 : 0));
     } else if constexpr (std::is_same_v<R, double>) {   // the wave-private transmitters (lte_wave.hip)
       if (path.tx == TX_FRAME_W)
-        LCHK(launch_ofdm_txf_w(s, p->grid, p->enc.p, p->enc_words, p->tx_map.p, B, cap_tx_syms, ch,
+        LCHK(launch_ofdm_txf_w(s, p->grid, p->enc.p, p->enc_words, tx_map, B, cap_tx_syms, ch,
                                path.tx_stage ? 1 : 0));
       else
         LCHK(launch_ofdm_tx_simo_w(s, p->grid, p->pw.p, p->PW, B, cap_tx_syms, ch));
@@ -2281,6 +2434,12 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
     if (e != LTE_OK) return e;
   }
   const bool fuse = path.fused(), xhand = path.xhand;
+  // HARQ round t: its own rate-matching maps, and channel / noise streams keyed
+  // by seed_t (the payload stream, and k_crc_count's re-draw of it, keep seed)
+  const int hq_t = p->harq ? p->hq_round : 0, hq_rv = p->harq ? p->hq.rv_seq[hq_t] : 0;
+  const uint64_t cseed = a->seed + (uint64_t)hq_t * 0x9E3779B97F4A7C15ull;
+  const int32_t* const tx_map = p->tx_map.p + (size_t)p->hq_slot[hq_rv] * p->n_re_bits;
+  const int32_t* const rx_map = p->rx_map.p + (size_t)p->hq_slot[hq_rv] * p->n_layers * p->n_re_bits;
   TxChannelT<R> xch{};
   if (do_tx || a->bits) {
     Timer t(p, KN_PAYLOAD);
@@ -2298,13 +2457,14 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
       cts = c.captx.p;
     }
     if (fuse) {
-      const int e = run_txch<R>(p, s, a, path, B, coded, inj_ph, inj_ph_stride, cts, xhand ? c.x.p : nullptr, &xch);
+      const int e = run_txch<R>(p, s, a, path, B, coded, cseed, tx_map, inj_ph, inj_ph_stride, cts,
+                                xhand ? c.x.p : nullptr, &xch);
       if (e != LTE_OK) return e;
     } else {
       Timer t(p, KN_OFDM_TX);
       // SC-FDM precodes the uncoded SISO / SIMO transmitters only: simulate_siso_coded
       // builds its own grids without the precoder (core/ofdm_core.py:1062-1099)
-      LCHK(launch_ofdm_tx<R>(s, g, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, p->tx_map.p, c.x.p, B, cts,
+      LCHK(launch_ofdm_tx<R>(s, g, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, tx_map, c.x.p, B, cts,
                              (d.sc_fdm && !coded) ? 1 : 0, path.tx_stage ? 1 : 0));
     }
   } else {
@@ -2320,7 +2480,7 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
   const int64_t yrs = ray ? p->L : 0, yfs = ray ? (int64_t)rx * p->L : p->L;
   if (ray && !fuse) {
     Timer t(p, KN_FADING);
-    LCHK(launch_fading<R>(s, B, rx, d.n_paths, c.gains.p, p->fid.p, a->seed, inj_ph, inj_ph_stride, c.phases.p,
+    LCHK(launch_fading<R>(s, B, rx, d.n_paths, c.gains.p, p->fid.p, cseed, inj_ph, inj_ph_stride, c.phases.p,
                           c.coef.p));
   }
   if (!fuse) {
@@ -2332,7 +2492,7 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
   }
   if (path.rx == RX_CHEST_DATA) {
     Timer t(p, KN_RX_CHEST);
-    LCHK(launch_rx_chest<R>(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, a->seed, inj_z, inj_z_stride, c.H.p,
+    LCHK(launch_rx_chest<R>(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, cseed, inj_z, inj_z_stride, c.H.p,
                             c.pstats.p));
   }
   V* cap_syms_dev = nullptr;
@@ -2350,7 +2510,7 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
   if (path.rx == RX_FRAME_W) {
     Timer t(p, KN_RX_DATA);
     if constexpr (std::is_same_v<R, double>)
-      LCHK(launch_rx_frame_w(s, g, ray ? 1 : 0, B, ysrc, yfs, c.npow.p, c.snr_lin.p, p->fid.p, a->seed, inj_z,
+      LCHK(launch_rx_frame_w(s, g, ray ? 1 : 0, B, ysrc, yfs, c.npow.p, c.snr_lin.p, p->fid.p, cseed, inj_z,
                              inj_z_stride, reinterpret_cast<R*>(zn_z<R>(p)), zn_nv<R>(p), cap_syms_dev,
                              a->cap_H ? c.H.p : nullptr, a->cap_pilot_stats ? c.pstats.p : nullptr));
     else
@@ -2358,27 +2518,27 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
   } else if (path.rx == RX_SIMO_W) {
     Timer t(p, KN_RX_DATA);
     if constexpr (std::is_same_v<R, double>)
-      LCHK(launch_rx_frame_simo_w(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, a->seed, inj_z, inj_z_stride,
+      LCHK(launch_rx_frame_simo_w(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, cseed, inj_z, inj_z_stride,
                                   p->pw.p, p->PW, d.n_bits, p->frame_err.p, cap_syms_dev, cap_bits_dev));
     else
       return fail(LTE_EINVAL, "the wave receivers run in float64 plans only");
   } else if (path.rx == RX_FRAME) {
     Timer t(p, KN_RX_DATA);
-    LCHK(launch_rx_frame<R>(s, g, d.chain, ray ? 1 : 0, B, ysrc, yfs, c.npow.p, c.snr_lin.p, p->fid.p, a->seed, inj_z,
+    LCHK(launch_rx_frame<R>(s, g, d.chain, ray ? 1 : 0, B, ysrc, yfs, c.npow.p, c.snr_lin.p, p->fid.p, cseed, inj_z,
                             inj_z_stride, p->pw.p, p->PW, d.n_bits, p->frame_err.p,
                             zn ? reinterpret_cast<R*>(zn_z<R>(p)) : c.llr.p, cap_syms_dev,
                             coded ? nullptr : cap_bits_dev, zn ? zn_nv<R>(p) : nullptr,
                             a->cap_H ? c.H.p : nullptr, a->cap_pilot_stats ? c.pstats.p : nullptr));
   } else if (path.rx == RX_SIMO || path.rx == RX_SIMO2) {
     Timer t(p, KN_RX_DATA);
-    LCHK(launch_rx_frame_simo<R>(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, a->seed, inj_z, inj_z_stride,
+    LCHK(launch_rx_frame_simo<R>(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, cseed, inj_z, inj_z_stride,
                                  p->pw.p, p->PW, d.n_bits, p->frame_err.p, cap_syms_dev, cap_bits_dev,
                                  a->cap_H ? c.H.p : nullptr, a->cap_pilot_stats ? c.pstats.p : nullptr,
                                  path.rx == RX_SIMO2 ? 1 : 0, xhand ? &xch : nullptr));
   } else if (path.rx == RX_CHEST_DATA) {
     Timer t(p, KN_RX_DATA);
     LCHK(launch_rx_data<R>(s, g, d.chain, ray ? 1 : 0, B, rx, ysrc, yrs, yfs, c.H.p, c.npow.p, c.snr_lin.p, p->fid.p,
-                           a->seed, inj_z, inj_z_stride, p->pw.p, p->PW, d.n_bits, p->frame_err.p,
+                           cseed, inj_z, inj_z_stride, p->pw.p, p->PW, d.n_bits, p->frame_err.p,
                            zn ? reinterpret_cast<R*>(zn_z<R>(p)) : c.llr.p, cap_syms_dev,
                            coded ? nullptr : cap_bits_dev,
                            // the IDFT runs in receive_and_decode only (core/lte_receiver.py:318-333): the SIMO
@@ -2386,30 +2546,57 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
                            (d.sc_fdm && d.chain == LTE_CHAIN_UNCODED) ? 1 : 0, zn ? zn_nv<R>(p) : nullptr));
   }
   if (coded && do_rx) {
+    const int G = (B + 63) / 64;
+    // HARQ: round 0 stores zeros in the rows its map does not cover (an earlier
+    // process has left sums there), later rounds add to every row they cover
+    const int hq_add = hq_t >= 1 ? 1 : 0;
     {
       Timer t(p, KN_DEMATCH);
+      if (p->harq && hq_t == 0 && p->hq_nz)
+        LCHK(launch_harq_zero<R>(s, p->hq_zmap.p, p->hq_nz, G, c.blk_ptrs.p, p->rows_dev.p, turbo_plan_ch(p)));
       if (zn)
-        LCHK(launch_dematch_zn<R>(s, zn_z<R>(p), zn_nv<R>(p), p->n_re_bits / d.bps, p->Nd, d.bps, B, p->rx_map.p,
-                                  p->n_layers, c.blk_ptrs.p, p->rows_dev.p, turbo_plan_ch(p)));
+        LCHK(launch_dematch_zn<R>(s, zn_z<R>(p), zn_nv<R>(p), p->n_re_bits / d.bps, p->Nd, d.bps, B, rx_map,
+                                  p->n_layers, c.blk_ptrs.p, p->rows_dev.p, turbo_plan_ch(p), 0, 0, hq_add));
       else
-        LCHK(launch_dematch<R>(s, c.llr.p, p->n_re_bits, B, p->rx_map.p, p->n_layers, c.blk_ptrs.p, p->rows_dev.p,
-                                 turbo_plan_ch(p)));
+        LCHK(launch_dematch<R>(s, c.llr.p, p->n_re_bits, B, rx_map, p->n_layers, c.blk_ptrs.p, p->rows_dev.p,
+                                 turbo_plan_ch(p), 0, hq_add));
     }
-    const int G = (B + 63) / 64;
     std::vector<TurboJob> jobs(p->C);
     for (int r = 0; r < p->C; ++r) {
       const CbInfo& cb = p->cbs[r];
       jobs[r] = TurboJob{c.blk[r].p, c.ckpt[r].p, p->decb[r].p, cb.K, cb.f1, cb.f2, G, turbo_plan_ch(p)};
     }
-    {
+    // HARQ rounds >= 1: groups whose frames are all acknowledged return at once
+    // (k_turbo*_skip read k_harq_latch's flags); none left: no decoder launch
+    const bool skip = path.hq_skip && (int)p->hq_skip_h.size() == G;
+    int hq_nskip = 0;
+    if (skip)
+      for (int g = 0; g < G; ++g) hq_nskip += p->hq_skip_h[g] ? 1 : 0;
+    if (!(skip && hq_nskip == G)) {
       Timer t(p, KN_TURBO);
-      LCHK(plan_launch_turbo(p, s, jobs, B, sizeof(R) == 8 ? 1 : 0));
+      if (skip)
+        LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, sizeof(R) == 8 ? 1 : 0, p->hq_skip.p));
+      else
+        LCHK(plan_launch_turbo(p, s, jobs, B, sizeof(R) == 8 ? 1 : 0));
     }
     {
       Timer t(p, KN_CRC);
       LCHK(launch_crc_count(s, p->cbi.p, p->C, p->dec_ptrs.p, p->kw_dev.p, B, p->pw.p, p->PW, d.n_bits,
                             p->frame_err.p, p->frame_crc.p, cap_bits_dev, 0, inj_bits ? nullptr : p->fid.p,
                             a->seed));
+    }
+    if (p->harq) {
+      {
+        Timer t(p, KN_HARQ);
+        LCHK(launch_harq_latch(s, B, hq_t, p->frame_err.p, p->frame_crc.p, p->hq_tx_used.p, p->hq_err.p, p->hq_crc.p,
+                               p->hq_skip.p));
+      }
+      p->hq_skip_h.resize(G);
+      HIPCHK(hipMemcpyAsync(p->hq_skip_h.data(), p->hq_skip.p, G * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      p->hq_last[0] = hq_t;
+      p->hq_last[1] = hq_rv;
+      p->hq_last[2] = hq_nskip;
+      p->hq_done = hq_t;
     }
   }
   if (do_rx) {
@@ -2435,7 +2622,7 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
     {
       Timer t(p, KN_CAP);
       hipLaunchKernelGGL(k_cap_rx<R>, dim3(((p->L + 255) / 256) * B, rx), dim3(256), 0, s, p->L, rx, B, ysrc, yrs, yfs,
-                         c.npow.p, p->fid.p, a->seed, inj_z, inj_z_stride, tmp.p);
+                         c.npow.p, p->fid.p, cseed, inj_z, inj_z_stride, tmp.p);
       LCHK((int)hipGetLastError());
     }
     HIPCHK(hipMemcpyAsync(a->cap_signal_rx, tmp.p, (size_t)B * rx * p->L * sizeof(V), hipMemcpyDeviceToHost, s));
@@ -2491,6 +2678,25 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
     }
     fid[b] = a->frame_ids ? a->frame_ids[b] : a->frame_id0 + (uint64_t)b;
   }
+  if (p->harq) {   // a retransmission serves round 0's frames; round 0 opens a new process
+    if (p->hq_round >= 1) {
+      const int t = p->hq_round;
+      std::string bad;
+      if (p->hq_done != t - 1)
+        bad = "HARQ: round " + std::to_string(t) + " without a completed round " + std::to_string(t - 1);
+      else if ((size_t)B != p->hq_fids.size())
+        bad = "HARQ: a retransmission must bring round 0's n_frames (" + std::to_string(p->hq_fids.size()) + ")";
+      else if (fid != p->hq_fids)
+        bad = "HARQ: a retransmission must bring round 0's frame ids";
+      if (!bad.empty()) {
+        p->hq_round = 0;   // the refused round is not pending any more
+        return fail(LTE_EINVAL, bad);
+      }
+    } else {
+      p->hq_fids = fid;
+      p->hq_done = -1;
+    }
+  }
   HIPCHK(hipMemcpyAsync(p->snr_idx.p, si.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(p->fid.p, fid.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice, s));
   // payload injection (packed MSB-first)
@@ -2521,6 +2727,7 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
     const int e = p->f64 ? run_siso<double>(p, a, path, B, n_snr, sl, inj_bits, inj_bits_stride)
                          : run_siso<float>(p, a, path, B, n_snr, sl, inj_bits, inj_bits_stride);
     HIPCHK(hipStreamSynchronize(s));
+    p->hq_round = 0;   // the next run opens a new process unless lte_plan_harq_set_round says otherwise
     return e;
   }
   if (stages != LTE_STAGE_ALL) return fail(LTE_EUNSUP, "multi-antenna chains run all stages");
@@ -2562,6 +2769,9 @@ int lte_run_path(const lte_plan* p, const lte_run_args* a, char* buf, int len) {
   }
   // the decoder family is named only when it is not the default one
   if (p->early_stop && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " turbo=es");
+  if (p->harq && n >= 0 && n < len)
+    n += std::snprintf(buf + n, len - n, " harq=t%d,rv%d,skip=%d", p->hq_round, p->hq.rv_seq[p->hq_round],
+                       select_siso(p, a, knobs).hq_skip ? 1 : 0);
   return n < len ? n : len - 1;
 }
 

@@ -506,8 +506,12 @@ __device__ __forceinline__ void half_pass(T* __restrict__ wbase, T* __restrict__
 // One launch decodes every code-block slot of the batch: wave w -> job r
 // (CB slot, i.e. one K) and frame group g.  256-thread blocks = 4 independent
 // waves (no LDS, no barriers).
-template <class T, bool LM = false, int CH = TURBO_CH>
-__device__ __forceinline__ void turbo_body(const TurboJobs& jobs, int iters, int mode) {
+// SKIP (the HARQ kernels k_turbo64_skip / k_turbo_skip): skip[g] != 0 marks a
+// frame group with nothing left to decode; g is wave-uniform, so the flag is a
+// scalar load and the wave leaves before it touches a row.
+template <class T, bool LM = false, int CH = TURBO_CH, bool SKIP = false>
+__device__ __forceinline__ void turbo_body(const TurboJobs& jobs, int iters, int mode,
+                                           const uint32_t* __restrict__ skip = nullptr) {
   const int wg = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (wg >= jobs.prefix[jobs.n]) return;
@@ -515,6 +519,9 @@ __device__ __forceinline__ void turbo_body(const TurboJobs& jobs, int iters, int
   while (wg >= jobs.prefix[r + 1]) ++r;
   const TurboJob jb = jobs.j[r];
   const int g = wg - jobs.prefix[r];
+  if constexpr (SKIP) {
+    if (skip[g] != 0u) return;
+  }
   const int K = jb.K;
   // the group's chunk of the block arrays (turbo_elem: [chunk][row][CH][64])
   const int slot = g % CH;
@@ -564,6 +571,28 @@ __global__ __launch_bounds__(256, LTE_TURBO64_ONE_WAVE ? 1 : 2) void k_turbo64(T
   asm volatile("" ::: "a31");
 #endif
   turbo_body<double, false, CH>(jobs, iters, mode);
+}
+
+// The fixed decoders with the HARQ group skip: the same bodies and register
+// caps as k_turbo / k_turbo64, one more kernel argument.
+template <int CH>
+__global__ __launch_bounds__(256, LTE_TURBO32_WAVES == 3 ? 2 : 1) void k_turbo_skip(TurboJobs jobs, int iters, int mode,
+                                                                                     const uint32_t* skip) {
+#if LTE_TURBO32_WAVES == 2
+  asm volatile("" ::: "a47");
+#elif LTE_TURBO32_WAVES == 1
+  asm volatile("" ::: "a127");
+#endif
+  turbo_body<float, false, CH, true>(jobs, iters, mode, skip);
+}
+
+template <int CH>
+__global__ __launch_bounds__(256, LTE_TURBO64_ONE_WAVE ? 1 : 2) void k_turbo64_skip(TurboJobs jobs, int iters, int mode,
+                                                                                     const uint32_t* skip) {
+#if LTE_TURBO64_ONE_WAVE
+  asm volatile("" ::: "a31");
+#endif
+  turbo_body<double, false, CH, true>(jobs, iters, mode, skip);
 }
 
 // f64 exact log-MAP (set_decoder_mode(False)); not a hot path
@@ -667,7 +696,8 @@ static int g_logmap = 0;
 void set_logmap(int on) { g_logmap = on ? 1 : 0; }
 int logmap_on() { return g_logmap; }
 
-int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int mode, int f64) {
+int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int mode, int f64, const uint32_t* skip) {
+  if (skip && g_logmap) return (int)hipErrorInvalidValue;   // max-log only (the caller does not ask for it)
   for (int o = 0; o < n; o += TURBO_MAX_JOBS) {
     TurboJobs J{};
     J.n = n - o < TURBO_MAX_JOBS ? n - o : TURBO_MAX_JOBS;
@@ -682,7 +712,15 @@ int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int
     for (int i = 1; i < J.n; ++i)
       if (J.j[i].ch != ch) return (int)hipErrorInvalidValue;   // one chunk width per launch
     const dim3 grid((waves + 3) / 4);
-    if (ch == TURBO_CH) {
+    if (skip) {   // every job has the flags' group count
+      for (int i = 1; i < J.n; ++i)
+        if (J.j[i].G != J.j[0].G) return (int)hipErrorInvalidValue;
+      if (ch == TURBO_CH && f64) hipLaunchKernelGGL(k_turbo64_skip<TURBO_CH>, grid, dim3(256), 0, s, J, iters, mode, skip);
+      else if (ch == TURBO_CH) hipLaunchKernelGGL(k_turbo_skip<TURBO_CH>, grid, dim3(256), 0, s, J, iters, mode, skip);
+      else if (ch == 1 && f64) hipLaunchKernelGGL(k_turbo64_skip<1>, grid, dim3(256), 0, s, J, iters, mode, skip);
+      else if (ch == 1) hipLaunchKernelGGL(k_turbo_skip<1>, grid, dim3(256), 0, s, J, iters, mode, skip);
+      else return (int)hipErrorInvalidValue;
+    } else if (ch == TURBO_CH) {
       if (f64 && g_logmap) hipLaunchKernelGGL(k_turbo64_logmap<TURBO_CH>, grid, dim3(256), 0, s, J, iters, mode);
       else if (f64) hipLaunchKernelGGL(k_turbo64<TURBO_CH>, grid, dim3(256), 0, s, J, iters, mode);
       else hipLaunchKernelGGL(k_turbo<TURBO_CH>, grid, dim3(256), 0, s, J, iters, mode);

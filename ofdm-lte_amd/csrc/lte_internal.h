@@ -198,9 +198,10 @@ bool rx_simo2_ok(const Grid& g, int num_rx, bool H, bool pstats);
 // [n_layers][T]: layer 0 assigns, layers 1.. add in order (E > N_cb
 // repetition, rate_matching.py:433-436).  g0: first 64-frame group.
 // ch: chunk width of the decoder rows (turbo_chunk of their capacity in groups)
+// add0: layer 0 adds too (HARQ soft combining: the rows hold the rounds before)
 template <class R>
 int launch_dematch(hipStream_t s, const R* llr, int T, int B, const int32_t* rx_map, int n_layers, R* const* blk,
-                   const int64_t* rows, int ch, int g0 = 0);
+                   const int64_t* rows, int ch, int g0 = 0, int add0 = 0);
 // dematch with the soft demapper fused in: reads the equalised symbols z
 // ([B][n_re]) and their noise variances ([B][n_grp][nd] per data subcarrier,
 // from the receivers' nv_out mode; nv_pairs: [B][n_sym][nd / 2] per Alamouti
@@ -209,7 +210,17 @@ int launch_dematch(hipStream_t s, const R* llr, int T, int B, const int32_t* rx_
 template <class R>
 int launch_dematch_zn(hipStream_t s, const cx<R>* z, const R* nv, int n_re, int nd, int bps, int B,
                       const int32_t* rx_map, int n_layers, R* const* blk, const int64_t* rows, int ch, int g0 = 0,
-                      int nv_pairs = 0);
+                      int nv_pairs = 0, int add0 = 0);
+// HARQ round 0: zeros to the nz decoder rows zmap lists (r << 24 | row) of groups 0 .. G-1
+template <class R>
+int launch_harq_zero(hipStream_t s, const int32_t* zmap, int nz, int G, R* const* blk, const int64_t* rows, int ch);
+// HARQ acknowledgement latch after k_crc_count of round t (k_harq_latch): a
+// frame not yet acknowledged (every frame at t = 0) records tx_used = t + 1 and
+// latches its errors / verdict (a passing verdict is the acknowledgement); an
+// acknowledged frame gets its latched errors / verdict written back over this
+// round's.  skip [ceil(B / 64)]: 1 when no frame of the group is still active.
+int launch_harq_latch(hipStream_t s, int B, int t, uint32_t* frame_err, uint32_t* frame_crc, uint32_t* tx_used,
+                      uint32_t* l_err, uint32_t* l_crc, uint32_t* skip);
 // f64 != 0: the float64 decoder (bit-exact with the reference), blk / ckpt hold doubles
 int launch_turbo(hipStream_t s, void* blk, void* ckpt, uint32_t* bits, int K, int f1, int f2, int iters,
                  int G, int mode, int f64, int ch);
@@ -226,7 +237,10 @@ struct TurboJobs {
   int n;
   int prefix[TURBO_MAX_JOBS + 1];
 };
-int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int mode, int f64);
+// skip set (max-log decoders, one group count for every job): group g's waves
+// return at once where skip[g] != 0 (k_turbo64_skip / k_turbo_skip)
+int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int mode, int f64,
+                      const uint32_t* skip = nullptr);
 // Full decode with CRC early termination (k_turbo64_es / k_turbo_es, max-log
 // only): a code block stops after the first iteration n >= 1 whose decisions
 // have CRC-24 remainder zero over all K bits (poly: CRC24A_POLY / CRC24B_POLY).

@@ -53,6 +53,7 @@ struct Knobs {
   // SISO / SIMO chains
   bool txch_fuse, tx_frame, tx_stage, tx_wave, txw_stage, simo_tx_wave;
   bool rx_fuse, rx_wave, simo_rx_wave, rxs_pairs, simo_xhand, demap_in_dematch;
+  bool harq_skip;
   // multi-antenna chains
   bool mimo_lp_fuse, mimo_flat_fuse, txch_pr, mimo_tx_wave, txm_frame, sfbc_txch_fuse, sfbc_rx_fuse, sfbc_link_merge;
   bool chm_tay, cht_econ, mimo_rx_wave, spatial_hp, dsp_stage;
@@ -88,6 +89,7 @@ inline Knobs read_knobs() {
   // the streams cost the HBM)
   k.simo_xhand = knob("LTE_SIMO_XHAND", 0);
   k.demap_in_dematch = knob("LTE_DEMAP_IN_DEMATCH", 1);   // coded 16/64-QAM: (z, nv) hand-off to k_dematch_zn (0: the LLR round trip)
+  k.harq_skip = knob("LTE_HARQ_SKIP", 1);      // HARQ rounds >= 1: finished 64-frame groups skip the decoder (0: k_turbo* decode every group)
   // --- multi-antenna transmitter
   k.mimo_lp_fuse = knob("LTE_MIMO_LP_FUSE", 1);       // transmit_mimo's link power formed by k_ofdm_tx_mimo (0: k_link_power)
   k.mimo_flat_fuse = knob("LTE_MIMO_FLAT_FUSE", 1);   // flat links: TX + channel in one pass, k_ofdm_txch_flat

@@ -70,12 +70,12 @@ __global__ __launch_bounds__(256) void k_dematch(const R* __restrict__ llr, int 
 
 template <class R>
 int launch_dematch(hipStream_t s, const R* llr, int T, int B, const int32_t* rx_map, int n_layers, R* const* blk,
-                   const int64_t* rows, int ch, int g0) {
+                   const int64_t* rows, int ch, int g0, int add0) {
   const int G = (B + 63) / 64 - g0;   // groups g0 .. ceil(B/64)-1
   if (G < 1 || G > 65535 || n_layers < 1) return (int)hipErrorInvalidValue;
   for (int k = 0; k < n_layers; ++k) {
     hipLaunchKernelGGL(k_dematch<R>, dim3((T + DM_CH - 1) / DM_CH, G), dim3(256), 0, s, llr, T, B,
-                       rx_map + (size_t)k * T, k > 0 ? 1 : 0, blk, rows, ch, g0);
+                       rx_map + (size_t)k * T, k > 0 || add0 ? 1 : 0, blk, rows, ch, g0);
     const int e = (int)hipGetLastError();
     if (e) return e;
   }
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void k_dematch_zn(const cx<R>* __restrict__ z,
 template <class R>
 int launch_dematch_zn(hipStream_t s, const cx<R>* z, const R* nv, int n_re, int nd, int bps, int B,
                       const int32_t* rx_map, int n_layers, R* const* blk, const int64_t* rows, int ch, int g0,
-                      int nv_pairs) {
+                      int nv_pairs, int add0) {
   const int G = (B + 63) / 64 - g0;
   if (G < 1 || G > 65535 || (bps != 4 && bps != 6) || n_layers < 1 || nd < 1) return (int)hipErrorInvalidValue;
   if (nv_pairs && (nd & 1)) return (int)hipErrorInvalidValue;
@@ -159,10 +159,10 @@ int launch_dematch_zn(hipStream_t s, const cx<R>* z, const R* nv, int n_re, int 
     const int32_t* mp = rx_map + (size_t)k * T;
     if (bps == 4)
       hipLaunchKernelGGL((k_dematch_zn<R, 4>), grid, dim3(256), 0, s, z, nv, n_re, nd, n_nv, nv_grp, nv_sh, B, mp,
-                         k > 0 ? 1 : 0, blk, rows, ch, g0);
+                         k > 0 || add0 ? 1 : 0, blk, rows, ch, g0);
     else
       hipLaunchKernelGGL((k_dematch_zn<R, 6>), grid, dim3(256), 0, s, z, nv, n_re, nd, n_nv, nv_grp, nv_sh, B, mp,
-                         k > 0 ? 1 : 0, blk, rows, ch, g0);
+                         k > 0 || add0 ? 1 : 0, blk, rows, ch, g0);
     const int e = (int)hipGetLastError();
     if (e) return e;
   }
@@ -170,13 +170,73 @@ int launch_dematch_zn(hipStream_t s, const cx<R>* z, const R* nv, int n_re, int 
 }
 
 template int launch_dematch<float>(hipStream_t, const float*, int, int, const int32_t*, int, float* const*,
-                                   const int64_t*, int, int);
+                                   const int64_t*, int, int, int);
 template int launch_dematch<double>(hipStream_t, const double*, int, int, const int32_t*, int, double* const*,
-                                    const int64_t*, int, int);
+                                    const int64_t*, int, int, int);
 template int launch_dematch_zn<float>(hipStream_t, const float2*, const float*, int, int, int, int, const int32_t*,
-                                      int, float* const*, const int64_t*, int, int, int);
+                                      int, float* const*, const int64_t*, int, int, int, int);
 template int launch_dematch_zn<double>(hipStream_t, const double2*, const double*, int, int, int, int,
-                                       const int32_t*, int, double* const*, const int64_t*, int, int, int);
+                                       const int32_t*, int, double* const*, const int64_t*, int, int, int, int);
+
+// ---------------------------------------------------------------------------
+// HARQ (HARQ section).  The soft rows of a process live in the
+// decoder's LS / LP / LS2T rows: round 0 assigns (k_dematch, add = 0) and
+// k_harq_zero stores zeros in the rows round 0's map leaves out; rounds >= 1
+// add (add = 1).  k_harq_latch keeps the per-frame acknowledgement state.
+
+// One wave per (listed row, group): 64 lanes of zeros.
+template <class R>
+__global__ __launch_bounds__(256) void k_harq_zero(const int32_t* __restrict__ zmap, int nz,
+                                                   R* const* __restrict__ blk, const int64_t* __restrict__ rows,
+                                                   int ch) {
+  const int i = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if (i >= nz) return;
+  const int m = zmap[i], r = m >> 24, row = m & 0xFFFFFF;
+  blk[r][turbo_elem_ch(ch, rows[r], blockIdx.y, row) + (threadIdx.x & 63)] = (R)0;
+}
+
+template <class R>
+int launch_harq_zero(hipStream_t s, const int32_t* zmap, int nz, int G, R* const* blk, const int64_t* rows, int ch) {
+  if (nz < 1 || G < 1 || G > 65535) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_harq_zero<R>, dim3((nz + 3) / 4, G), dim3(256), 0, s, zmap, nz, blk, rows, ch);
+  return (int)hipGetLastError();
+}
+template int launch_harq_zero<float>(hipStream_t, const int32_t*, int, int, float* const*, const int64_t*, int);
+template int launch_harq_zero<double>(hipStream_t, const int32_t*, int, int, double* const*, const int64_t*, int);
+
+// One wave64 per 64-frame group, lane f = frame g * 64 + f, after k_crc_count
+// of round t.  The group's flag for the next round's decoder: no lane still
+// active (lanes >= B count as finished).
+__global__ __launch_bounds__(64) void k_harq_latch(int B, int t, uint32_t* __restrict__ frame_err,
+                                                   uint32_t* __restrict__ frame_crc, uint32_t* __restrict__ tx_used,
+                                                   uint32_t* __restrict__ l_err, uint32_t* __restrict__ l_crc,
+                                                   uint32_t* __restrict__ skip) {
+  const int g = blockIdx.x, b = g * 64 + (int)threadIdx.x;
+  bool active = false;
+  if (b < B) {
+    // the latched verdict is the acknowledgement; round 0 opens the process: nothing is acknowledged yet
+    if (t == 0 || !l_crc[b]) {
+      const uint32_t e = frame_err[b], c = frame_crc[b];
+      tx_used[b] = (uint32_t)(t + 1);
+      l_err[b] = e;
+      l_crc[b] = c;
+      active = c == 0;
+    } else {
+      frame_err[b] = l_err[b];
+      frame_crc[b] = l_crc[b];
+    }
+  }
+  const unsigned long long still = __ballot(active);
+  if (threadIdx.x == 0) skip[g] = still == 0ull ? 1u : 0u;
+}
+
+int launch_harq_latch(hipStream_t s, int B, int t, uint32_t* frame_err, uint32_t* frame_crc, uint32_t* tx_used,
+                      uint32_t* l_err, uint32_t* l_crc, uint32_t* skip) {
+  if (B < 1 || t < 0) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_harq_latch, dim3((B + 63) / 64), dim3(64), 0, s, B, t, frame_err, frame_crc, tx_used, l_err,
+                     l_crc, skip);
+  return (int)hipGetLastError();
+}
 
 // ---------------------------------------------------------------------------
 // Stage entry: rate_dematching_turbo (rate_matching.py:374-489) for any E,

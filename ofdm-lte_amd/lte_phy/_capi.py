@@ -56,6 +56,10 @@ class RunArgs(ctypes.Structure):
                 ('cap_pmi', P(c_i32)), ('cap_bf_gain', P(c_f64))]
 
 
+class HarqDesc(ctypes.Structure):   # lte_harq_desc
+    _fields_ = [('max_tx', c_i32), ('rv_seq', c_i32 * 8), ('G', c_i64)]
+
+
 # every symbol include/lte_phy.h declares, with its ctypes signature
 _SIGS = {
     'lte_strerror': (ctypes.c_char_p, [ctypes.c_int]),
@@ -72,6 +76,11 @@ _SIGS = {
     'lte_plan_set_early_stop': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'lte_plan_early_stop': (ctypes.c_int, [ctypes.c_void_p]),
     'lte_plan_turbo_iters_used': (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_uint8), c_i64]),
+    'lte_plan_create_harq': (ctypes.c_int, [P(PlanDesc), P(HarqDesc), P(ctypes.c_void_p)]),
+    'lte_plan_harq_set_round': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'lte_plan_harq_tx_used': (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_uint8), c_i64]),
+    'lte_plan_harq_info': (ctypes.c_int, [ctypes.c_void_p, P(c_i64), ctypes.c_int]),
+    'lte_harq_code_block_bits': (ctypes.c_int, [c_i32, c_i32, c_i64, P(c_i32), P(c_i32), c_i32]),
     'lte_timing_enable': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'lte_timing_read': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, P(c_f64), P(c_i64),
                                        ctypes.c_int]),

@@ -24,7 +24,8 @@ class RunResult(dict):
 class Plan:
     def __init__(self, *, N, Nc, cp_len, bps, n_sym, chain, channel, num_rx=1, delays=(), gains=(), fD=0.0,
                  fs=0.0, n_bits, turbo_iters=8, max_frames=1, cell_id=0, num_tx=1, rank=0, detector=0,
-                 precoder=(), sc_fdm=0, bf_adaptive=0, no_equalization=0, precision=None, early_stop=False):
+                 precoder=(), sc_fdm=0, bf_adaptive=0, no_equalization=0, precision=None, early_stop=False,
+                 harq=None):
         C.device_init()
         d = C.PlanDesc()
         d.N, d.Nc, d.cp_len, d.bps, d.n_sym = N, Nc, cp_len, bps, n_sym
@@ -51,7 +52,27 @@ class Plan:
                     d.precoder[(t * 4 + c) * 2 + 1] = float(W[t, c].imag)
         self.desc = d
         h = ctypes.c_void_p()
-        C.check(C.load().lte_plan_create(ctypes.byref(d), ctypes.byref(h)))
+        # HARQ (lte_plan_create_harq; coded SISO chain): dict(max_tx=4, rv_seq=(0, 2, 3, 1),
+        # coded_bits=0), coded_bits = G, the coded bits per transmission (0: 3K + 12 per code block)
+        self.harq = None
+        if harq is not None:
+            hq = dict(max_tx=4, rv_seq=(0, 2, 3, 1), coded_bits=0)
+            unknown = set(harq) - set(hq)
+            if unknown:
+                raise ValueError(f'harq: unknown keys {sorted(unknown)}')
+            hq.update(harq)
+            hq['max_tx'], hq['coded_bits'] = int(hq['max_tx']), int(hq['coded_bits'] or 0)
+            hq['rv_seq'] = tuple(int(v) for v in hq['rv_seq'])
+            if not 1 <= hq['max_tx'] <= 8 or len(hq['rv_seq']) < hq['max_tx']:
+                raise ValueError('harq: max_tx must be in 1..8 with one rv_seq entry per transmission')
+            hd = C.HarqDesc()
+            hd.max_tx, hd.G = hq['max_tx'], hq['coded_bits']
+            for t in range(hq['max_tx']):
+                hd.rv_seq[t] = hq['rv_seq'][t]
+            self.harq = hq
+            C.check(C.load().lte_plan_create_harq(ctypes.byref(d), ctypes.byref(hd), ctypes.byref(h)))
+        else:
+            C.check(C.load().lte_plan_create(ctypes.byref(d), ctypes.byref(h)))
         self.h = h
         info = np.zeros(8, dtype=np.int64)
         C.check(C.load().lte_plan_info(h, C.ptr(info, C.c_i64)))
@@ -99,13 +120,61 @@ class Plan:
     def run(self, snr_db, **kw):
         """One batch through lte_run (keywords: _args) -> RunResult."""
         a, out, keep = self._args(snr_db, **kw)
+        path = self._path(a)   # before the run: a HARQ plan's round is consumed by it
         C.check(C.load().lte_run(self.h, ctypes.byref(a)))
-        out.path = self._path(a)
+        out.path = path
         if self.early_stop and (a.stages & C.STAGE_RX):
             used = np.zeros((a.n_frames, self.n_cb), dtype=np.uint8)
             C.check(C.load().lte_plan_turbo_iters_used(self.h, C.ptr(used, C.U8), used.size))
             out['turbo_iters_used'] = used
+        if self.harq is not None and (a.stages & C.STAGE_RX):   # the process's state after this round
+            used = np.zeros(a.n_frames, dtype=np.uint8)
+            C.check(C.load().lte_plan_harq_tx_used(self.h, C.ptr(used, C.U8), used.size))
+            out['tx_used'] = used
+            out['harq_info'] = self.harq_info()
         del keep
+        return out
+
+    # ------------------------------------------------------------------ HARQ
+    def harq_round(self, t):
+        """The next run() is transmission t of the process (lte_plan_harq_set_round):
+        0 starts a new one, t >= 1 must follow round t - 1 with the same frames."""
+        C.check(C.load().lte_plan_harq_set_round(self.h, int(t)))
+
+    def harq_info(self):
+        """lte_plan_harq_info as a dict: max_tx, round / rv / skipped (decoder groups)
+        of the last run, coded_bits (G as sent), E (per code block)."""
+        v = np.zeros(6 + self.n_cb, dtype=np.int64)
+        C.check(C.load().lte_plan_harq_info(self.h, C.ptr(v, C.c_i64), len(v)))
+        return {'max_tx': int(v[0]), 'round': int(v[1]), 'rv': int(v[2]), 'skipped': int(v[3]),
+                'coded_bits': int(v[4]), 'n_cb': int(v[5]), 'E': [int(e) for e in v[6:]]}
+
+    def run_harq(self, snr_db, **kw):
+        """One HARQ process: the rounds 0 .. max_tx - 1 with the same arguments,
+        stopping after the first round that leaves no frame unacknowledged.
+        Returns tx_used / crc_ok / frame_errors (latched), counts (after the
+        last round run), counts_by_round [max_tx, n_snr, 4] (rounds not run
+        repeat the last), rounds_run, skipped (decoder groups per round run),
+        and with capture= a list `rounds` of each round's captures."""
+        if self.harq is None:
+            raise ValueError('run_harq needs a plan made with harq=')
+        capture = tuple(kw.get('capture', ()))
+        cbr, rounds, skipped, r = [], [], [], None
+        for t in range(self.harq['max_tx']):
+            self.harq_round(t)
+            r = self.run(snr_db, **kw)
+            cbr.append(r['counts'].copy())
+            skipped.append(r['harq_info']['skipped'])
+            if capture:
+                rounds.append({k: r[k] for k in capture})
+            if bool(np.all(r['crc_ok'] != 0)):
+                break
+        out = RunResult(counts=r['counts'], frame_errors=r['frame_errors'], crc_ok=r['crc_ok'],
+                        tx_used=r['tx_used'], rounds_run=len(cbr), skipped=skipped,
+                        counts_by_round=np.stack(cbr + [cbr[-1]] * (self.harq['max_tx'] - len(cbr))))
+        out.path = r.path
+        if capture:
+            out['rounds'] = rounds
         return out
 
     def path(self, snr_db, **kw):
@@ -239,10 +308,13 @@ _CACHE_MAX = 8
 def get_plan(**kw):
     kw['precision'] = C.precision_of(kw.get('precision'))   # resolved now: part of the cache key
     kw['early_stop'] = bool(kw.get('early_stop', False))   # likewise: an early-stop plan is never a fixed one
+    hq = kw.get('harq')   # likewise, as a sorted tuple of its settings (None: a plain plan)
+    kw['harq'] = None if hq is None else tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple, np.ndarray)) else v)
+                                                      for k, v in dict(hq).items()))
     key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple, np.ndarray)) else v) for k, v in kw.items()))
     p = _CACHE.get(key)
     if p is None:
-        p = Plan(**kw)
+        p = Plan(**dict(kw, harq=None if kw['harq'] is None else dict(kw['harq'])))
         _CACHE[key] = p
         while len(_CACHE) > _CACHE_MAX:
             _CACHE.popitem(last=False)

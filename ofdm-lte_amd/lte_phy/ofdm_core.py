@@ -505,7 +505,7 @@ class OFDMSimulator:
     def Nd(self):
         return len(self.grid._data)
 
-    def _plan(self, chain, n_sym, n_bits, num_rx=1, max_frames=1, iters=8, early_stop=False):
+    def _plan(self, chain, n_sym, n_bits, num_rx=1, max_frames=1, iters=8, early_stop=False, harq=None):
         """SC-FDM (enable_sc_fdm / mode 'sc-fdm') reaches the uncoded SISO / SIMO
         transmitters and the SISO receiver; simulate_siso_coded ignores it, as
         the reference does (lte_plan_desc.sc_fdm, include/lte_phy.h)."""
@@ -518,7 +518,7 @@ class OFDMSimulator:
                         chain=chain, channel=ch.kind, num_rx=num_rx, delays=tuple(ch.delays),
                         gains=tuple(ch.gains), fD=ch.fD, fs=cfg.fs, n_bits=n_bits, turbo_iters=iters,
                         max_frames=max_frames, sc_fdm=sc, no_equalization=noeq, precision=self.precision,
-                        early_stop=early_stop)
+                        early_stop=early_stop, harq=harq)
 
     def _ref_draws(self, L, num_rx=1):
         """Exactly the global-RNG consumption of one reference simulate_* call:
@@ -880,6 +880,66 @@ class OFDMSimulator:
             out['turbo_iters_hist'] = hist
             out['turbo_iters_mean'] = (hist * np.arange(hist.shape[1])).sum(axis=1) / np.maximum(hist.sum(axis=1), 1)
         return out
+
+    def run_harq_grid(self, snr_range, num_trials, seed=0, n_bits=None, coded_bits=None, max_tx=4,
+                      rv_seq=(0, 2, 3, 1), frames_per_call=4096, rank=0, world_size=1, turbo_iters=8, **other):
+        """HARQ curve of the coded SISO chain on the device: every (SNR, trial)
+        frame is sent up to max_tx times, transmission t with redundancy version
+        rv_seq[t] and `coded_bits` coded bits (None / 0: 3K + 12 per code block),
+        the receiver adds each round's rate-dematched LLRs to the rounds before
+        and a frame stops at its first CRC pass (include/lte_phy.h,
+        lte_plan_create_harq).  Frame ids and sharding as run_grid (SNR-major ids:
+        64-frame decoder groups are mostly of one SNR, so finished groups skip
+        the decoder).  Returns snr_db; counts_by_round uint64 [S, max_tx, 4]
+        (run_grid's counts after t + 1 transmissions) and tx_hist uint64
+        [S, max_tx + 1] (frames acknowledged after 1..max_tx transmissions, index
+        0 = never), both all-reducible; bler_by_tx [S, max_tx]; mean_tx [S];
+        throughput [S] = n_bits * acknowledged / transmissions; code_rate =
+        (n_bits + 24) / coded bits sent; plan.  Only the coded SISO chain: the
+        run_grid keywords coded=False, num_rx > 1 or mimo= raise ValueError."""
+        return _harq_grid(self, snr_range, num_trials, seed, n_bits, coded_bits, max_tx, rv_seq, frames_per_call,
+                          rank, world_size, turbo_iters, other)
+
+
+def _harq_grid(sim, snr_range, num_trials, seed, n_bits, coded_bits, max_tx, rv_seq, frames_per_call, rank,
+               world_size, turbo_iters, other):
+    """OFDMSimulator.run_harq_grid's body."""
+    bad = {k: v for k, v in other.items()
+           if not ((k == 'coded' and v is True) or (k == 'num_rx' and v == 1) or (k == 'mimo' and v is None))}
+    if bad:
+        raise ValueError(f"run_harq_grid runs the coded SISO chain only (HARQ is not built for {bad})")
+    max_tx, rv_seq = int(max_tx), tuple(int(v) for v in rv_seq)
+    if not 1 <= max_tx <= 8 or len(rv_seq) < max_tx or any(not 0 <= v <= 3 for v in rv_seq):
+        raise ValueError('run_harq_grid: max_tx must be in 1..8 and rv_seq hold one entry in 0..3 per transmission')
+    snrs = np.atleast_1d(np.asarray(snr_range, dtype=np.float64))
+    S, T = len(snrs), int(num_trials)
+    if T < 1 or frames_per_call < 1:
+        raise ValueError('run_harq_grid: num_trials and frames_per_call must be >= 1')
+    nb = int(n_bits or 27760)
+    cfg = sim.config
+    G = int(coded_bits or 0)
+    Kc, Ec = np.zeros(32, dtype=np.int32), np.zeros(32, dtype=np.int32)
+    C.check(C.load().lte_harq_code_block_bits(nb, cfg.bits_per_symbol, G, C.ptr(Kc, C.I32), C.ptr(Ec, C.I32), 32))
+    plan = sim._plan(C.CHAIN_CODED, 0, nb, max_frames=frames_per_call, iters=turbo_iters,
+                     harq=dict(max_tx=max_tx, rv_seq=rv_seq[:max_tx], coded_bits=G))
+    ids = np.array([s * T + t for s in range(S) for t in trial_shard(T, rank, world_size)], dtype=np.uint64)
+    cbr = np.zeros((S, max_tx, 4), dtype=np.uint64)
+    hist = np.zeros((S, max_tx + 1), dtype=np.uint64)
+    sent = np.zeros(S, dtype=np.uint64)
+    for i in range(0, len(ids), frames_per_call):
+        chunk = ids[i:i + frames_per_call]
+        si = (chunk // T).astype(np.int32)
+        r = plan.run_harq(snrs[si], snr_index=si, n_snr=S, seed=seed, frame_ids=chunk)
+        cbr += r['counts_by_round'].transpose(1, 0, 2)
+        np.add.at(hist, (si, np.where(r['crc_ok'] != 0, r['tx_used'], 0)), 1)
+        np.add.at(sent, si, r['tx_used'].astype(np.uint64))
+    acked = hist[:, 1:].sum(axis=1)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        bler = cbr[:, :, 2] / np.maximum(cbr[:, :, 3], 1)
+        mean_tx = sent / np.maximum(hist.sum(axis=1), 1)
+        thr = nb * acked / np.maximum(sent, 1)
+    return {'snr_db': snrs, 'counts_by_round': cbr, 'tx_hist': hist, 'bler_by_tx': bler, 'mean_tx': mean_tx,
+            'throughput': thr, 'code_rate': (nb + 24) / plan.coded_bits, 'plan': plan}
 
 
 def _spatial_plan(config, channel_type, itu_profile, velocity_kmh, frequency_ghz, n_sym, n_bits, max_frames=1,
