@@ -49,7 +49,28 @@ enum {
    * rank-1 codebook PMI feedback, static codebook or adaptive MRT precoder, MRC:
    * OFDMSimulator.simulate_beamforming core/ofdm_core.py:2260-2477.  num_tx
    * 2 / 4 / 8, num_rx 1-8; L = n_sym * Nd REs per antenna (noise layout). */
-  LTE_CHAIN_BEAMFORMING = 6
+  LTE_CHAIN_BEAMFORMING = 6,
+  /* Coded SIMO, 1 x num_rx MRC with turbo coding: this library's composition
+   * (the reference has no coded SIMO driver), LTE_CHAIN_CODED's coding chain
+   * around LTE_CHAIN_SIMO's link and combiner.  A SISO-family chain (num_tx 1,
+   * num_rx as LTE_CHAIN_SIMO, stages as the SISO chains).
+   *   TX: exactly LTE_CHAIN_CODED's -- CRC-24A, segmentation, turbo encoding,
+   *     rate matching at rv 0 with E = 3K + 12, QAM, the T/F interleaver with
+   *     cols = Nd, pilots of cell 0; n_sym follows from the coded length
+   *     (desc.n_sym = 0).
+   *   Link: transmit_simo's, one independent channel per RX; injected draws and
+   *     Philox streams are LTE_CHAIN_SIMO's.
+   *   Combiner: per RX the FFT and the LS estimate on the first symbol of every
+   *     14-symbol group; num = sum_r conj(H_r) Y_r in RX order, D = sum_r |H_r|^2,
+   *     z = num / (D + 1e-10) -- bit for bit LTE_CHAIN_SIMO's.
+   *   Soft output: sigma^2 = 1 / 10^(SNR/10), sigma^2_eff = max(sigma^2 /
+   *     clip(D, 1e-6, 1e6), sigma^2 / 4) per (group, data subcarrier), on awgn and
+   *     rayleigh alike (the combiner divides by D on both); then max-log LLRs,
+   *     T/F de-interleave, dematch, turbo_iters iterations, desegmentation,
+   *     CRC-24A.  counts, frame_errors, frame_crc_ok and cap_bits_rx as
+   *     LTE_CHAIN_CODED.  lte_plan_set_early_stop applies; HARQ does not
+   *     (lte_plan_create_harq: LTE_EUNSUP). */
+  LTE_CHAIN_SIMO_CODED = 7
 };
 /* MIMODetector.detector_type (core/mimo_detector.py:116-133); IRC == MMSE */
 enum { LTE_DET_MMSE = 0, LTE_DET_ZF = 1, LTE_DET_SIC = 2, LTE_DET_MRC = 3 };

@@ -1317,6 +1317,11 @@ static int plan_mimo_tables(lte_plan* p) {
 
 }  // extern "C"
 
+// The chains that run the coding chain (encoder, dematch, turbo decoder, CRC),
+// and those of them that run_siso serves.
+static bool siso_coded(int chain) { return chain == LTE_CHAIN_CODED || chain == LTE_CHAIN_SIMO_CODED; }
+static bool chain_is_coded(int chain) { return siso_coded(chain) || chain == LTE_CHAIN_SFBC_CODED; }
+
 // Device workspace of the SISO / SIMO chains in precision R.  The TX signal x
 // is allocated on first use (the fused TX + channel path never writes it).
 template <class R>
@@ -1417,7 +1422,7 @@ static int plan_alloc(lte_plan* p) {
   const lte_plan_desc& d = p->d;
   const size_t B = (size_t)d.max_frames;
   const int G = (int)((B + 63) / 64);
-  const bool coded = d.chain == LTE_CHAIN_CODED || d.chain == LTE_CHAIN_SFBC_CODED;
+  const bool coded = chain_is_coded(d.chain);
   bool bad = false;
   bad |= p->pw.alloc(B * p->PW) != 0;
   if (p->mimo) {
@@ -1472,14 +1477,15 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
   if (d.N < 128 || d.N > 2048 || (d.N & (d.N - 1))) return fail(LTE_EUNSUP, "N must be a power of two in [128, 2048]");
   if (d.Nc <= 0 || d.Nc >= d.N || d.cp_len < 0 || d.cp_len > d.N) return fail(LTE_EINVAL, "bad Nc / cp_len");
   if (d.bps != 2 && d.bps != 4 && d.bps != 6) return fail(LTE_EINVAL, "Unsupported modulation");
-  if (d.chain < 0 || d.chain > LTE_CHAIN_BEAMFORMING) return fail(LTE_EINVAL, "bad chain");
+  if (d.chain < 0 || d.chain > LTE_CHAIN_SIMO_CODED) return fail(LTE_EINVAL, "bad chain");
   if (d.channel != LTE_CH_AWGN && d.channel != LTE_CH_RAYLEIGH) return fail(LTE_EINVAL, "Tipo de canal desconocido");
   if (d.num_rx < 1 || d.num_rx > 16) return fail(LTE_EINVAL, "num_rx must be >= 1");
   const bool bf = d.chain == LTE_CHAIN_BEAMFORMING;
-  const bool mimo = d.chain >= LTE_CHAIN_SFBC && !bf;
+  // LTE_CHAIN_SIMO_CODED is a SISO-family chain (one TX, run_siso) numbered after the multi-antenna ones
+  const bool mimo = d.chain >= LTE_CHAIN_SFBC && !bf && d.chain != LTE_CHAIN_SIMO_CODED;
   const int num_tx = d.num_tx > 0 ? d.num_tx : 1;
   if (!mimo && !bf && num_tx != 1) return fail(LTE_EINVAL, "num_tx > 1 needs a multi-antenna chain");
-  if (!mimo && !bf && d.chain != LTE_CHAIN_SIMO && d.num_rx != 1)
+  if (!mimo && !bf && d.chain != LTE_CHAIN_SIMO && d.chain != LTE_CHAIN_SIMO_CODED && d.num_rx != 1)
     return fail(LTE_EINVAL, "SISO chains need num_rx == 1");
   if (bf && num_tx != 2 && num_tx != 4 && num_tx != 8)
     return fail(LTE_EINVAL, "num_tx=" + std::to_string(num_tx) + " no soportado en TM6");
@@ -1514,7 +1520,7 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
     p->harq = true;
     p->hq = *harq;
   }
-  const bool coded = d.chain == LTE_CHAIN_CODED || d.chain == LTE_CHAIN_SFBC_CODED;
+  const bool coded = chain_is_coded(d.chain);
   if (coded && d.turbo_iters < 0) { delete p; return fail(LTE_EINVAL, "bad turbo_iters"); }
   int rc = plan_tables(p);
   if (rc) { delete p; return rc; }
@@ -1685,7 +1691,7 @@ int lte_plan_precision(const lte_plan* p) {
 int lte_plan_set_early_stop(lte_plan* p, int on) {
   if (!p) return fail(LTE_EINVAL, "null plan");
   if (p->harq) return fail(LTE_EUNSUP, "CRC early termination is not combined with HARQ");
-  if (p->d.chain != LTE_CHAIN_CODED && p->d.chain != LTE_CHAIN_SFBC_CODED)
+  if (!chain_is_coded(p->d.chain))
     return fail(LTE_EINVAL, "early stop applies to the coded chains only (nothing is decoded in this plan)");
   if (on && p->es_used.empty()) {
     std::vector<DBuf<uint32_t>> u(p->C);
@@ -1853,14 +1859,14 @@ static bool tx_per_frame(const lte_plan* p) {
   return (size_t)spw * (p->grid.N * el + (size_t)p->enc_words * 4) <= 65536;
 }
 
-// Coded SISO 16/64-QAM without an LLR capture: k_rx_data hands over the
+// Coded SISO / SIMO 16/64-QAM without an LLR capture: the receiver hands over the
 // equalised symbol and sigma^2_eff per RE and k_dematch_zn demaps while it
 // builds the decoder rows, instead of a round trip of bps LLRs per RE.  The
 // (z, nv) arrays live in the LLR buffer ([max_frames][n_re] z, then
 // [max_frames][n_re] nv: 3 R per RE).
 static bool demap_in_dematch(const lte_plan* p, const lte_run_args* a) {
   const lte_plan_desc& d = p->d;
-  return d.chain == LTE_CHAIN_CODED && !p->mimo && !p->bf && (d.bps == 4 || d.bps == 6) && !a->cap_llr;
+  return siso_coded(d.chain) && !p->mimo && !p->bf && (d.bps == 4 || d.bps == 6) && !a->cap_llr;
 }
 
 // Fused SISO receiver (k_rx_frame): one RX, coded or uncoded, no SC-FDM.
@@ -1868,9 +1874,9 @@ static bool rx_fusable(const lte_plan* p) {
   const lte_plan_desc& d = p->d;
   return rx_frame_supported(p->grid, d.chain, d.num_rx, (d.sc_fdm && d.chain == LTE_CHAIN_UNCODED) ? 1 : 0);
 }
-// Fused SIMO MRC receiver (k_rx_frame_simo*).
+// Fused SIMO MRC receiver (k_rx_frame_simo*), uncoded or with the coded chain's soft output.
 static bool rx_simo_fusable(const lte_plan* p) {
-  return p->d.chain == LTE_CHAIN_SIMO && rx_frame_simo_supported(p->grid, p->d.num_rx);
+  return (p->d.chain == LTE_CHAIN_SIMO || p->d.chain == LTE_CHAIN_SIMO_CODED) && rx_frame_simo_supported(p->grid, p->d.num_rx);
 }
 
 // the kernel families, as lte_run_path prints them
@@ -1912,7 +1918,7 @@ struct MimoPath {
 static SisoPath select_siso(const lte_plan* p, const lte_run_args* a, const Knobs& k) {
   const lte_plan_desc& d = p->d;
   const Grid& g = p->grid;
-  const bool coded = d.chain == LTE_CHAIN_CODED, tv = d.fD != 0.0;
+  const bool coded = siso_coded(d.chain), tv = d.fD != 0.0;
   const bool cap_H = a->cap_H != nullptr, cap_ps = a->cap_pilot_stats != nullptr;
   const int stages = a->stages ? a->stages : LTE_STAGE_ALL, rx = d.num_rx, scf = (d.sc_fdm && !coded) ? 1 : 0;
   const bool do_tx = stages & LTE_STAGE_TX, do_ch = stages & LTE_STAGE_CHANNEL, do_rx = stages & LTE_STAGE_RX;
@@ -1927,11 +1933,11 @@ static SisoPath select_siso(const lte_plan* p, const lte_run_args* a, const Knob
   const bool rxf = rx_fuse && rx_fusable(p);
   const bool rxs = rx_fuse && !rxf && rx_simo_fusable(p);
   const bool pairs = rxs && k.rxs_pairs && rx_simo2_ok(g, rx, cap_H, cap_ps);
-  s.xhand = fuse && pairs && !tv && k.simo_xhand;
+  s.xhand = fuse && pairs && !tv && k.simo_xhand && !coded;   // (the hand-over is an uncoded form)
   if (rxf)
     s.rx = s.zn && k.rx_wave && rx_frame_w_supported(g, d.chain, p->f64) ? RX_FRAME_W : RX_FRAME;
   else if (rxs)
-    s.rx = !s.xhand && k.simo_rx_wave && rx_simo_w_supported(g, rx, p->f64, cap_H, cap_ps, false) ? RX_SIMO_W
+    s.rx = !s.xhand && k.simo_rx_wave && rx_simo_w_supported(g, d.chain, rx, p->f64, cap_H, cap_ps, false) ? RX_SIMO_W
            : pairs ? RX_SIMO2 : RX_SIMO;
   else
     s.rx = do_rx ? RX_CHEST_DATA : RX_NONE;
@@ -2409,7 +2415,7 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
   const Grid& g = p->grid;
-  const bool coded = d.chain == LTE_CHAIN_CODED, ray_cfg = d.channel == LTE_CH_RAYLEIGH;
+  const bool coded = siso_coded(d.chain), ray_cfg = d.channel == LTE_CH_RAYLEIGH;
   const int rx = d.num_rx;
   hipStream_t s = p->stream;
   const int stages = a->stages ? a->stages : LTE_STAGE_ALL;
@@ -2532,9 +2538,12 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
   } else if (path.rx == RX_SIMO || path.rx == RX_SIMO2) {
     Timer t(p, KN_RX_DATA);
     LCHK(launch_rx_frame_simo<R>(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, cseed, inj_z, inj_z_stride,
-                                 p->pw.p, p->PW, d.n_bits, p->frame_err.p, cap_syms_dev, cap_bits_dev,
+                                 p->pw.p, p->PW, d.n_bits, p->frame_err.p, cap_syms_dev,
+                                 coded ? nullptr : cap_bits_dev,
                                  a->cap_H ? c.H.p : nullptr, a->cap_pilot_stats ? c.pstats.p : nullptr,
-                                 path.rx == RX_SIMO2 ? 1 : 0, xhand ? &xch : nullptr));
+                                 path.rx == RX_SIMO2 ? 1 : 0, xhand ? &xch : nullptr, c.snr_lin.p,
+                                 !coded ? nullptr : zn ? reinterpret_cast<R*>(zn_z<R>(p)) : c.llr.p,
+                                 coded && zn ? zn_nv<R>(p) : nullptr));
   } else if (path.rx == RX_CHEST_DATA) {
     Timer t(p, KN_RX_DATA);
     LCHK(launch_rx_data<R>(s, g, d.chain, ray ? 1 : 0, B, rx, ysrc, yrs, yfs, c.H.p, c.npow.p, c.snr_lin.p, p->fid.p,
@@ -2717,7 +2726,7 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
   const int stages = a->stages ? a->stages : LTE_STAGE_ALL;
   if (!(stages & LTE_STAGE_TX) && !a->in_signal) return fail(LTE_EINVAL, "in_signal required when the TX stage is skipped");
   p->evuse.clear();
-  if (logmap_on() && (d.chain == LTE_CHAIN_CODED || d.chain == LTE_CHAIN_SFBC_CODED) && !p->f64)
+  if (logmap_on() && chain_is_coded(d.chain) && !p->f64)
     return fail(LTE_EUNSUP, "exact log-MAP decoding runs in float64 plans only");
   if (logmap_on() && p->early_stop)
     return fail(LTE_EUNSUP, "CRC early termination runs the max-log decoders only (set_decoder_mode(True))");
@@ -2755,7 +2764,7 @@ int lte_run_path(const lte_plan* p, const lte_run_args* a, char* buf, int len) {
     const SisoPath s = select_siso(p, a, knobs);
     n = std::snprintf(buf, len, "tx=%s tx_stage=%d ch_fix=%d rx=%s xhand=%d dematch=%s", SISO_TX_NAME[s.tx], s.tx_stage,
                       s.ch_fix, SISO_RX_NAME[s.rx], s.xhand,
-                      p->d.chain != LTE_CHAIN_CODED || s.rx == RX_NONE ? "none" : s.zn ? "zn" : "llr");
+                      !siso_coded(p->d.chain) || s.rx == RX_NONE ? "none" : s.zn ? "zn" : "llr");
   } else {
     const MimoPath s = p->f64 ? select_mimo<double>(p, a, knobs) : select_mimo<float>(p, a, knobs);
     char ch[48];   // the channel pass: fused into the TX, k_channel_mimo, or k_channel_tay with its form

@@ -179,10 +179,14 @@ int launch_rx_frame(hipStream_t s, const Grid& g, int chain, int rayleigh, int B
                     int64_t y_frame_stride, const R* npow, const R* snr_lin, const uint64_t* fid, uint64_t seed,
                     const R* inj_z, int64_t inj_stride, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
                     R* llr, cx<R>* cap_syms, uint8_t* cap_bits, R* nv_out, cx<R>* H, R* pstats);
-// Fused SIMO MRC receiver (uncoded, 2..RXS_MAXRX RX): one slot per frame walks
+// Fused SIMO MRC receiver (2..RXS_MAXRX RX): one slot per frame walks
 // its symbols, every RX's estimate in registers; H / pstats: optional captures
 // [B][num_rx][n_grp][N] / [B][num_rx][n_grp][2].  pairs: k_rx_frame_simo2
-// (rx_simo2_ok), else k_rx_frame_simo.
+// (rx_simo2_ok), else k_rx_frame_simo.  llr null: uncoded (hard decisions
+// against pw, bit errors into frame_err).  llr set (LTE_CHAIN_SIMO_CODED; needs
+// snr_lin, no xc hand-over): soft output and no error count -- with nv_out
+// (16 / 64-QAM) llr takes z per RE and nv_out sigma^2_eff per (frame, group,
+// data subcarrier) as launch_rx_frame's, else llr takes bps LLRs per RE.
 constexpr int RXS_MAXRX = 4;
 bool rx_frame_simo_supported(const Grid& g, int num_rx);
 template <class R>
@@ -190,7 +194,7 @@ int launch_rx_frame_simo(hipStream_t s, const Grid& g, int B, int num_rx, const 
                          int64_t y_frame_stride, const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z,
                          int64_t inj_stride, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
                          cx<R>* cap_syms, uint8_t* cap_bits, cx<R>* H, R* pstats, int pairs,
-                         const TxChannelT<R>* xc);
+                         const TxChannelT<R>* xc, const R* snr_lin, R* llr, R* nv_out);
 // the paired SIMO receiver applies (N = 1024, an even RX count, no H / pilot
 // statistics capture); xc->x_out (the TX's symbol handoff) needs it
 bool rx_simo2_ok(const Grid& g, int num_rx, bool H, bool pstats);
@@ -427,7 +431,7 @@ int launch_npow_mimo(hipStream_t s, int B, int num_rx, const R* pow_part, int nb
 // wave-private f64 RX FFT + CRS pilot estimates (lte_wave.hip), N = 2048, the
 // pilot-estimate handoff: launch_rx_fft_mimo's outputs (Knobs::mimo_rx_wave)
 bool rx_fft_mimo_w_supported(const Grid& g, const MimoGrid& m, int f64, int h_pilots);
-bool rx_simo_w_supported(const Grid& g, int num_rx, int f64, bool H, bool pstats, bool xin);
+bool rx_simo_w_supported(const Grid& g, int chain, int num_rx, int f64, bool H, bool pstats, bool xin);
 bool tx_simo_w_supported(const Grid& g, int f64, int coded, int sc_fdm, int n_paths, int max_delay, int num_rx,
                          bool tv, bool xout);
 int launch_ofdm_tx_simo_w(hipStream_t s, const Grid& g, const uint32_t* pw, int PW, int B, double2* cap_syms,

@@ -1221,12 +1221,28 @@ __device__ __forceinline__ re_t<V> abs2_ref(V h) {
 // ---------------------------------------------------------------------------
 // Hard decision / soft demap.  Natural-binary QAM, I-level-major index
 // (modulator.py:28-59, Q9): bits = [I-level bits | Q-level bits], MSB first.
+// The BPS max-log LLRs of one RE stored at lo (RE order) as 8-B pairs (float32
+// 16-QAM: one 16-B store): the LLR output of every SISO / SIMO receiver.
+template <class R, int BPS>
+__device__ __forceinline__ void store_llrs(R* lo, cx<R> z, R nv) {
+  R o[BPS];
+  soft_demap<BPS>(z, nv, o);
+  if constexpr (BPS == 4 && sizeof(R) == 4) {
+    *reinterpret_cast<float4*>(lo) = make_float4(o[0], o[1], o[2], o[3]);
+  } else {
+#pragma unroll
+    for (int m = 0; m < BPS; m += 2) *reinterpret_cast<cx<R>*>(lo + m) = mkc(o[m], o[m + 1]);
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Data path: one slot per (frame, OFDM symbol).  Per RX: CP-remove + noise +
 // FFT/sqrt(N) (lte_receiver.py:444-491); then
 //  UNCODED: ZF Y/(H+1e-6) (lte_receiver.py:154-180) -> hard bits -> bit errors
 //  CODED:   ZF -> sigma2_eff (ofdm_core.py:1224-1243) -> LLRs (RE order)
 //  SIMO:    MRC sum conj(H_i)Y_i / (sum|H_i|^2 + 1e-10) (ofdm_core.py:1405-1534)
+//  SIMO_CODED: SIMO's z -> sigma2_eff = max(s2 / clip(D), s2 / 4), D = sum|H_i|^2,
+//           on either channel -> CODED's outputs (include/lte_phy.h)
 // Templated on chain and bits/symbol so every per-RE array stays in VGPRs.
 //  SCF (SC-FDM, UNCODED): the ZF outputs of the symbol's Nd data REs go
 //       through the M = Nd IDFT (core/lte_receiver.py:318-333) before slicing.
@@ -1254,7 +1270,10 @@ __global__ __launch_bounds__(WG) void k_rx_data(Grid g, int rayleigh, int B, int
   const R sc = rx_scale<R>(N);
   constexpr R QS = (R)qam_norm<BPS>();
   constexpr int QM = 4;  // data REs per thread (Nd < N/2 for every LTE profile)
-  constexpr int NRX = CHAIN == LTE_CHAIN_SIMO ? 8 : 1;
+  // SIMO_CODED: the MRC sums of SIMO, then CODED's soft output with sigma^2 / D
+  constexpr bool MRC = CHAIN == LTE_CHAIN_SIMO || CHAIN == LTE_CHAIN_SIMO_CODED;
+  constexpr bool SOFT = CHAIN == LTE_CHAIN_CODED || CHAIN == LTE_CHAIN_SIMO_CODED;
+  constexpr int NRX = MRC ? 8 : 1;
   V num[QM];
   R den[QM];
 #pragma unroll
@@ -1276,7 +1295,7 @@ __global__ __launch_bounds__(WG) void k_rx_data(Grid g, int rayleigh, int B, int
         if (j < g.Nd) {
           const int k = g.data_idx[j];
           const V Y = cscale(buf[k], sc), h = Hf[k];
-          if constexpr (CHAIN == LTE_CHAIN_SIMO) {
+          if constexpr (MRC) {
             num[q] = cadd(num[q], cmulc(Y, h));
             den[q] += abs2_ref(h);
           } else {
@@ -1316,29 +1335,22 @@ __global__ __launch_bounds__(WG) void k_rx_data(Grid g, int rayleigh, int B, int
     if (!active || j >= g.Nd) continue;
     const int re = l * g.Nd + j;
     V z = num[q];
-    if constexpr (CHAIN == LTE_CHAIN_SIMO) {
+    if constexpr (MRC) {
       const R r = (R)1 / (den[q] + (R)1e-10);
       z = mkc(z.x * r, z.y * r);
     }
     if (cap_syms) cap_syms[fre + re] = z;
-    if constexpr (CHAIN == LTE_CHAIN_CODED) {
+    if constexpr (SOFT) {
       const R s2 = (R)1 / snr_lin[b];
       R nv = s2;
-      if (rayleigh) nv = fmax(s2 / fmin(fmax(den[q], (R)1e-6), (R)1e6), s2 / (R)4);
+      // (MRC divides by D = den on either channel type)
+      if (rayleigh || MRC) nv = fmax(s2 / fmin(fmax(den[q], (R)1e-6), (R)1e6), s2 / (R)4);
       if (nvo) {   // demap in k_dematch_zn: the equalised symbol and sigma^2_eff per (group, subcarrier)
         reinterpret_cast<V*>(llr)[fre + re] = z;
         nvo[((size_t)b * g.n_grp + grp) * g.Nd + j] = nv;
         continue;
       }
-      R o[BPS];
-      soft_demap<BPS>(z, nv, o);
-      R* lo = llr + (fre + re) * BPS;
-      if constexpr (BPS == 4 && sizeof(R) == 4) {
-        *reinterpret_cast<float4*>(lo) = make_float4(o[0], o[1], o[2], o[3]);
-      } else {
-#pragma unroll
-        for (int m = 0; m < BPS; m += 2) *reinterpret_cast<V*>(lo + m) = mkc(o[m], o[m + 1]);
-      }
+      store_llrs<R, BPS>(llr + (fre + re) * BPS, z, nv);
     } else {
       const int idx = hard_index(z, BPS, QS);
       const int64_t pb0 = (int64_t)re * BPS;
@@ -1351,7 +1363,7 @@ __global__ __launch_bounds__(WG) void k_rx_data(Grid g, int rayleigh, int B, int
     }
   }
   // one atomic per frame per wave (all lanes reach this point; inactive lanes carry 0)
-  if constexpr (CHAIN != LTE_CHAIN_CODED) frame_err_add(frame_err, b, errs);
+  if constexpr (!SOFT) frame_err_add(frame_err, b, errs);
 }
 
 // ---------------------------------------------------------------------------
@@ -1525,15 +1537,7 @@ __global__ __launch_bounds__(WG, RXF_WAVES) void k_rx_frame(Grid g, int rayleigh
           // demap in k_dematch_zn: the equalised symbol (sigma^2_eff per subcarrier in nvo)
           reinterpret_cast<V*>(llr)[fre + re] = z;
         } else if constexpr (CHAIN == LTE_CHAIN_CODED) {
-          R o[BPS];
-          soft_demap<BPS>(z, nvq[q], o);
-          R* lo = llr + (fre + re) * BPS;
-          if constexpr (BPS == 4 && sizeof(R) == 4) {
-            *reinterpret_cast<float4*>(lo) = make_float4(o[0], o[1], o[2], o[3]);
-          } else {
-#pragma unroll
-            for (int m = 0; m < BPS; m += 2) *reinterpret_cast<V*>(lo + m) = mkc(o[m], o[m + 1]);
-          }
+          store_llrs<R, BPS>(llr + (fre + re) * BPS, z, nvq[q]);
         } else {
           const int idx = hard_index(z, BPS, QS);
           const int64_t pb0 = (int64_t)re * BPS;
@@ -1612,12 +1616,38 @@ __device__ __forceinline__ cx<R> interp_seg(const cx<R>* hp, int np, int sidx, R
   return mkc(fk * ((v1.x - v0.x) * ig) + v0.x, fk * ((v1.y - v0.y) * ig) + v0.y);
 }
 
-template <class R, int BPS, int NC = 0>
-__global__ __launch_bounds__(WG, RXF_WAVES) void k_rx_frame_simo(
+// k_rx_frame_simo*'s SOFT (LTE_CHAIN_SIMO_CODED, include/lte_phy.h): the same MRC sums feed the
+// coded chain's soft output instead of the hard decision -- no bit errors are
+// counted here (k_crc_count does, after the decoder).  RXS_SOFT_ZN: z per RE
+// into llr (viewed as cx<R>) and sigma^2_eff = max(s2 / clip(D, 1e-6, 1e6),
+// s2 / 4), s2 = 1 / snr_lin, per (frame, group, data subcarrier) into nvo at
+// each estimate, k_rx_frame<.., ZN>'s layout for k_dematch_zn; RXS_SOFT_LLR: BPS
+// max-log LLRs per RE in RE order for k_dematch.  D is the group's sum_r
+// |H_r|^2 the combiner divides by, on either channel type.
+constexpr int RXS_HARD = 0, RXS_SOFT_LLR = 1, RXS_SOFT_ZN = 2;
+template <class R>
+__device__ __forceinline__ R mrc_sigma2_eff(R s2, R D) {
+  return fmax(s2 / fmin(fmax(D, (R)1e-6), (R)1e6), s2 / (R)4);
+}
+
+// The float64 soft instances of k_rx_frame_simo are bounded for 2 waves per
+// SIMD: at RXF_WAVES = 3 (168 VGPRs) they spill 10..24 VGPRs to scratch, as the
+// uncoded float64 instances do; with 256 VGPRs they keep everything in registers.
+// Measured: the spilling 3-wave form is 4-9 % faster in the
+// receiver slot (0.4-1 % of a decoder-bound step); no scratch is the default.
+#ifndef RXS_SOFT_WAVES64   // waves per SIMD of the float64 soft instances (A/B builds: 3 = the uncoded bound)
+#define RXS_SOFT_WAVES64 2
+#endif
+template <class R, int SOFT>
+constexpr int rxs_waves() { return SOFT != RXS_HARD && sizeof(R) == 8 ? RXS_SOFT_WAVES64 : RXF_WAVES; }
+
+template <class R, int BPS, int NC = 0, int SOFT = RXS_HARD>
+__global__ __launch_bounds__(WG, (rxs_waves<R, SOFT>())) void k_rx_frame_simo(
     Grid g, int B, int num_rx, const cx<R>* __restrict__ y, int64_t y_rx_stride, int64_t y_frame_stride,
     const R* __restrict__ npow, const uint64_t* __restrict__ fid, uint64_t seed, const R* __restrict__ inj_z,
     int64_t inj_stride, const uint32_t* __restrict__ pw, int PW, int n_bits, uint32_t* __restrict__ frame_err,
-    cx<R>* __restrict__ cap_syms, uint8_t* __restrict__ cap_bits, cx<R>* __restrict__ H, R* __restrict__ pstats) {
+    cx<R>* __restrict__ cap_syms, uint8_t* __restrict__ cap_bits, cx<R>* __restrict__ H, R* __restrict__ pstats,
+    const R* __restrict__ snr_lin, R* __restrict__ llr, R* __restrict__ nvo) {
   using V = cx<R>;
   using G = GridT<R>;
   V* sm = dyn_lds<V>();
@@ -1724,6 +1754,16 @@ __global__ __launch_bounds__(WG, RXF_WAVES) void k_rx_frame_simo(
         const R rr = (R)1 / (den[q] + (R)1e-10);
         const V z = mkc(num[q].x * rr, num[q].y * rr);
         if (cap_syms) cap_syms[fre + re] = z;
+        if constexpr (SOFT != RXS_HARD) {
+          const R s2 = (R)1 / snr_lin[b];
+          if constexpr (SOFT == RXS_SOFT_ZN) {
+            reinterpret_cast<V*>(llr)[fre + re] = z;
+            if (est) nvo[((size_t)b * g.n_grp + grp) * g.Nd + j] = mrc_sigma2_eff(s2, den[q]);
+          } else {
+            store_llrs<R, BPS>(llr + (fre + re) * BPS, z, mrc_sigma2_eff(s2, den[q]));
+          }
+          continue;
+        }
         const int idx = hard_index(z, BPS, QS);
         const int64_t pb0 = (int64_t)re * BPS;
         errs += __popc(((uint32_t)idx ^ getbits<BPS>(fb, pb0, n_bits)) & bits_valid<BPS>(pb0, n_bits));
@@ -1735,7 +1775,7 @@ __global__ __launch_bounds__(WG, RXF_WAVES) void k_rx_frame_simo(
       }
     }
   }
-  frame_err_add(frame_err, b, errs);
+  if constexpr (SOFT == RXS_HARD) frame_err_add(frame_err, b, errs);
 }
 
 // k_rx_frame_simo2<.., XIN>'s loader: RX rx's N samples of symbol l formed
@@ -1796,12 +1836,16 @@ __device__ __forceinline__ void tap_symbol_noisy2(V* buf, const V* xs, const V (
 // (TxChannelT::x_out): each symbol is staged in LDS once and every RX forms its
 // samples with its own taps (tap_symbol_noisy2) -- one stream through HBM
 // instead of num_rx, both ways.
-template <class R, int BPS, int NC, bool XIN = false>
+// SOFT: as k_rx_frame_simo's (the coded chain takes no symbol hand-over: XIN
+// stays an uncoded form).
+template <class R, int BPS, int NC, bool XIN = false, int SOFT = RXS_HARD>
 __global__ __launch_bounds__(WG, RXF_WAVES) void k_rx_frame_simo2(
     Grid g, int B, int num_rx, const cx<R>* __restrict__ y, int64_t y_rx_stride, int64_t y_frame_stride,
     const R* __restrict__ npow, const uint64_t* __restrict__ fid, uint64_t seed, const R* __restrict__ inj_z,
     int64_t inj_stride, const uint32_t* __restrict__ pw, int PW, int n_bits, uint32_t* __restrict__ frame_err,
-    cx<R>* __restrict__ cap_syms, uint8_t* __restrict__ cap_bits, TxChannelT<R> xc) {
+    cx<R>* __restrict__ cap_syms, uint8_t* __restrict__ cap_bits, TxChannelT<R> xc, const R* __restrict__ snr_lin,
+    R* __restrict__ llr, R* __restrict__ nvo) {
+  static_assert(!XIN || SOFT == RXS_HARD, "the symbol hand-over is uncoded only");
   using V = cx<R>;
   using G = GridT<R>;
   constexpr int N = NC, T = N >> 3;
@@ -1905,6 +1949,16 @@ __global__ __launch_bounds__(WG, RXF_WAVES) void k_rx_frame_simo2(
       const R rr = (R)1 / (den[q] + (R)1e-10);
       const V z = mkc(num[q].x * rr, num[q].y * rr);
       if (cap_syms) cap_syms[fre + re] = z;
+      if constexpr (SOFT != RXS_HARD) {
+        const R s2 = (R)1 / snr_lin[b];
+        if constexpr (SOFT == RXS_SOFT_ZN) {
+          reinterpret_cast<V*>(llr)[fre + re] = z;
+          if (est) nvo[((size_t)b * g.n_grp + l / 14) * g.Nd + j] = mrc_sigma2_eff(s2, den[q]);
+        } else {
+          store_llrs<R, BPS>(llr + (fre + re) * BPS, z, mrc_sigma2_eff(s2, den[q]));
+        }
+        continue;
+      }
       const int idx = hard_index(z, BPS, QS);
       const int64_t pb0 = (int64_t)re * BPS;
       errs += __popc(((uint32_t)idx ^ getbits<BPS>(fb, pb0, n_bits)) & bits_valid<BPS>(pb0, n_bits));
@@ -1915,7 +1969,7 @@ __global__ __launch_bounds__(WG, RXF_WAVES) void k_rx_frame_simo2(
       }
     }
   }
-  frame_err_add(frame_err, b, errs);
+  if constexpr (SOFT == RXS_HARD) frame_err_add(frame_err, b, errs);
 }
 
 bool rx_frame_simo_supported(const Grid& g, int num_rx) {
@@ -1931,36 +1985,47 @@ int launch_rx_frame_simo(hipStream_t s, const Grid& g, int B, int num_rx, const 
                          int64_t y_frame_stride, const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z,
                          int64_t inj_stride, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
                          cx<R>* cap_syms, uint8_t* cap_bits, cx<R>* H, R* pstats, int pairs,
-                         const TxChannelT<R>* xc) {
+                         const TxChannelT<R>* xc, const R* snr_lin, R* llr, R* nv_out) {
   if (!rx_frame_simo_supported(g, num_rx)) return (int)hipErrorInvalidValue;
+  // soft output (llr non-null): (z, nv) with nv_out, else LLRs; the (z, nv) hand-off is 16 / 64-QAM's
+  const int soft = !llr ? RXS_HARD : nv_out ? RXS_SOFT_ZN : RXS_SOFT_LLR;
+  if (soft != RXS_HARD && (!snr_lin || (xc && xc->x_out))) return (int)hipErrorInvalidValue;
+  if ((soft == RXS_SOFT_ZN && g.bps == 2) || (soft == RXS_HARD && nv_out)) return (int)hipErrorInvalidValue;
   if (pairs) {   // k_rx_frame_simo2
     if (!rx_simo2_ok(g, num_rx, H != nullptr, pstats != nullptr)) return (int)hipErrorInvalidValue;
     const bool xin = xc && xc->x_out;
     const size_t shm2 = (2 * (size_t)g.N + RXS_MAXRX * g.Np + (xin ? g.N : 0)) * sizeof(cx<R>);
     const TxChannelT<R> xcv = xin ? *xc : TxChannelT<R>{};
+#define LTE_RXS2_GO(BPS_, XIN_, SOFT_)                                                                               \
+  hipLaunchKernelGGL((k_rx_frame_simo2<R, BPS_, 1024, XIN_, SOFT_>), dim3(B), dim3(WG), shm2, s, g, B, num_rx, y,    \
+                     y_rx_stride, y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,     \
+                     cap_syms, cap_bits, xcv, snr_lin, llr, nv_out)
 #define LTE_RXS2(BPS_)                                                                                               \
   do {                                                                                                               \
-    if (xin)                                                                                                         \
-      hipLaunchKernelGGL((k_rx_frame_simo2<R, BPS_, 1024, true>), dim3(B), dim3(WG), shm2, s, g, B, num_rx, y,       \
-                         y_rx_stride, y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err, \
-                         cap_syms, cap_bits, xcv);                                                                   \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_rx_frame_simo2<R, BPS_, 1024>), dim3(B), dim3(WG), shm2, s, g, B, num_rx, y, y_rx_stride, \
-                         y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err, cap_syms,    \
-                         cap_bits, xcv);                                                                             \
+    if (xin) LTE_RXS2_GO(BPS_, true, RXS_HARD);                                                                      \
+    else if (soft == RXS_SOFT_LLR) LTE_RXS2_GO(BPS_, false, RXS_SOFT_LLR);                                           \
+    else if (soft == RXS_SOFT_ZN) LTE_RXS2_GO(BPS_, false, (BPS_ == 2 ? RXS_SOFT_LLR : RXS_SOFT_ZN));                \
+    else LTE_RXS2_GO(BPS_, false, RXS_HARD);                                                                         \
   } while (0)
     if (g.bps == 2) LTE_RXS2(2); else if (g.bps == 4) LTE_RXS2(4); else LTE_RXS2(6);
 #undef LTE_RXS2
+#undef LTE_RXS2_GO
     return (int)hipGetLastError();
   }
   if (xc && xc->x_out) return (int)hipErrorInvalidValue;   // the symbol handoff needs the paired receiver
   const int spw = WG / (g.N >> 3);
   const int blocks = (B + spw - 1) / spw;
   const size_t shm = (size_t)spw * (g.N + RXS_MAXRX * g.Np) * sizeof(cx<R>);
+#define LTE_RXS_GO(BPS_, NC_, SOFT_)                                                                                 \
+  hipLaunchKernelGGL((k_rx_frame_simo<R, BPS_, NC_, SOFT_>), dim3(blocks), dim3(WG), shm, s, g, B, num_rx, y,        \
+                     y_rx_stride, y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,     \
+                     cap_syms, cap_bits, H, pstats, snr_lin, llr, nv_out)
 #define LTE_RXS(BPS_, NC_)                                                                                           \
-  hipLaunchKernelGGL((k_rx_frame_simo<R, BPS_, NC_>), dim3(blocks), dim3(WG), shm, s, g, B, num_rx, y, y_rx_stride,  \
-                     y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err, cap_syms,        \
-                     cap_bits, H, pstats)
+  do {                                                                                                               \
+    if (soft == RXS_SOFT_LLR) LTE_RXS_GO(BPS_, NC_, RXS_SOFT_LLR);                                                   \
+    else if (soft == RXS_SOFT_ZN) LTE_RXS_GO(BPS_, NC_, (BPS_ == 2 ? RXS_SOFT_LLR : RXS_SOFT_ZN));                   \
+    else LTE_RXS_GO(BPS_, NC_, RXS_HARD);                                                                            \
+  } while (0)
 #define LTE_RXS_BPS(NC_)                                                                                             \
   do {                                                                                                               \
     if (g.bps == 2) LTE_RXS(2, NC_);                                                                                 \
@@ -1971,6 +2036,7 @@ int launch_rx_frame_simo(hipStream_t s, const Grid& g, int B, int num_rx, const 
   else LTE_RXS_BPS(0);
 #undef LTE_RXS_BPS
 #undef LTE_RXS
+#undef LTE_RXS_GO
   return (int)hipGetLastError();
 }
 
@@ -1997,10 +2063,10 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
                    int n_bits, uint32_t* frame_err, R* llr, cx<R>* cap_syms, uint8_t* cap_bits, int sc_fdm,
                    R* nv_out) {
   if (g.bps != 2 && g.bps != 4 && g.bps != 6) return (int)hipErrorInvalidValue;
-  if (nv_out && chain != LTE_CHAIN_CODED) return (int)hipErrorInvalidValue;
+  if (nv_out && chain != LTE_CHAIN_CODED && chain != LTE_CHAIN_SIMO_CODED) return (int)hipErrorInvalidValue;
   if (sc_fdm && (chain != LTE_CHAIN_UNCODED || !GridT<R>::chirp(g) || !GridT<R>::bhat(g)))
     return (int)hipErrorInvalidValue;
-  if (chain == LTE_CHAIN_SIMO && num_rx > 8) return (int)hipErrorInvalidValue;
+  if ((chain == LTE_CHAIN_SIMO || chain == LTE_CHAIN_SIMO_CODED) && num_rx > 8) return (int)hipErrorInvalidValue;
   const int spw = WG / (g.N >> 3);
   const int64_t total = (int64_t)B * g.n_sym;
   if (total > 0x7FFFFFFF - spw) return (int)hipErrorInvalidValue;
@@ -2013,6 +2079,7 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
   if (chain == LTE_CHAIN_CODED && g.N == 2048) LTE_RXA(LTE_CHAIN_CODED, false, 2048);   // the headline chain
   else if (chain == LTE_CHAIN_CODED) LTE_RXA(LTE_CHAIN_CODED, false, 0);
   else if (chain == LTE_CHAIN_SIMO) LTE_RXA(LTE_CHAIN_SIMO, false, 0);
+  else if (chain == LTE_CHAIN_SIMO_CODED) LTE_RXA(LTE_CHAIN_SIMO_CODED, false, 0);
   else if (sc_fdm) LTE_RXA(LTE_CHAIN_UNCODED, true, 0);
   else LTE_RXA(LTE_CHAIN_UNCODED, false, 0);
 #undef LTE_RXA
@@ -2041,7 +2108,8 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
                                  const uint32_t*, int, int, uint32_t*, R*, cx<R>*, uint8_t*, int, R*);              \
   template int launch_rx_frame_simo<R>(hipStream_t, const Grid&, int, int, const cx<R>*, int64_t, int64_t, const R*,  \
                                        const uint64_t*, uint64_t, const R*, int64_t, const uint32_t*, int, int,       \
-                                       uint32_t*, cx<R>*, uint8_t*, cx<R>*, R*, int, const TxChannelT<R>*);          \
+                                       uint32_t*, cx<R>*, uint8_t*, cx<R>*, R*, int, const TxChannelT<R>*,           \
+                                       const R*, R*, R*);                                                              \
   template int launch_rx_frame<R>(hipStream_t, const Grid&, int, int, int, const cx<R>*, int64_t, const R*, const R*, \
                                   const uint64_t*, uint64_t, const R*, int64_t, const uint32_t*, int, int, uint32_t*, \
                                   R*, cx<R>*, uint8_t*, R*, cx<R>*, R*);

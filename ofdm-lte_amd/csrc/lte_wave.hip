@@ -626,8 +626,10 @@ void k_rx_frame_simo_w(Grid g, int B, int num_rx, int yrow, const double2* __res
   frame_err_add(frame_err, b, errs);
 }
 
-bool rx_simo_w_supported(const Grid& g, int num_rx, int f64, bool H, bool pstats, bool xin) {
-  return f64 && g.N == 1024 && g.kinfo && g.pilots64 && g.cp % 2 == 0 && num_rx >= 1 && num_rx <= SIMOW_WAVES &&
+bool rx_simo_w_supported(const Grid& g, int chain, int num_rx, int f64, bool H, bool pstats, bool xin) {
+  // uncoded only: LTE_CHAIN_SIMO_CODED's soft output is k_rx_frame_simo*'s
+  return chain == LTE_CHAIN_SIMO && f64 && g.N == 1024 && g.kinfo && g.pilots64 && g.cp % 2 == 0 && num_rx >= 1 &&
+         num_rx <= SIMOW_WAVES &&
          num_rx <= RXS_MAXRX && !H && !pstats && !xin && g.Nd <= 2 * 64 * SIMOW_WAVES && g.Np >= 1 &&
          (g.bps == 2 || g.bps == 4 || g.bps == 6);
 }
@@ -893,7 +895,7 @@ int launch_rx_frame_simo_w(hipStream_t s, const Grid& g, int B, int num_rx, cons
                            int64_t y_frame_stride, const double* npow, const uint64_t* fid, uint64_t seed,
                            const double* inj_z, int64_t inj_stride, const uint32_t* pw, int PW, int n_bits,
                            uint32_t* frame_err, double2* cap_syms, uint8_t* cap_bits) {
-  if (!rx_simo_w_supported(g, num_rx, 1, false, false, false)) return (int)hipErrorInvalidValue;
+  if (!rx_simo_w_supported(g, LTE_CHAIN_SIMO, num_rx, 1, false, false, false)) return (int)hipErrorInvalidValue;
   const int yrow = g.Nd > SIMOW_ROW_MIN ? g.Nd : SIMOW_ROW_MIN;
   const size_t shm = ((size_t)SIMOW_WAVES * yrow + (size_t)num_rx * g.Np) * sizeof(double2) +
                      (size_t)2 * 64 * SIMOW_WAVES * sizeof(int2) + (size_t)g.Np * sizeof(double);

@@ -15,6 +15,12 @@ import numpy as np
 from . import _capi as C
 
 
+# Plan.coded / Plan.mimo by chain, as lte_plan_create classifies them: the coded
+# SIMO chain decodes but is a SISO-family chain (one TX, the SISO capture shapes)
+CODED_CHAINS = (C.CHAIN_CODED, C.CHAIN_SFBC_CODED, C.CHAIN_SIMO_CODED)
+MIMO_CHAINS = (C.CHAIN_SFBC, C.CHAIN_SFBC_CODED, C.CHAIN_SPATIAL)
+
+
 class RunResult(dict):
     """Plan.run's outputs by name (counts, frame_errors, the captures); .path:
     the kernel path the run took (lte_run_path) as a dict of its fields."""
@@ -85,9 +91,9 @@ class Plan:
         self.num_rx, self.N, self.bps, self.n_bits, self.max_frames = num_rx, N, bps, int(n_bits), int(max_frames)
         self.chain = chain
         self.num_tx = int(num_tx)
-        self.coded = chain in (C.CHAIN_CODED, C.CHAIN_SFBC_CODED)
+        self.coded = chain in CODED_CHAINS
         self.bf = chain == C.CHAIN_BEAMFORMING
-        self.mimo = chain >= C.CHAIN_SFBC and not self.bf
+        self.mimo = chain in MIMO_CHAINS
         sfbc = chain in (C.CHAIN_SFBC, C.CHAIN_SFBC_CODED)
         # multi-antenna geometry (lte_capi.hip lte_plan_create): REs per OFDM symbol,
         # data SCs carrying data, channel estimates per frame

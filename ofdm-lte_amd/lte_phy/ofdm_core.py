@@ -655,6 +655,59 @@ class OFDMSimulator:
         self.last_results = res
         return res
 
+    # -------------------------------------------------------------- SIMO + turbo
+    def simulate_simo_coded(self, bits: np.ndarray, snr_db: float = 10.0, num_rx: int = 2) -> Dict:
+        """1 x num_rx MRC receive diversity with turbo coding (LTE_CHAIN_SIMO_CODED,
+        include/lte_phy.h; not in the reference, which has no coded SIMO driver):
+        simulate_siso_coded's coding chain around simulate_simo's link and
+        combiner.  The LLRs are formed on z = sum(conj(H_i) Y_i)/(sum|H_i|^2 +
+        1e-10) with sigma^2_eff = max(sigma^2 / clip(D, 1e-6, 1e6), sigma^2 / 4),
+        D = sum|H_i|^2, on either channel type.  One GPU call; the global RNG is
+        consumed as simulate_simo consumes it.  Returns simulate_siso_coded's keys
+        with signal_rx_list (one stream per RX) for signal_rx, channel_gain (D per
+        coded symbol, de-interleaved) for H_estimate, no channel_snr_db, and
+        num_rx / combining_method."""
+        bits = self._bits_in(bits)
+        if num_rx < 1:
+            raise ValueError("num_rx must be >= 1")
+        n0 = len(bits)
+        plan = self._plan(C.CHAIN_SIMO_CODED, 0, n0, num_rx=num_rx, iters=8)
+        ph, z = self._ref_draws(plan.L, num_rx)
+        r = plan.run([snr_db], bits=(bits & 1).astype(np.uint8)[None], phases=ph[None] if ph.size else None,
+                     noise=z[None], capture=('signal_tx', 'signal_rx', 'data_syms', 'bits_rx', 'tx_syms', 'H'))
+        bps, Nd = self.config.bits_per_symbol, self.Nd
+        coded = plan.coded_bits
+        dec = r['bits_rx'][0].astype(np.uint8)
+        err = int(np.sum(bits != dec))
+        sig_tx = r['signal_tx'][0].astype(np.complex128)
+        pa = papr(sig_tx)
+        # T/F de-interleave of the captured TX / RX REs, as simulate_siso_coded
+        ncs_tx = -(-coded // bps)
+        rows = -(-ncs_tx // Nd)
+        q = np.arange(ncs_tx)
+        qam = r['tx_syms'][0].astype(np.complex128)[(q % Nd) * rows + q // Nd]
+        ncs = coded // bps
+        rows_rx = -(-ncs // Nd)
+        q = np.arange(ncs)
+        src = (q % Nd) * rows_rx + q // Nd
+        Hs = r['H'][0].astype(np.complex128)                           # [num_rx][n_grp][N]
+        Dg = np.zeros((plan.n_grp, Nd))
+        for a in range(num_rx):                                        # RX order, as the combiner sums
+            Dg += np.abs(Hs[a][:, self.grid._data]) ** 2
+        gain = np.concatenate([Dg[l // SLOT_SIZE] for l in range(plan.n_sym)])[src]
+        s2 = 1.0 / (10 ** (snr_db / 10))
+        nv = np.maximum(s2 / np.clip(gain, 1e-6, 1e6), s2 / 4.0)
+        res = {'transmitted_bits': int(n0), 'received_bits': int(n0), 'bits_received_array': dec,
+               'bit_errors': err, 'ber': float(err / n0), 'crc_pass': bool(r['crc_ok'][0]),
+               'snr_db': float(snr_db), 'papr_db': float(pa['papr_db']), 'papr_linear': float(pa['papr_linear']),
+               'coded_bits_length': int(coded), 'signal_tx': sig_tx,
+               'signal_rx_list': [r['signal_rx'][0, i].astype(np.complex128) for i in range(num_rx)],
+               'symbols_tx': qam, 'symbols_rx': r['data_syms'][0].astype(np.complex128)[src],
+               'channel_gain': gain, 'noise_var_mean': float(np.mean(nv)), 'num_rx': num_rx,
+               'combining_method': 'mrc'}
+        self.last_results = res
+        return res
+
     # -------------------------------------------------------------- SFBC (config 4)
     def _sfbc_plan(self, n_sym, n_bits, num_rx, coded=False, max_frames=1, iters=8, early_stop=False):
         cfg, ch = self.config, self.channels[0]
@@ -795,7 +848,9 @@ class OFDMSimulator:
         world_size > 1 this process handles trials t = rank, rank+W, ... and
         the caller all-reduces the returned `counts`.
 
-        mimo=None: SISO (coded: config 2) / SIMO MRC (num_rx > 1: config 3);
+        mimo=None: SISO (coded: config 2) / SIMO MRC (num_rx > 1: config 3;
+        coded with num_rx > 1: the coded SIMO chain, config 2's coding around
+        config 3's link and combiner, simulate_simo_coded);
         mimo='sfbc': 2 x num_rx Alamouti (coded: config 4);
         mimo='spatial': TM4 (config 5 = 4x4 rank-4 PMI-0 MMSE; the spatial channel of
         simulate_spatial_multiplexing: gains converted once more, fD from
@@ -853,7 +908,8 @@ class OFDMSimulator:
             raise ValueError(f"unknown mimo mode {mimo!r}")
         elif coded:
             nb = int(n_bits or 27760)
-            plan = self._plan(C.CHAIN_CODED, 0, nb, max_frames=frames_per_call, iters=turbo_iters,
+            chain = C.CHAIN_SIMO_CODED if num_rx > 1 else C.CHAIN_CODED
+            plan = self._plan(chain, 0, nb, num_rx=num_rx, max_frames=frames_per_call, iters=turbo_iters,
                               early_stop=early_stop)
         else:
             nb = int(n_bits or SLOT_SIZE * self.Nd * cfg.bits_per_symbol)

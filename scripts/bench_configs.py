@@ -35,6 +35,16 @@ def configs(lte_phy, C):
         s = O(Cfg(bandwidth=10.0, modulation='16-QAM'), channel_type='rayleigh_mp', itu_profile='Vehicular_A')
         return s._plan(C.CHAIN_SIMO, 14, 14 * s.Nd * 4, num_rx=4, max_frames=F)
 
+    def c2mrc(num_rx):   # config 2's coding around config 3's link and combiner (LTE_CHAIN_SIMO_CODED)
+        def f(F):
+            s = O(Cfg(bandwidth=20.0, modulation='64-QAM'), channel_type='rayleigh_mp', itu_profile='Pedestrian_A')
+            return s._plan(C.CHAIN_SIMO_CODED, 0, 27760, num_rx=num_rx, max_frames=F)
+        return f
+
+    def c3cod(F):        # config 3's numerology and link, coded: TB 9000 = 14 OFDM symbols
+        s = O(Cfg(bandwidth=10.0, modulation='16-QAM'), channel_type='rayleigh_mp', itu_profile='Vehicular_A')
+        return s._plan(C.CHAIN_SIMO_CODED, 0, 9000, num_rx=4, max_frames=F)
+
     def c4(F):
         s = O(Cfg(bandwidth=20.0, modulation='64-QAM'), channel_type='rayleigh_mp', itu_profile='Pedestrian_A')
         return s._sfbc_plan(0, 27760, 2, coded=True, max_frames=F)
@@ -78,7 +88,10 @@ def configs(lte_phy, C):
     return {
         'c1': ('config 1: SISO 1.25 MHz QPSK AWGN, 14 symbols uncoded', c1),
         'c2': ('config 2: SISO 20 MHz 64-QAM PedA + turbo (TB 27760)', c2),
+        'c2mrc2': ('config 2 + MRC: SIMO 1x2 MRC + turbo, 20 MHz 64-QAM PedA (TB 27760)', c2mrc(2)),
+        'c2mrc4': ('config 2 + MRC: SIMO 1x4 MRC + turbo, 20 MHz 64-QAM PedA (TB 27760)', c2mrc(4)),
         'c3': ('config 3: SIMO 1x4 MRC 10 MHz 16-QAM VehA, 14 symbols uncoded', c3),
+        'c3cod': ('config 3 + turbo: SIMO 1x4 MRC + turbo, 10 MHz 16-QAM VehA (TB 9000)', c3cod),
         'c4': ('config 4: SFBC 2x2 Alamouti + turbo, 20 MHz 64-QAM PedA (TB 27760)', c4),
         'c5': ('config 5: spatial 4x4 rank-4 MMSE, 20 MHz 64-QAM, flat CN(0,1) links', c5('awgn')),
         'c5r': ('config 5: spatial 4x4 rank-4 MMSE, 20 MHz 64-QAM, PedA 3 km/h links', c5('rayleigh_mp')),
