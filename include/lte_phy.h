@@ -213,6 +213,10 @@ int lte_version(void);                     /* ABI version: LTE_ABI_VERSION (3) *
  * implements the ABI of the header the caller was compiled against, LTE_EUNSUP
  * (with lte_last_error() naming both versions) otherwise. */
 int lte_abi_check(int abi_version);
+/* Diagnostic: bytes of device memory the library holds in this process at this
+ * moment, over every plan and every call in flight (an addition to ABI 3).  A
+ * plan's create / destroy pair and any completed stage call leave it unchanged. */
+int64_t lte_device_bytes_held(void);
 
 /* Plans. */
 int lte_plan_create(const lte_plan_desc *desc, lte_plan **out);

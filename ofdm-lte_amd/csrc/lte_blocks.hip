@@ -1,5 +1,5 @@
 // Kernels behind the stage entries of the reference's building-block classes
-// (lte_capi.hip: lte_qam_map_host64, lte_chest_host64, lte_zf_host64), float64
+// (lte_stages.hip: lte_qam_map_host64, lte_chest_host64, lte_zf_host64), float64
 // with NumPy's operation order and no contraction into FMAs, so the results
 // are the reference's to the last bit wherever NumPy's own operations are
 // correctly rounded:

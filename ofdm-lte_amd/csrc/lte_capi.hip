@@ -1,7 +1,7 @@
 // C ABI of liblte_hip.so (include/lte_phy.h): plan construction (all index /
 // permutation tables are built here, natively, once per configuration),
 // device workspace ownership, and orchestration of the kernel chain on the
-// plan's HIP stream.
+// plan's HIP stream.  The stand-alone stage entry points are in lte_stages.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,37 +9,30 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <vector>
 
-#include "lte_common.h"
-#include "lte_internal.h"
+#include "lte_plan.h"
 
 using namespace lte;
 
-namespace {
+// Host table builders; the ones lte_stages.hip shares are declared in lte_plan.h.
+namespace lte {
 
-thread_local std::string g_err;
+static thread_local std::string g_err;
 
 int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
 
-#define HIPCHK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t _e = (expr);                                                                  \
-    if (_e != hipSuccess) return fail(LTE_EHIP, std::string(#expr ": ") + hipGetErrorString(_e)); \
-  } while (0)
-#define LCHK(expr)                                                                           \
-  do {                                                                                       \
-    int _e = (expr);                                                                         \
-    if (_e != 0) return fail(LTE_EHIP, std::string(#expr ": ") + hipGetErrorString((hipError_t)_e)); \
-  } while (0)
+std::atomic<int64_t> g_dev_bytes{0};
 
 // ------------------------------------------------------------------ MT19937
 // NumPy legacy RandomState: seed(s) = init_genrand(s); choice([1,-1], n) =
 // randint(0, 2, n) = (next_uint32 & 1) per draw (masked bounded ints).
+namespace {
 struct MT19937 {
   uint32_t mt[624];
   int idx;
@@ -64,6 +57,7 @@ struct MT19937 {
     return y;
   }
 };
+}  // namespace
 
 // QPP table (3GPP TS 36.212 Table 5.1.3-3; turbo_encoder.py:34-73)
 const int QPP_TAB[][3] = {
@@ -105,14 +99,14 @@ bool qpp_lookup(int K, int* f1, int* f2) {
   return false;
 }
 
-int find_interleaver_size(int n) {  // segmentation.py:53-71
+static int find_interleaver_size(int n) {  // segmentation.py:53-71
   for (int i = 0; i < N_QPP; ++i)
     if (QPP_TAB[i][0] >= n) return QPP_TAB[i][0];
   return -1;
 }
 
 // segment_code_blocks (segmentation.py:74-263) as a table of CB slots.
-bool segmentation_plan(int B, std::vector<CbInfo>& out) {
+static bool segmentation_plan(int B, std::vector<CbInfo>& out) {
   const int Z = 6144;
   out.clear();
   if (B <= Z) {
@@ -165,7 +159,6 @@ std::vector<int> subblock_perm(int n) {
 
 // Where coded bit i of CB (K, rv) comes from: stream (0/1/2) and index in that
 // stream, or stream -1 (padding of v1/v2).  rate_matching.py:249-297.
-struct RmSrc { int stream, idx; };
 void rm_source(int K, int rv, int E, std::vector<RmSrc>& out) {
   const int ml = K + 6, Ncb = 3 * ml;
   const int starts[4] = {0, Ncb / 4, Ncb / 2, 3 * Ncb / 4};
@@ -181,42 +174,14 @@ void rm_source(int K, int rv, int E, std::vector<RmSrc>& out) {
   }
 }
 
-// ------------------------------------------------------------------ buffers
-template <class T>
-struct DBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  int alloc(size_t count) {
-    if (count <= n && p) return 0;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-    if (count == 0) return 0;
-    if (hipMalloc(&p, count * sizeof(T)) != hipSuccess) return -1;
-    n = count;
-    return 0;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-};
-
 int ilog2(int n) {
   int l = 0;
   while ((1 << l) < n) ++l;
   return l;
 }
 
-struct GridHost {
-  int N, Nc, cp, Nd, Np;
-  std::vector<int32_t> data, pilot, seg;
-  std::vector<float> inv_gap;
-};
-
 // LTEResourceGrid._init_subcarrier_types (resource_mapper.py:57-93)
-GridHost make_grid(int N, int Nc, int cp) {
+static GridHost make_grid(int N, int Nc, int cp) {
   GridHost g;
   g.N = N; g.Nc = Nc; g.cp = cp;
   const int gl = (N - Nc) / 2, gr = N - Nc - gl, dc = N / 2;
@@ -240,14 +205,14 @@ GridHost make_grid(int N, int Nc, int cp) {
 }
 
 // Grid::kinfo: data ordinal, -(pilot ordinal + 2) or -1 per subcarrier
-std::vector<int32_t> make_kinfo(const GridHost& g) {
+static std::vector<int32_t> make_kinfo(const GridHost& g) {
   std::vector<int32_t> k(g.N, -1);
   for (int j = 0; j < g.Nd; ++j) k[g.data[j]] = j;
   for (int i = 0; i < g.Np; ++i) k[g.pilot[i]] = -(i + 2);
   return k;
 }
 
-std::vector<float2> make_constellation(int bps) {  // modulator.py:28-59
+static std::vector<float2> make_constellation(int bps) {  // modulator.py:28-59
   std::vector<float2> c;
   if (bps == 2) {
     const double s = 1.0 / std::sqrt(2.0);
@@ -340,159 +305,11 @@ void make_pilots(int cell, int n, std::vector<double>& re_im) {
   }
 }
 
-struct TableSet {  // device copies of the static grid tables for one N (f64 copies in f64 plans)
-  DBuf<int32_t> data, pilot, seg, kinfo;
-  DBuf<float> inv_gap;
-  DBuf<float2> pilots, tw, constel, chirp, bhat;
-  DBuf<double> inv_gap64;
-  DBuf<double2> pilots64, tw64, chirp64, bhat64;
-  void release() {
-    data.release(); pilot.release(); seg.release(); kinfo.release(); inv_gap.release(); pilots.release();
-    tw.release(); constel.release(); chirp.release(); bhat.release();
-    inv_gap64.release(); pilots64.release(); tw64.release(); chirp64.release(); bhat64.release();
-  }
-};
+// launch families of lte_timing_read (the KN_ ids of lte_plan.h)
+static const char* KNAMES[] = {"payload", "encode", "ofdm_tx", "fading", "channel", "rx_chest", "rx_data",
+                               "dematch", "turbo",   "crc_count", "accumulate", "capture", "harq"};
 
-// per-precision device buffers of the signal chains (R = float / double)
-template <class R>
-struct ChainBufs {
-  DBuf<cx<R>> x, y, coef, H, capbuf, captx, xh, tcoef;
-  DBuf<R> gains, phases, pow_part, pstats, npow, llr, snr_lin, inj_ph, inj_z;
-  // multi-antenna chains: received data SCs [B][n_sym][num_rx][n_dsc] (H holds
-  // the estimates [B][num_rx][n_est][num_tx][n_dsc]), transmit_mimo's link
-  // power partials / noise sigmas, link injections
-  DBuf<cx<R>> Ym;
-  DBuf<R> link_part, link_sigma, inj_lz, inj_lh;
-  std::vector<DBuf<R>> blk, ckpt;
-  DBuf<R*> blk_ptrs;
-  void release() {
-    x.release(); y.release(); coef.release(); H.release(); capbuf.release(); captx.release(); xh.release();
-    tcoef.release();
-    gains.release(); phases.release(); pow_part.release(); pstats.release(); npow.release(); llr.release();
-    snr_lin.release(); inj_ph.release(); inj_z.release();
-    Ym.release(); link_part.release(); link_sigma.release(); inj_lz.release(); inj_lh.release();
-    for (auto& b : blk) b.release();
-    for (auto& b : ckpt) b.release();
-    blk_ptrs.release();
-  }
-};
-
-template <class T>
-int upload(DBuf<T>& d, const std::vector<T>& h) {
-  if (d.alloc(std::max<size_t>(h.size(), 1))) return -1;
-  if (!h.empty() && hipMemcpy(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return -1;
-  return 0;
-}
-
-const char* KNAMES[] = {"payload", "encode", "ofdm_tx", "fading", "channel", "rx_chest", "rx_data",
-                        "dematch", "turbo",   "crc_count", "accumulate", "capture", "harq"};
-enum { KN_PAYLOAD, KN_ENCODE, KN_OFDM_TX, KN_FADING, KN_CHANNEL, KN_RX_CHEST, KN_RX_DATA, KN_DEMATCH, KN_TURBO,
-       KN_CRC, KN_ACC, KN_CAP, KN_HARQ, KN_COUNT };
-
-}  // namespace
-
-// ------------------------------------------------------------------ capture kernel
-namespace lte {
-// received stream with its noise, as the reference returns it (signal + noise)
-template <class R>
-__global__ void k_cap_rx(int L, int num_rx, int B, const cx<R>* __restrict__ y, int64_t y_rx_stride,
-                         int64_t y_frame_stride, const R* __restrict__ npow, const uint64_t* __restrict__ fid,
-                         uint64_t seed, const R* __restrict__ inj_z, int64_t inj_stride, cx<R>* __restrict__ out) {
-  const int nb = (L + 255) / 256;
-  const int n = (blockIdx.x % nb) * blockDim.x + threadIdx.x;
-  const int rx = blockIdx.y, b = blockIdx.x / nb;
-  if (n >= L) return;
-  const R sigma = sqrt(npow[(size_t)b * num_rx + rx] / (R)2);
-  cx<R> z;
-  if (inj_z) {
-    const R* zf = inj_z + (size_t)b * inj_stride + (size_t)rx * 2 * L;
-    z = mkc(zf[n], zf[L + n]);
-  } else {
-    const u32x4 r = rng4(seed, fid[b], RNG_STREAM_NOISE + (uint32_t)rx, (uint32_t)(n >> 1));
-    z = (n & 1) ? gauss2<R>(r.z, r.w) : gauss2<R>(r.x, r.y);
-  }
-  const cx<R> v = y[b * y_frame_stride + rx * y_rx_stride + n];
-  out[((size_t)b * num_rx + rx) * L + n] = mkc(v.x + sigma * z.x, v.y + sigma * z.y);
-}
 }  // namespace lte
-
-struct lte_plan {
-  lte_plan_desc d;
-  int L, n_sym, Nd, Np, n_grp, nblk, PW, C = 0, KWmax = 0, EW = 0, enc_words = 0;
-  int coded_len = 0, n_re_bits = 0;
-  int log2N;
-  GridHost gh;
-  TableSet tabs;
-  Grid grid;
-  hipStream_t stream = nullptr;
-  int f64 = 0;                       // signal chain + decoder in float64 (every chain but beamforming)
-  int n_layers = 1;                  // rx_map layers (> 1: rate-matching repetition, E > N_cb)
-  std::vector<CbInfo> cbs;
-  // device
-  DBuf<CbInfo> cbi;
-  DBuf<int32_t> tx_map, rx_map, delays;
-  DBuf<int32_t> txf_map, txf_re;   // k_ofdm_txf's bank-aware lane order (empty: RE order)
-  double txf_model[2] = {0, 0};     // modelled extra LDS cycles per 32-lane gather: RE order, lane order
-  DBuf<uint32_t> pw, enc, inj_bits;
-  DBuf<uint8_t> inj_bytes;   // the caller's payload bits as given (packed on the device)
-  DBuf<uint16_t> enc_qmask;   // encoder 2's per-bit segment-state contributions (encode_qmask)
-  int qstride = 0;
-  ChainBufs<float> c32;              // f32 plans (and the beamforming chain)
-  ChainBufs<double> c64;             // f64 plans
-  DBuf<uint32_t> frame_err, frame_crc;
-  DBuf<int32_t> snr_idx;
-  DBuf<double> nvar;                 // spatial detectors' noise variance 10 ** (-snr_db / 10), float64
-  DBuf<uint64_t> fid;
-  DBuf<unsigned long long> counts;
-  DBuf<uint8_t> cap_bits;
-  std::vector<DBuf<uint32_t>> decb;
-  DBuf<int64_t> rows_dev;
-  DBuf<uint32_t*> dec_ptrs;
-  DBuf<int> kw_dev;
-  // CRC early termination (lte_plan_set_early_stop): per CB slot the iterations
-  // used [G][64] words; es_frames: frames of the last decoded run (0: none yet)
-  bool early_stop = false;
-  std::vector<DBuf<uint32_t>> es_used;
-  int es_frames = 0;
-  // HARQ (lte_plan_create_harq).  tx_map / rx_map hold one map per distinct rv
-  // of rv_seq back to back (n_re_bits entries each, hq_slot[rv] its index).
-  // hq_round: the next lte_run's transmission; hq_done: last completed round
-  // (-1: none in this process); hq_fids: round 0's frame ids.  Per frame
-  // [max_frames]: tx_used, latched errors / verdict (a passing verdict is the
-  // acknowledgement); hq_skip [G]: 1 = every frame of the group is acknowledged
-  // (k_harq_latch)
-  bool harq = false;
-  lte_harq_desc hq{};
-  int hq_slot[4] = {0, 0, 0, 0};
-  int hq_round = 0, hq_done = -1;
-  int hq_last[3] = {-1, 0, 0};       // last run: round, rv, decoder groups skipped
-  std::vector<uint64_t> hq_fids;
-  DBuf<uint32_t> hq_tx_used, hq_err, hq_crc, hq_skip;
-  std::vector<uint32_t> hq_skip_h;   // hq_skip after the last round
-  DBuf<int32_t> hq_zmap;             // decoder input rows (r << 24 | row) rv_seq[0]'s map leaves unwritten
-  int hq_nz = 0;
-  // multi-antenna chains (lte_mimo.hip)
-  bool mimo = false;
-  // beamforming chain (lte_bf.hip)
-  bool bf = false;
-  int bf_ncb = 0;
-  DBuf<double> bf_cb;
-  DBuf<BfFrameT<float>> bf_fr;
-  DBuf<BfFrameT<double>> bf_fr64;
-  int res = 0;                       // QAM symbols per OFDM symbol (= Nd for SISO / SIMO)
-  MimoGrid mg{};
-  DBuf<int32_t> m_np, m_ppos, m_pseg;
-  DBuf<float2> m_pval;
-  DBuf<double2> m_pval64;
-  DBuf<float> m_pig;
-  DBuf<double> m_pig64, m_W;
-  // timing
-  bool timing = false;
-  double kms[KN_COUNT] = {0};
-  int64_t klaunch[KN_COUNT] = {0};
-  std::vector<hipEvent_t> evpool;
-  std::vector<std::pair<int, int>> evuse;  // (kernel id, first event index)
-};
 
 namespace {
 
@@ -591,390 +408,7 @@ int lte_device_init(int device) {
   return LTE_OK;
 }
 
-int lte_pilots(int cell_id, int n, double* out) {
-  if (n < 0 || !out) return fail(LTE_EINVAL, "bad pilot request");
-  std::vector<double> v;
-  make_pilots(cell_id, n, v);
-  std::memcpy(out, v.data(), v.size() * sizeof(double));
-  return LTE_OK;
-}
-
-int lte_philox_host(uint64_t seed, int n_frames, const uint64_t* frame_ids, uint32_t stream, int64_t n_ctr,
-                    uint32_t* out_u32, double* out_gauss64, float* out_gauss32) {
-  if (n_frames < 0 || n_ctr < 0 || n_ctr > 0xFFFFFFFFll || (n_frames && !frame_ids))
-    return fail(LTE_EINVAL, "bad philox arguments");
-  const int64_t n = (int64_t)n_frames * n_ctr;
-  if (n == 0) return LTE_OK;
-  DBuf<uint64_t> dfid;
-  DBuf<uint32_t> du;
-  DBuf<double> d64;
-  DBuf<float> d32;
-  auto rel = [&] { dfid.release(); du.release(); d64.release(); d32.release(); };
-  if (dfid.alloc(n_frames) || (out_u32 && du.alloc(4 * n)) || (out_gauss64 && d64.alloc(4 * n)) ||
-      (out_gauss32 && d32.alloc(4 * n))) {
-    rel();
-    return fail(LTE_ENOMEM, "philox buffers");
-  }
-  int rc = LTE_OK;
-  if (hipMemcpy(dfid.p, frame_ids, n_frames * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      launch_philox_draws(nullptr, seed, dfid.p, n_frames, stream, n_ctr, du.p, d64.p, d32.p) ||
-      hipDeviceSynchronize() != hipSuccess ||
-      (out_u32 && hipMemcpy(out_u32, du.p, 16 * n, hipMemcpyDeviceToHost) != hipSuccess) ||
-      (out_gauss64 && hipMemcpy(out_gauss64, d64.p, 32 * n, hipMemcpyDeviceToHost) != hipSuccess) ||
-      (out_gauss32 && hipMemcpy(out_gauss32, d32.p, 16 * n, hipMemcpyDeviceToHost) != hipSuccess))
-    rc = fail(LTE_EHIP, "philox failed");
-  rel();
-  return rc;
-}
-
-}  // extern "C"
-
-// OFDMChannel.transmit on an arbitrary stream in precision R (lte_channel_host / _host64).
-template <class R>
-static int channel_host(int64_t L, int num_rx, int channel, int n_paths, const int32_t* delays, const double* gains,
-                        double fD, double fs, double snr_db, uint64_t seed, const R* x, const double* phases,
-                        const double* noise, R* y, R* noise_power) {
-  using V = cx<R>;
-  if (L < 1 || L > (1LL << 30) || num_rx < 1 || !x || !y) return fail(LTE_EINVAL, "bad channel arguments");
-  const bool ray = channel == LTE_CH_RAYLEIGH;
-  if (!ray && channel != LTE_CH_AWGN) return fail(LTE_EINVAL, "Tipo de canal desconocido");
-  if (ray && (n_paths < 1 || n_paths > LTE_MAX_PATHS || !delays || !gains)) return fail(LTE_EINVAL, "bad paths");
-  Grid g{};
-  g.L = (int)L;
-  const int nblk = channel_nblk((int)L);
-  DBuf<V> dx, dy, dcoef, dout;
-  DBuf<R> dph, dpp, dsl, dnp, dz, dgain, dinj;
-  DBuf<int32_t> ddel;
-  DBuf<uint64_t> dfid;
-  int rc = LTE_OK;
-  auto cleanup = [&]() {
-    dx.release(); dy.release(); dcoef.release(); dout.release(); dph.release(); dpp.release(); dsl.release();
-    dnp.release(); dz.release(); dgain.release(); dinj.release(); ddel.release(); dfid.release();
-  };
-  if (dx.alloc(L) || dout.alloc((size_t)num_rx * L) || dpp.alloc((size_t)num_rx * nblk) || dsl.alloc(1) ||
-      dnp.alloc(num_rx) || dfid.alloc(1) || (ray && (dy.alloc((size_t)num_rx * L) ||
-      dcoef.alloc((size_t)num_rx * n_paths) || dph.alloc((size_t)num_rx * n_paths * 16)))) {
-    cleanup();
-    return fail(LTE_ENOMEM, "channel buffers");
-  }
-  const R sl = (R)std::pow(10.0, snr_db / 10.0);
-  const uint64_t fid0 = 0;
-  bool ok = hipMemcpy(dx.p, x, L * sizeof(V), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(dsl.p, &sl, sizeof(R), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(dfid.p, &fid0, 8, hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && ray) {
-    std::vector<int32_t> dl(delays, delays + n_paths);
-    std::vector<R> hg(gains, gains + n_paths);
-    ok = upload(ddel, dl) == 0 && upload(dgain, hg) == 0;
-    if (ok && phases) {
-      std::vector<R> hp(phases, phases + (size_t)num_rx * n_paths * 16);
-      ok = upload(dinj, hp) == 0;
-    }
-    ok = ok && launch_fading<R>(nullptr, 1, num_rx, n_paths, dgain.p, dfid.p, seed, phases ? dinj.p : nullptr, 0,
-                                dph.p, dcoef.p) == 0;
-  }
-  if (ok && noise) {
-    std::vector<R> hz(noise, noise + (size_t)num_rx * 2 * L);
-    ok = upload(dz, hz) == 0;
-  }
-  ok = ok && launch_channel<R>(nullptr, g, 1, num_rx, ray ? 1 : 0, n_paths, ddel.p, dgain.p, (R)fD, (R)fs, dph.p,
-                               dcoef.p, dx.p, dy.p, dpp.p, nblk, ray ? *std::max_element(delays, delays + n_paths) : 0) == 0;
-  ok = ok && launch_npow<R>(nullptr, 1, num_rx, dpp.p, nblk, (int)L, dsl.p, dnp.p) == 0;
-  if (ok) {
-    const V* ys = ray ? dy.p : dx.p;
-    hipLaunchKernelGGL(k_cap_rx<R>, dim3((unsigned)((L + 255) / 256), num_rx), dim3(256), 0, nullptr, (int)L, num_rx,
-                       1, ys, ray ? L : 0, ray ? (int64_t)num_rx * L : L, dnp.p, dfid.p, seed,
-                       noise ? dz.p : nullptr, 0, dout.p);
-    ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-         hipMemcpy(y, dout.p, (size_t)num_rx * L * sizeof(V), hipMemcpyDeviceToHost) == hipSuccess &&
-         (!noise_power || hipMemcpy(noise_power, dnp.p, num_rx * sizeof(R), hipMemcpyDeviceToHost) == hipSuccess);
-  }
-  if (!ok) rc = fail(LTE_EHIP, std::string("channel failed: ") + hipGetErrorString(hipGetLastError()));
-  cleanup();
-  return rc;
-}
-
-extern "C" {
-
-int lte_channel_host(int64_t L, int num_rx, int channel, int n_paths, const int32_t* delays, const double* gains,
-                     double fD, double fs, double snr_db, uint64_t seed, const float* x, const double* phases,
-                     const double* noise, float* y, float* noise_power) {
-  return channel_host<float>(L, num_rx, channel, n_paths, delays, gains, fD, fs, snr_db, seed, x, phases, noise, y,
-                             noise_power);
-}
-
-int lte_channel_host64(int64_t L, int num_rx, int channel, int n_paths, const int32_t* delays, const double* gains,
-                       double fD, double fs, double snr_db, uint64_t seed, const double* x, const double* phases,
-                       const double* noise, double* y, double* noise_power) {
-  return channel_host<double>(L, num_rx, channel, n_paths, delays, gains, fD, fs, snr_db, seed, x, phases, noise, y,
-                              noise_power);
-}
-
-}  // extern "C"
-
-// Multi-antenna channel on arbitrary streams in precision R (lte_channel_mimo_host / _host64).
-template <class R>
-static int channel_mimo_host(int64_t L, int num_tx, int num_rx, int mode, int channel, int n_paths,
-                             const int32_t* delays, const double* gains, double fD, double fs, double snr_db,
-                             uint64_t seed, const R* x, const double* phases, const double* link_noise,
-                             const double* link_h, const double* noise, R* y, R* link_stats, R* noise_power) {
-  using V = cx<R>;
-  if (L < 1 || L > (1LL << 28) || num_tx < 1 || num_tx > 8 || num_rx < 1 || num_rx > 16 || !x || !y)
-    return fail(LTE_EINVAL, "bad channel arguments");
-  if (mode != 0 && mode != 1) return fail(LTE_EINVAL, "mode must be 0 (transmit_mimo) or 1 (spatial)");
-  const bool ray = channel == LTE_CH_RAYLEIGH;
-  if (!ray && channel != LTE_CH_AWGN) return fail(LTE_EINVAL, "Tipo de canal desconocido");
-  if (ray && (n_paths < 1 || n_paths > LTE_MAX_PATHS || !delays || !gains)) return fail(LTE_EINVAL, "bad paths");
-  // an arbitrary stream is cut into 1024-sample chunks for the fD != 0
-  // expansion (f32: second order; f64: degree 5, or the per-sample sum past
-  // mimo_taylor_ok)
-  const int chunk = 1024;
-  Grid g{};
-  g.N = chunk;
-  g.cp = 0;
-  g.L = (int)L;
-  MimoGrid m{};
-  m.mode = mode == 0 ? MIMO_SFBC : MIMO_SPATIAL;
-  m.num_tx = num_tx;
-  m.num_rx = num_rx;
-  m.exact_jakes = ray && fD != 0.0 && !mimo_taylor_ok_prec(sizeof(R) == 8, fD, fs, chunk);
-  for (int k = 0; k < 16; ++k) m.jw[k] = 6.283185307179586 * fD * std::cos(6.283185307179586 * (k + 1) / 16.0);
-  m.n_cs = (ray && fD != 0.0 && !m.exact_jakes) ? (int)((L + chunk - 1) / chunk) : 1;
-  const int np = ray ? n_paths : 1;
-  // partial-sum slots: 256-sample blocks (link stats) or OFDM-symbol blocks (channel), whichever is more
-  const int nblk = std::max((int)((L + 255) / 256), mimo_channel_nblk(g.L, g.N + g.cp));
-  const size_t links = (size_t)num_rx * num_tx;
-  const bool link_noise_on = mode == 0 && ray;
-  DBuf<V> dx, dy, dcoef, dout;
-  DBuf<R> dgain, dph, dlz, dlh, dz, dpp, dlp, dls, dsl, dnp, dstp, dst, dphs;
-  DBuf<int32_t> ddel;
-  DBuf<uint64_t> dfid;
-  auto cleanup = [&]() {
-    dx.release(); dy.release(); dcoef.release(); dout.release(); dgain.release(); dph.release(); dlz.release();
-    dlh.release(); dz.release(); dpp.release(); dlp.release(); dls.release(); dsl.release(); dnp.release();
-    dstp.release(); dst.release(); dphs.release(); ddel.release(); dfid.release();
-  };
-  if (dx.alloc((size_t)num_tx * L) || dy.alloc((size_t)num_rx * L) || dout.alloc((size_t)num_rx * L) ||
-      dcoef.alloc(links * np * m.n_cs * mimo_ncf<R>()) || dpp.alloc((size_t)num_rx * nblk) || dsl.alloc(1) ||
-      dnp.alloc(num_rx) || dfid.alloc(1) || (m.exact_jakes && dphs.alloc(links * np * 16)) ||
-      (link_noise_on && (dlp.alloc(links * nblk) || dls.alloc(links)))) {
-    cleanup();
-    return fail(LTE_ENOMEM, "channel buffers");
-  }
-  auto up = [&](DBuf<R>& d, const double* src, size_t n) {
-    std::vector<R> h(src, src + n);
-    return upload(d, h) == 0;
-  };
-  const R sl = (R)std::pow(10.0, snr_db / 10.0);
-  const uint64_t fid0 = 0;
-  bool ok = hipMemcpy(dx.p, x, (size_t)num_tx * L * sizeof(V), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(dsl.p, &sl, sizeof(R), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(dfid.p, &fid0, 8, hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && ray) {
-    std::vector<int32_t> dl(delays, delays + n_paths);
-    ok = upload(ddel, dl) == 0 && up(dgain, gains, n_paths);
-  }
-  if (ok && ray && phases) ok = up(dph, phases, links * n_paths * 16);
-  if (ok && link_noise_on && link_noise) ok = up(dlz, link_noise, links * 2 * L);
-  if (ok && !ray && mode == 1 && link_h) ok = up(dlh, link_h, links * 2);
-  if (ok && noise) ok = up(dz, noise, (size_t)num_rx * 2 * L);
-  ok = ok && launch_fading_mimo<R>(nullptr, g, m, 1, ray ? 1 : 0, n_paths, dgain.p, fD, fs, dfid.p, seed,
-                                   (ray && phases) ? dph.p : nullptr, 0,
-                                   (!ray && mode == 1 && link_h) ? dlh.p : nullptr, 0, dcoef.p, dphs.p) == 0;
-  const R* lz = (link_noise_on && link_noise) ? dlz.p : nullptr;
-  ok = ok && launch_channel_mimo<R>(nullptr, g, m, 1, np, ray ? ddel.p : nullptr, dcoef.p, dphs.p, dgain.p, fs, dx.p,
-                                    dy.p, link_noise_on ? 1 : 0, dfid.p, seed, lz, 0, dlp.p, dls.p, dpp.p, nblk,
-                                    channel_mimo_select<R>(m, np, g.N + g.cp, fs, read_knobs()), 0) == 0;
-  ok = ok && launch_npow_mimo<R>(nullptr, 1, num_rx, dpp.p, mimo_channel_nblk(g.L, g.N + g.cp), (int)L, dsl.p,
-                                 mode == 0 ? (double)num_tx : 1.0, dnp.p) == 0;
-  if (ok) {
-    hipLaunchKernelGGL(k_cap_rx<R>, dim3((unsigned)((L + 255) / 256), num_rx), dim3(256), 0, nullptr, (int)L, num_rx, 1,
-                       dy.p, (int64_t)L, (int64_t)num_rx * L, dnp.p, dfid.p, seed, noise ? dz.p : nullptr, 0,
-                       dout.p);
-    ok = hipGetLastError() == hipSuccess;
-  }
-  if (ok && link_stats) {
-    ok = dstp.alloc(links * 4 * nblk) == 0 && dst.alloc(links * 4) == 0 &&
-         launch_link_stats<R>(nullptr, g, m, 1, np, ray ? ddel.p : nullptr, dcoef.p, dphs.p, dgain.p, fs, dx.p,
-                              link_noise_on ? dls.p : nullptr, dfid.p, seed, lz, 0, dstp.p, nblk, dst.p) == 0;
-  }
-  ok = ok && hipDeviceSynchronize() == hipSuccess &&
-       hipMemcpy(y, dout.p, (size_t)num_rx * L * sizeof(V), hipMemcpyDeviceToHost) == hipSuccess &&
-       (!noise_power || hipMemcpy(noise_power, dnp.p, num_rx * sizeof(R), hipMemcpyDeviceToHost) == hipSuccess) &&
-       (!link_stats || hipMemcpy(link_stats, dst.p, links * 4 * sizeof(R), hipMemcpyDeviceToHost) == hipSuccess);
-  int rc = LTE_OK;
-  if (!ok) rc = fail(LTE_EHIP, std::string("mimo channel failed: ") + hipGetErrorString(hipGetLastError()));
-  cleanup();
-  return rc;
-}
-
-extern "C" {
-
-int lte_channel_mimo_host(int64_t L, int num_tx, int num_rx, int mode, int channel, int n_paths,
-                          const int32_t* delays, const double* gains, double fD, double fs, double snr_db,
-                          uint64_t seed, const float* x, const double* phases, const double* link_noise,
-                          const double* link_h, const double* noise, float* y, float* link_stats,
-                          float* noise_power) {
-  return channel_mimo_host<float>(L, num_tx, num_rx, mode, channel, n_paths, delays, gains, fD, fs, snr_db, seed, x,
-                                  phases, link_noise, link_h, noise, y, link_stats, noise_power);
-}
-
-int lte_channel_mimo_host64(int64_t L, int num_tx, int num_rx, int mode, int channel, int n_paths,
-                            const int32_t* delays, const double* gains, double fD, double fs, double snr_db,
-                            uint64_t seed, const double* x, const double* phases, const double* link_noise,
-                            const double* link_h, const double* noise, double* y, double* link_stats,
-                            double* noise_power) {
-  return channel_mimo_host<double>(L, num_tx, num_rx, mode, channel, n_paths, delays, gains, fD, fs, snr_db, seed, x,
-                                   phases, link_noise, link_h, noise, y, link_stats, noise_power);
-}
-
-int lte_mimo_detect_host(int detector, int num_rx, int num_tx, int rank, int bps, int64_t n_sc, const double* y,
-                         const double* H, const double* W, double sigma2, double* out) {
-  if (num_rx < rank) return fail(LTE_EINVAL, "num_rx (" + std::to_string(num_rx) + ") debe ser >= num_layers (" +
-                                                 std::to_string(rank) + ")");
-  if (detector < LTE_DET_MMSE || detector > LTE_DET_MRC) return fail(LTE_EINVAL, "Detector no soportado");
-  if (detector == LTE_DET_MRC && rank != 1) return fail(LTE_EINVAL, "MRC solo soporta num_layers=1 (rank-1)");
-  if (num_rx < 1 || num_rx > 4 || num_tx < 1 || num_tx > 4 || rank < 1 || rank > num_tx)
-    return fail(LTE_EUNSUP, "GPU detector: num_rx, num_tx <= 4, 1 <= rank <= num_tx");
-  if (bps != 0 && bps != 2 && bps != 4 && bps != 6) return fail(LTE_EINVAL, "Unsupported modulation");
-  if (n_sc < 1 || n_sc > (1LL << 26) || !y || !H || !W || !out) return fail(LTE_EINVAL, "bad detector arguments");
-  std::vector<double> w4(32, 0.0);
-  for (int t = 0; t < num_tx; ++t)
-    for (int c = 0; c < rank; ++c) {
-      w4[(t * 4 + c) * 2] = W[(t * rank + c) * 2];
-      w4[(t * 4 + c) * 2 + 1] = W[(t * rank + c) * 2 + 1];
-    }
-  DBuf<double> dy, dH, dW, dout;
-  const size_t ny = (size_t)num_rx * n_sc * 2, nh = (size_t)num_rx * num_tx * n_sc * 2, no = (size_t)rank * n_sc * 2;
-  bool ok = dy.alloc(ny) == 0 && dH.alloc(nh) == 0 && dout.alloc(no) == 0 && upload(dW, w4) == 0 &&
-            hipMemcpy(dy.p, y, ny * 8, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(dH.p, H, nh * 8, hipMemcpyHostToDevice) == hipSuccess;
-  ok = ok && launch_det_stage(nullptr, detector, num_rx, num_tx, rank, bps, n_sc, dy.p, dH.p, dW.p, sigma2, dout.p) == 0;
-  ok = ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(out, dout.p, no * 8, hipMemcpyDeviceToHost) == hipSuccess;
-  int rc = LTE_OK;
-  if (!ok) rc = fail(LTE_EHIP, std::string("mimo detect failed: ") + hipGetErrorString(hipGetLastError()));
-  dy.release(); dH.release(); dW.release(); dout.release();
-  return rc;
-}
-
-// SFBCAlamouti.encode / .decode on host arrays (core/sfbc_alamouti.py:45-163).
-static int sfbc_stage(int decode, int64_t n, const double* a, const double* h0, const double* h1, double reg,
-                      double* o0, double* o1) {
-  if (n % 2 != 0)
-    return fail(LTE_EINVAL, decode ? "Number of RX symbols must be even, got " + std::to_string(n)
-                                   : "Number of symbols must be even for Alamouti coding, got " + std::to_string(n));
-  if (n < 0 || n > (1LL << 28) || !a || !o0 || (decode ? (!h0 || !h1) : !o1))
-    return fail(LTE_EINVAL, "bad SFBC arguments");
-  if (n == 0) return LTE_OK;
-  const size_t nr = (size_t)n * 2;
-  DBuf<double> da, dh0, dh1, d0, d1;
-  bool ok = da.alloc(nr) == 0 && d0.alloc(nr) == 0 && (decode ? dh0.alloc(nr) == 0 && dh1.alloc(nr) == 0
-                                                                : d1.alloc(nr) == 0) &&
-            hipMemcpy(da.p, a, nr * 8, hipMemcpyHostToDevice) == hipSuccess;
-  if (ok && decode)
-    ok = hipMemcpy(dh0.p, h0, nr * 8, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(dh1.p, h1, nr * 8, hipMemcpyHostToDevice) == hipSuccess;
-  ok = ok && launch_sfbc_stage(nullptr, decode, n, da.p, dh0.p, dh1.p, reg, d0.p, d1.p) == 0;
-  ok = ok && hipDeviceSynchronize() == hipSuccess && hipMemcpy(o0, d0.p, nr * 8, hipMemcpyDeviceToHost) == hipSuccess;
-  if (ok && !decode) ok = hipMemcpy(o1, d1.p, nr * 8, hipMemcpyDeviceToHost) == hipSuccess;
-  int rc = LTE_OK;
-  if (!ok) rc = fail(LTE_EHIP, std::string("SFBC stage failed: ") + hipGetErrorString(hipGetLastError()));
-  da.release(); dh0.release(); dh1.release(); d0.release(); d1.release();
-  return rc;
-}
-
-int lte_sfbc_encode_host64(int64_t n, const double* syms, double* tx0, double* tx1) {
-  return sfbc_stage(0, n, syms, nullptr, nullptr, 0.0, tx0, tx1);
-}
-
-int lte_sfbc_decode_host64(int64_t n, const double* rx, const double* H0, const double* H1, double regularization,
-                           double* out) {
-  return sfbc_stage(1, n, rx, H0, H1, regularization, out, nullptr);
-}
-
-// Output position j of [3K+12] (turbo_encode order) fed by rate-matched index
-// i (E <= N_cb) -- rate_dematching_turbo's de-collection + sub-block
-// de-interleave + re-interleave (rate_matching.py:428-489) as one map.
-static int dematch_first_map(int K, int E, int rv_idx, int32_t* src, bool* repeats) {
-  int f1, f2;
-  if (!qpp_lookup(K, &f1, &f2)) return fail(LTE_EINVAL, "Invalid interleaver size K=" + std::to_string(K));
-  if (E <= 0 || !src) return fail(LTE_EINVAL, "bad E");
-  const int Ncb = 3 * (K + 6);
-  std::vector<RmSrc> rs;
-  rm_source(K, rv_idx, std::min(E, Ncb), rs);
-  const int n = 3 * K + 12;
-  for (int j = 0; j < n; ++j) src[j] = -1;
-  for (int i = 0; i < (int)rs.size(); ++i) {
-    const RmSrc s = rs[i];
-    if (s.stream < 0) continue;
-    int j;
-    if (s.stream == 0) {
-      if (s.idx < K) j = 3 * s.idx;
-      else if (s.idx < K + 3) j = 3 * K + (s.idx - K);
-      else j = 3 * K + 6 + (s.idx - K - 3);
-    } else if (s.stream == 1) {
-      j = s.idx < K ? 3 * s.idx + 1 : 3 * K + 3 + (s.idx - K);
-    } else {
-      j = s.idx < K ? 3 * s.idx + 2 : 3 * K + 9 + (s.idx - K);
-    }
-    src[j] = i;
-  }
-  if (repeats) *repeats = E > Ncb;
-  return LTE_OK;
-}
-
-int lte_rate_dematch_map(int K, int E, int rv_idx, int32_t* src) {
-  bool rep = false;
-  const int rc = dematch_first_map(K, E, rv_idx, src, &rep);
-  if (rc != LTE_OK) return rc;
-  if (rep) return fail(LTE_EUNSUP, "E > N_cb repeats LLRs: use lte_rate_dematch_host64 (sums the repeats)");
-  return LTE_OK;
-}
-
-int lte_rate_dematch_host64(int K, int E, int rv_idx, int64_t ncb, const double* llr, double* out) {
-  if (E == 0) {   // nothing received: every position punctured, zeros(3K + 12) like the reference
-    if (K < 0 || ncb < 0 || (ncb > 0 && !out)) return fail(LTE_EINVAL, "bad arguments");
-    std::fill(out, out + (size_t)ncb * (3 * (size_t)K + 12), 0.0);
-    return LTE_OK;
-  }
-  if (ncb < 0 || (ncb > 0 && (!llr || !out))) return fail(LTE_EINVAL, "bad arguments");
-  std::vector<int32_t> src(3 * (size_t)K + 12);
-  const int rc = dematch_first_map(K, E, rv_idx, src.data(), nullptr);
-  if (rc != LTE_OK || ncb == 0) return rc;
-  const int n = 3 * K + 12;
-  DBuf<double> dl, dout;
-  DBuf<int32_t> dsrc;
-  if (dl.alloc((size_t)ncb * E) || dout.alloc((size_t)ncb * n) || upload(dsrc, src))
-    return fail(LTE_ENOMEM, "dematch buffers");
-  int r = LTE_OK;
-  if (hipMemcpy(dl.p, llr, (size_t)ncb * E * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      launch_rate_dematch(nullptr, dl.p, E, 3 * (K + 6), n, dsrc.p, ncb, dout.p) ||
-      hipDeviceSynchronize() != hipSuccess ||
-      hipMemcpy(out, dout.p, (size_t)ncb * n * 8, hipMemcpyDeviceToHost) != hipSuccess)
-    r = fail(LTE_EHIP, std::string("rate dematch failed: ") + hipGetErrorString(hipGetLastError()));
-  dl.release(); dout.release(); dsrc.release();
-  return r;
-}
-
-int lte_qpp_perm(int K, int32_t* perm) {
-  int f1, f2;
-  if (!qpp_lookup(K, &f1, &f2)) return fail(LTE_EINVAL, "Invalid interleaver size K=" + std::to_string(K));
-  if (!perm) return fail(LTE_EINVAL, "null perm");
-  for (int64_t i = 0; i < K; ++i) perm[i] = (int32_t)((f1 * i + f2 * i * i) % K);   // turbo_encoder.py:76-103
-  return LTE_OK;
-}
-
-int lte_subblock_perm(int n, int32_t* perm) {
-  if (n < 0 || (n > 0 && !perm)) return fail(LTE_EINVAL, "bad arguments");
-  const std::vector<int> p = subblock_perm(n);   // rate_matching.py:25-94, <NULL>s removed
-  std::copy(p.begin(), p.end(), perm);
-  return LTE_OK;
-}
-
-int lte_set_decoder_mode(int use_max_log_map) {
-  set_logmap(use_max_log_map ? 0 : 1);
-  return LTE_OK;
-}
+int64_t lte_device_bytes_held(void) { return g_dev_bytes.load(); }
 
 static int plan_tables(lte_plan* p) {
   const lte_plan_desc& d = p->d;
@@ -1511,7 +945,9 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
   if (d.precision != LTE_PREC_DEFAULT && d.precision != LTE_PREC_F32 && d.precision != LTE_PREC_F64)
     return fail(LTE_EINVAL, "precision must be LTE_PREC_DEFAULT, LTE_PREC_F32 or LTE_PREC_F64");
   // float64 (the reference's arithmetic) is the default of every chain
-  lte_plan* p = new lte_plan();
+  // (a refused plan is destroyed like any other: whatever it holds by then goes with it)
+  std::unique_ptr<lte_plan, int (*)(lte_plan*)> own(new lte_plan(), lte_plan_destroy);
+  lte_plan* const p = own.get();
   p->d = d;
   p->d.num_tx = num_tx;
   p->mimo = mimo;
@@ -1521,22 +957,22 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
     p->hq = *harq;
   }
   const bool coded = chain_is_coded(d.chain);
-  if (coded && d.turbo_iters < 0) { delete p; return fail(LTE_EINVAL, "bad turbo_iters"); }
+  if (coded && d.turbo_iters < 0) return fail(LTE_EINVAL, "bad turbo_iters");
   int rc = plan_tables(p);
-  if (rc) { delete p; return rc; }
+  if (rc) return rc;
   // Nd < N/2 is assumed by k_rx_data (4 data REs per thread)
-  if (p->Nd * 2 >= d.N) { delete p; return fail(LTE_EUNSUP, "Nd >= N/2 not supported"); }
+  if (p->Nd * 2 >= d.N) return fail(LTE_EUNSUP, "Nd >= N/2 not supported");
   const bool sfbc = d.chain == LTE_CHAIN_SFBC || d.chain == LTE_CHAIN_SFBC_CODED;
   // REs per OFDM symbol: SFBC drops an odd last data SC (core/sfbc_alamouti.py:196-200, Q18)
   p->res = sfbc ? (p->Nd & ~1) : p->Nd;
   if (coded) {
     rc = plan_coded_maps(p, read_knobs());
-    if (rc) { p->tabs.release(); delete p; return rc; }
+    if (rc) return rc;
     p->PW = (d.n_bits + 24 + 31) / 32 + 1;
   } else {
-    if (d.n_sym < 1) { delete p; return fail(LTE_EINVAL, "n_sym must be >= 1"); }
+    if (d.n_sym < 1) return fail(LTE_EINVAL, "n_sym must be >= 1");
     p->n_sym = d.n_sym;
-    if ((int64_t)d.n_bits > (int64_t)p->n_sym * p->res * d.bps) { delete p; return fail(LTE_EINVAL, "n_bits exceeds frame capacity"); }
+    if ((int64_t)d.n_bits > (int64_t)p->n_sym * p->res * d.bps) return fail(LTE_EINVAL, "n_bits exceeds frame capacity");
     p->PW = (p->n_sym * p->res * d.bps + 31) / 32 + 1;
   }
   p->L = bf ? p->n_sym * p->Nd : p->n_sym * (d.N + d.cp_len);   // beamforming: REs per antenna
@@ -1562,7 +998,7 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
         }
     }
     p->bf_ncb = (int)(cb.size() / (2 * num_tx));
-    if (upload(p->bf_cb, cb)) { p->tabs.release(); delete p; return fail(LTE_ENOMEM, "codebook upload"); }
+    if (upload(p->bf_cb, cb)) return fail(LTE_ENOMEM, "codebook upload");
   }
   if (mimo) {
     MimoGrid& m = p->mg;
@@ -1582,8 +1018,8 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
     for (int k = 0; k < 16; ++k) m.jw[k] = 6.283185307179586 * d.fD * std::cos(6.283185307179586 * (k + 1) / 16.0);
     m.n_cs = (d.channel == LTE_CH_RAYLEIGH && d.fD != 0.0 && !m.exact_jakes) ? p->n_sym : 1;
     rc = plan_mimo_tables(p);
-    if (rc) { p->tabs.release(); delete p; return rc; }
-    if (!sfbc) {   // precoder W [num_tx][rank] in a [4][4] table; rank 0 in the descriptor -> identity
+    if (rc) return rc;
+    if (!sfbc) {  // precoder W [num_tx][rank] in a [4][4] table; rank 0 in the descriptor -> identity
       std::vector<double> w4(32, 0.0);
       for (int t = 0; t < num_tx; ++t)
         for (int c = 0; c < rank; ++c) {
@@ -1594,7 +1030,7 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
             w4[(t * 4 + c) * 2] = t == c ? 1.0 : 0.0;
           }
         }
-      if (upload(p->m_W, w4)) { p->tabs.release(); delete p; return fail(LTE_ENOMEM, "precoder upload"); }
+      if (upload(p->m_W, w4)) return fail(LTE_ENOMEM, "precoder upload");
       m.W = p->m_W.p;
     }
   }
@@ -1608,25 +1044,23 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
   if (d.channel == LTE_CH_RAYLEIGH) {
     std::vector<int32_t> dl(d.delays, d.delays + d.n_paths);
     for (int i = 0; i < d.n_paths; ++i)
-      if (dl[i] < 0) { p->tabs.release(); delete p; return fail(LTE_EINVAL, "negative delay"); }
-    if (upload(p->delays, dl)) { p->tabs.release(); delete p; return fail(LTE_ENOMEM, "upload"); }
+      if (dl[i] < 0) return fail(LTE_EINVAL, "negative delay");
+    if (upload(p->delays, dl)) return fail(LTE_ENOMEM, "upload");
   }
   if (hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking) != hipSuccess) {
-    delete p;
+    p->stream = nullptr;   // nothing for lte_plan_destroy to wait on
     return fail(LTE_EHIP, "stream creation failed");
   }
   rc = plan_alloc(p);
-  if (rc) { lte_plan_destroy(p); return rc; }
-  if (p->counts.alloc(4 * 64)) { lte_plan_destroy(p); return fail(LTE_ENOMEM, "counts"); }
+  if (rc) return rc;
+  if (p->counts.alloc(4 * 64)) return fail(LTE_ENOMEM, "counts");
   if (p->harq) {
     const size_t B = (size_t)d.max_frames;
     if (p->hq_tx_used.alloc(B) || p->hq_err.alloc(B) || p->hq_crc.alloc(B) ||
-        p->hq_skip.alloc((B + 63) / 64) || hipMemset(p->hq_tx_used.p, 0, B * sizeof(uint32_t)) != hipSuccess) {
-      lte_plan_destroy(p);
+        p->hq_skip.alloc((B + 63) / 64) || hipMemset(p->hq_tx_used.p, 0, B * sizeof(uint32_t)) != hipSuccess)
       return fail(LTE_ENOMEM, "HARQ state");
-    }
   }
-  *out = p;
+  *out = own.release();
   return LTE_OK;
 }
 
@@ -1653,26 +1087,11 @@ int lte_harq_code_block_bits(int32_t n_bits, int32_t bps, int64_t G, int32_t* K,
 
 int lte_plan_destroy(lte_plan* p) {
   if (!p) return LTE_OK;
+  // the stream drains first: no buffer is freed under work that may be pending on it
   if (p->stream) (void)hipStreamSynchronize(p->stream);
-  p->tabs.release();
-  p->cbi.release(); p->tx_map.release(); p->rx_map.release(); p->delays.release();
-  p->txf_map.release(); p->txf_re.release();
-  p->pw.release(); p->enc.release(); p->inj_bits.release(); p->inj_bytes.release(); p->enc_qmask.release();
-  p->c32.release(); p->c64.release();
-  p->frame_err.release(); p->frame_crc.release(); p->snr_idx.release(); p->nvar.release(); p->fid.release(); p->counts.release();
-  p->cap_bits.release();
-  for (auto& b : p->decb) b.release();
-  for (auto& b : p->es_used) b.release();
-  p->hq_zmap.release();
-  p->hq_tx_used.release(); p->hq_err.release(); p->hq_crc.release(); p->hq_skip.release();
-  p->rows_dev.release(); p->dec_ptrs.release(); p->kw_dev.release();
-  p->m_np.release(); p->m_ppos.release(); p->m_pseg.release(); p->m_pval.release(); p->m_pval64.release();
-  p->m_pig.release(); p->m_pig64.release(); p->m_W.release(); p->bf_cb.release();
-  p->bf_fr.release();
-  p->bf_fr64.release();
   for (auto e : p->evpool) (void)hipEventDestroy(e);
   if (p->stream) (void)hipStreamDestroy(p->stream);
-  delete p;
+  delete p;   // every DBuf member frees itself
   return LTE_OK;
 }
 
@@ -1698,10 +1117,7 @@ int lte_plan_set_early_stop(lte_plan* p, int on) {
     const size_t G = ((size_t)p->d.max_frames + 63) / 64;
     bool bad = false;
     for (auto& b : u) bad |= b.alloc(G * 64) != 0;
-    if (bad) {
-      for (auto& b : u) b.release();
-      return fail(LTE_ENOMEM, "early-stop iteration counts");
-    }
+    if (bad) return fail(LTE_ENOMEM, "early-stop iteration counts");
     p->es_used.swap(u);
   }
   if (on && p->d.turbo_iters > 255) return fail(LTE_EUNSUP, "early stop reports iterations as bytes: turbo_iters <= 255");
@@ -1792,12 +1208,6 @@ int lte_timing_read(lte_plan* p, char* names, int names_len, double* ms, int64_t
     names[names_len - 1] = 0;
   }
   return KN_COUNT;
-}
-
-static void pack_bits(const uint8_t* bits, int n, uint32_t* w, int nw) {
-  std::memset(w, 0, sizeof(uint32_t) * nw);
-  for (int i = 0; i < n; ++i)
-    if (bits[i] & 1) w[i >> 5] |= 1u << (31 - (i & 31));
 }
 
 }  // extern "C"
@@ -2020,6 +1430,148 @@ static MimoPath select_mimo(const lte_plan* p, const lte_run_args* a, const Knob
   return s;
 }
 
+// ---------------------------------------------------------------------------
+// The stages every run driver shares: capture buffers, the coded receive tail
+// and the read-back of the results.
+
+// What a receiver writes beside its counts when a capture asks for it: the
+// data symbols [B][n_syms] and the received bits [B][n_bits] (null: not asked)
+template <class R>
+struct Captures {
+  cx<R>* syms = nullptr;
+  uint8_t* bits = nullptr;
+  size_t n_syms = 0;
+};
+
+template <class R>
+static int capture_bufs(lte_plan* p, const lte_run_args* a, int B, size_t n_syms, Captures<R>* cap) {
+  cap->n_syms = n_syms;
+  if (a->cap_data_syms) {
+    if (cbuf<R>(p).capbuf.alloc((size_t)B * n_syms)) return fail(LTE_ENOMEM, "capture");
+    cap->syms = cbuf<R>(p).capbuf.p;
+  }
+  if (a->cap_bits_rx) {
+    if (p->cap_bits.alloc((size_t)B * p->d.n_bits)) return fail(LTE_ENOMEM, "capture");
+    cap->bits = p->cap_bits.p;
+  }
+  return LTE_OK;
+}
+
+// The coded receive tail: the receiver's soft output -> decoder rows (rx_map;
+// zn: k_dematch_zn demaps (z, nv) with nd noise variances per row, nv_pairs:
+// one per Alamouti RE pair), turbo decoding, CRC and error counts per frame.
+// HARQ (SISO only): add0 = 0 is round 0, which first zeroes the rows its map
+// leaves unwritten, add0 = 1 a later round, which adds to the rows' sums;
+// hq_skip: the skip-aware decoders; the groups they skipped go to hq_last[2].
+template <class R>
+static int decode_blocks(lte_plan* p, const lte_run_args* a, int B, const int32_t* rx_map, int nd, int nv_pairs,
+                         int add0, bool zn, bool hq_skip, uint8_t* cap_bits_dev, const uint32_t* inj_bits) {
+  const lte_plan_desc& d = p->d;
+  ChainBufs<R>& c = cbuf<R>(p);
+  hipStream_t s = p->stream;
+  const int G = (B + 63) / 64;
+  {
+    Timer t(p, KN_DEMATCH);
+    if (p->harq && !add0 && p->hq_nz)
+      LCHK(launch_harq_zero<R>(s, p->hq_zmap.p, p->hq_nz, G, c.blk_ptrs.p, p->rows_dev.p, turbo_plan_ch(p)));
+    if (zn)
+      LCHK(launch_dematch_zn<R>(s, zn_z<R>(p), zn_nv<R>(p), p->n_re_bits / d.bps, nd, d.bps, B, rx_map, p->n_layers,
+                                c.blk_ptrs.p, p->rows_dev.p, turbo_plan_ch(p), 0, nv_pairs, add0));
+    else
+      LCHK(launch_dematch<R>(s, c.llr.p, p->n_re_bits, B, rx_map, p->n_layers, c.blk_ptrs.p, p->rows_dev.p,
+                             turbo_plan_ch(p), 0, add0));
+  }
+  std::vector<TurboJob> jobs(p->C);
+  for (int r = 0; r < p->C; ++r) {
+    const CbInfo& cb = p->cbs[r];
+    jobs[r] = TurboJob{c.blk[r].p, c.ckpt[r].p, p->decb[r].p, cb.K, cb.f1, cb.f2, G, turbo_plan_ch(p)};
+  }
+  // HARQ rounds >= 1: groups whose frames are all acknowledged return at once
+  // (k_turbo*_skip read k_harq_latch's flags); none left: no decoder launch
+  const bool skip = hq_skip && (int)p->hq_skip_h.size() == G;
+  int nskip = 0;
+  if (skip)
+    for (int g = 0; g < G; ++g) nskip += p->hq_skip_h[g] ? 1 : 0;
+  p->hq_last[2] = nskip;
+  if (!(skip && nskip == G)) {
+    Timer t(p, KN_TURBO);
+    if (skip)
+      LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, sizeof(R) == 8 ? 1 : 0, p->hq_skip.p));
+    else
+      LCHK(plan_launch_turbo(p, s, jobs, B, sizeof(R) == 8 ? 1 : 0));
+  }
+  Timer t(p, KN_CRC);
+  LCHK(launch_crc_count(s, p->cbi.p, p->C, p->dec_ptrs.p, p->kw_dev.p, B, p->pw.p, p->PW, d.n_bits, p->frame_err.p,
+                        p->frame_crc.p, cap_bits_dev, 0, inj_bits ? nullptr : p->fid.p, a->seed));
+  return LTE_OK;
+}
+
+// The received streams as the receivers read them (strides in samples) and
+// the noise draws they add, for the cap_signal_rx capture (k_cap_rx);
+// num_rx = 0: the chain has no time-domain streams (beamforming)
+template <class R>
+struct RxStreams {
+  int num_rx;
+  const cx<R>* y;
+  int64_t rx_stride, frame_stride;
+  uint64_t seed;
+  const R* inj_z;
+  int64_t inj_z_stride;
+};
+
+// End of every run: the per-SNR counters (acc: the receiver ran), then the
+// results and the captures every chain has to the caller, the final
+// synchronise, the launch timings and the host-side adds.  A driver queues its
+// own captures on the stream before it calls this.
+template <class R>
+static int read_back(lte_plan* p, const lte_run_args* a, int B, int n_snr, bool coded, bool acc,
+                     const Captures<R>& cap, const RxStreams<R>& rxs) {
+  using V = cx<R>;
+  const lte_plan_desc& d = p->d;
+  ChainBufs<R>& c = cbuf<R>(p);
+  hipStream_t s = p->stream;
+  if (acc) {
+    Timer t(p, KN_ACC);
+    LCHK(launch_accumulate(s, B, coded ? 1 : 0, d.n_bits, n_snr, p->snr_idx.p, p->frame_err.p, p->frame_crc.p,
+                           p->counts.p));
+  }
+  std::vector<unsigned long long> hc((size_t)4 * n_snr);
+  HIPCHK(hipMemcpyAsync(hc.data(), p->counts.p, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+  if (a->frame_errors)
+    HIPCHK(hipMemcpyAsync(a->frame_errors, p->frame_err.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  std::vector<uint32_t> crc;
+  if (a->frame_crc_ok && coded) {
+    crc.resize(B);
+    HIPCHK(hipMemcpyAsync(crc.data(), p->frame_crc.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  }
+  DBuf<V> sig_rx;   // lives until the final synchronise below has passed
+  if (a->cap_signal_rx && rxs.num_rx) {
+    const size_t n = (size_t)B * rxs.num_rx * p->L;
+    if (sig_rx.alloc(n)) return fail(LTE_ENOMEM, "capture");
+    {
+      Timer t(p, KN_CAP);
+      LCHK(launch_cap_rx<R>(s, p->L, rxs.num_rx, B, rxs.y, rxs.rx_stride, rxs.frame_stride, c.npow.p, p->fid.p,
+                            rxs.seed, rxs.inj_z, rxs.inj_z_stride, sig_rx.p));
+    }
+    HIPCHK(hipMemcpyAsync(a->cap_signal_rx, sig_rx.p, n * sizeof(V), hipMemcpyDeviceToHost, s));
+  }
+  if (a->cap_data_syms)
+    HIPCHK(hipMemcpyAsync(a->cap_data_syms, cap.syms, (size_t)B * cap.n_syms * sizeof(V), hipMemcpyDeviceToHost, s));
+  if (a->cap_bits_rx)
+    HIPCHK(hipMemcpyAsync(a->cap_bits_rx, cap.bits, (size_t)B * d.n_bits, hipMemcpyDeviceToHost, s));
+  if (a->cap_llr && coded)
+    HIPCHK(hipMemcpyAsync(a->cap_llr, c.llr.p, (size_t)B * p->n_re_bits * sizeof(R), hipMemcpyDeviceToHost, s));
+  if (a->cap_noise_power && rxs.num_rx)
+    HIPCHK(hipMemcpyAsync(a->cap_noise_power, c.npow.p, (size_t)B * rxs.num_rx * sizeof(R), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (p->timing) collect_timing(p);
+  if (a->counts)
+    for (size_t i = 0; i < hc.size(); ++i) a->counts[i] += hc[i];
+  if (a->frame_crc_ok && coded)
+    for (int b = 0; b < B; ++b) a->frame_crc_ok[b] = (uint8_t)crc[b];
+  return LTE_OK;
+}
+
 // Multi-antenna chains (SFBC 2xN, uncoded / coded; TM4 spatial multiplexing)
 // in precision R.
 template <class R>
@@ -2151,94 +1703,26 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, in
                                  h_pilots ? 1 : 0));
     }
   }
-  V* cap_syms_dev = nullptr;
-  uint8_t* cap_bits_dev = nullptr;
-  if (a->cap_data_syms) {
-    if (c.capbuf.alloc((size_t)B * p->n_sym * m.res)) return fail(LTE_ENOMEM, "capture");
-    cap_syms_dev = c.capbuf.p;
-  }
-  if (a->cap_bits_rx) {
-    if (p->cap_bits.alloc((size_t)B * d.n_bits)) return fail(LTE_ENOMEM, "capture");
-    cap_bits_dev = p->cap_bits.p;
-  }
+  Captures<R> cap;
+  if (const int e = capture_bufs<R>(p, a, B, (size_t)p->n_sym * m.res, &cap)) return e;
   if (!rx_fuse) {
     Timer t(p, KN_RX_DATA);
     if (sfbc)
       LCHK(launch_det_sfbc<R>(s, g, m, coded ? 1 : 0, ray ? 1 : 0, B, c.Ym.p, c.H.p, c.snr_lin.p, p->pw.p, p->PW,
-                              d.n_bits, p->frame_err.p, c.llr.p, cap_syms_dev, coded ? nullptr : cap_bits_dev,
+                              d.n_bits, p->frame_err.p, c.llr.p, cap.syms, coded ? nullptr : cap.bits,
                               zn ? zn_z<R>(p) : nullptr, zn ? zn_nv<R>(p) : nullptr));
     else
       LCHK(launch_det_spatial<R>(s, g, m, B, c.Ym.p, c.H.p, p->nvar.p, p->pw.p, p->PW, d.n_bits, p->frame_err.p,
-                                 cap_syms_dev, cap_bits_dev, h_pilots ? 1 : 0, path.det_stage ? 1 : 0));
+                                 cap.syms, cap.bits, h_pilots ? 1 : 0, path.det_stage ? 1 : 0));
   }
-  if (coded) {
-    {
-      Timer t(p, KN_DEMATCH);
-      if (zn)
-        LCHK(launch_dematch_zn<R>(s, zn_z<R>(p), zn_nv<R>(p), p->n_re_bits / d.bps, m.res, d.bps, B, p->rx_map.p,
-                                  p->n_layers, c.blk_ptrs.p, p->rows_dev.p, turbo_plan_ch(p), 0, 1));
-      else
-        LCHK(launch_dematch<R>(s, c.llr.p, p->n_re_bits, B, p->rx_map.p, p->n_layers, c.blk_ptrs.p, p->rows_dev.p,
-                                 turbo_plan_ch(p)));
-    }
-    const int G = (B + 63) / 64;
-    std::vector<TurboJob> jobs(p->C);
-    for (int r = 0; r < p->C; ++r) {
-      const CbInfo& cb = p->cbs[r];
-      jobs[r] = TurboJob{c.blk[r].p, c.ckpt[r].p, p->decb[r].p, cb.K, cb.f1, cb.f2, G, turbo_plan_ch(p)};
-    }
-    {
-      Timer t(p, KN_TURBO);
-      LCHK(plan_launch_turbo(p, s, jobs, B, sizeof(R) == 8 ? 1 : 0));
-    }
-    {
-      Timer t(p, KN_CRC);
-      LCHK(launch_crc_count(s, p->cbi.p, p->C, p->dec_ptrs.p, p->kw_dev.p, B, p->pw.p, p->PW, d.n_bits,
-                            p->frame_err.p, p->frame_crc.p, cap_bits_dev, 0, inj_bits ? nullptr : p->fid.p,
-                            a->seed));
-    }
-  }
-  {
-    Timer t(p, KN_ACC);
-    LCHK(launch_accumulate(s, B, coded ? 1 : 0, d.n_bits, n_snr, p->snr_idx.p, p->frame_err.p, p->frame_crc.p, p->counts.p));
-  }
-  std::vector<unsigned long long> hc((size_t)4 * n_snr);
-  HIPCHK(hipMemcpyAsync(hc.data(), p->counts.p, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  if (a->frame_errors)
-    HIPCHK(hipMemcpyAsync(a->frame_errors, p->frame_err.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  std::vector<uint32_t> crc;
-  if (a->frame_crc_ok && coded) {
-    crc.resize(B);
-    HIPCHK(hipMemcpyAsync(crc.data(), p->frame_crc.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  }
+  if (coded)   // (k_det_sfbc's noise variances are per Alamouti RE pair)
+    if (const int e = decode_blocks<R>(p, a, B, p->rx_map.p, m.res, 1, 0, zn, false, cap.bits, inj_bits)) return e;
+  // this chain's own captures; lpart / lstats live until read_back has synchronised
   if (a->cap_signal_tx)
     HIPCHK(hipMemcpyAsync(a->cap_signal_tx, c.x.p, (size_t)B * m.num_tx * p->L * sizeof(V), hipMemcpyDeviceToHost, s));
-  if (a->cap_signal_rx) {
-    DBuf<V> tmp;
-    if (tmp.alloc((size_t)B * m.num_rx * p->L)) return fail(LTE_ENOMEM, "capture");
-    {
-      Timer t(p, KN_CAP);
-      hipLaunchKernelGGL(k_cap_rx<R>, dim3(((p->L + 255) / 256) * B, m.num_rx), dim3(256), 0, s, p->L, m.num_rx, B,
-                         c.y.p, (int64_t)p->L, (int64_t)m.num_rx * p->L, c.npow.p, p->fid.p, a->seed, inj_z,
-                         inj_z_stride, tmp.p);
-      LCHK((int)hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(a->cap_signal_rx, tmp.p, (size_t)B * m.num_rx * p->L * sizeof(V), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    tmp.release();
-  }
-  if (a->cap_data_syms)
-    HIPCHK(hipMemcpyAsync(a->cap_data_syms, cap_syms_dev, (size_t)B * p->n_sym * m.res * sizeof(V),
-                          hipMemcpyDeviceToHost, s));
   if (a->cap_H)   // multi-antenna layout [B][num_rx][n_est][num_tx][n_dsc]
     HIPCHK(hipMemcpyAsync(a->cap_H, c.H.p, (size_t)B * m.num_rx * m.n_est * m.num_tx * m.n_dsc * sizeof(V),
                           hipMemcpyDeviceToHost, s));
-  if (a->cap_bits_rx)
-    HIPCHK(hipMemcpyAsync(a->cap_bits_rx, cap_bits_dev, (size_t)B * d.n_bits, hipMemcpyDeviceToHost, s));
-  if (a->cap_llr && coded)
-    HIPCHK(hipMemcpyAsync(a->cap_llr, c.llr.p, (size_t)B * p->n_re_bits * sizeof(R), hipMemcpyDeviceToHost, s));
-  if (a->cap_noise_power)
-    HIPCHK(hipMemcpyAsync(a->cap_noise_power, c.npow.p, (size_t)B * m.num_rx * sizeof(R), hipMemcpyDeviceToHost, s));
   DBuf<R> lpart, lstats;
   if (a->cap_link_stats) {
     const int nb = (p->L + 255) / 256;
@@ -2252,18 +1736,10 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, in
     }
     HIPCHK(hipMemcpyAsync(a->cap_link_stats, lstats.p, (size_t)B * links * 4 * sizeof(R), hipMemcpyDeviceToHost, s));
   }
-  HIPCHK(hipStreamSynchronize(s));
-  if (p->timing) collect_timing(p);
-  if (a->counts)
-    for (size_t i = 0; i < hc.size(); ++i) a->counts[i] += hc[i];
-  if (a->frame_crc_ok && coded)
-    for (int b = 0; b < B; ++b) a->frame_crc_ok[b] = (uint8_t)crc[b];
-  return LTE_OK;
+  return read_back<R>(p, a, B, n_snr, coded, true, cap,
+                      RxStreams<R>{m.num_rx, c.y.p, (int64_t)p->L, (int64_t)m.num_rx * p->L, a->seed, inj_z,
+                                   inj_z_stride});
 }
-
-extern "C" {
-
-}  // extern "C"
 
 // Beamforming chain (frequency domain, flat H per frame), R = double (the
 // default) / float.  sig: the per-frame noise scale sqrt(10^(-SNR/10) / 2).
@@ -2293,41 +1769,20 @@ static int run_bf(lte_plan* p, const lte_run_args* a, int B, int n_snr, const st
     Timer t(p, KN_PAYLOAD);
     LCHK(launch_payload(s, p->pw.p, p->PW, d.n_bits, 0, p->fid.p, a->seed, B, inj_bits, inj_bits_stride));
   }
-  cx<R>* cap_syms_dev = nullptr;
-  uint8_t* cap_bits_dev = nullptr;
-  if (a->cap_data_syms) {
-    if (c.capbuf.alloc((size_t)B * p->L)) return fail(LTE_ENOMEM, "capture");
-    cap_syms_dev = c.capbuf.p;
-  }
-  if (a->cap_bits_rx) {
-    if (p->cap_bits.alloc((size_t)B * d.n_bits)) return fail(LTE_ENOMEM, "capture");
-    cap_bits_dev = p->cap_bits.p;
-  }
+  Captures<R> cap;
+  if (const int e = capture_bufs<R>(p, a, B, (size_t)p->L, &cap)) return e;
   {
     Timer t(p, KN_RX_DATA);
     LCHK(launch_bf<R>(s, B, p->n_sym, p->Nd, d.bps, d.num_tx, d.num_rx, d.bf_adaptive, p->bf_ncb, p->bf_cb.p,
                       p->fid.p, a->seed, inj_h, inj_h_stride, frd, c.snr_lin.p, p->pw.p, p->PW, d.n_bits, inj_z,
-                      inj_z_stride, p->frame_err.p, cap_syms_dev, cap_bits_dev));
+                      inj_z_stride, p->frame_err.p, cap.syms, cap.bits));
   }
-  {
-    Timer t(p, KN_ACC);
-    LCHK(launch_accumulate(s, B, 0, d.n_bits, n_snr, p->snr_idx.p, p->frame_err.p, p->frame_crc.p, p->counts.p));
-  }
-  std::vector<unsigned long long> hc((size_t)4 * n_snr);
-  HIPCHK(hipMemcpyAsync(hc.data(), p->counts.p, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  if (a->frame_errors)
-    HIPCHK(hipMemcpyAsync(a->frame_errors, p->frame_err.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  if (a->cap_data_syms)
-    HIPCHK(hipMemcpyAsync(a->cap_data_syms, cap_syms_dev, (size_t)B * p->L * sizeof(cx<R>), hipMemcpyDeviceToHost, s));
-  if (a->cap_bits_rx)
-    HIPCHK(hipMemcpyAsync(a->cap_bits_rx, cap_bits_dev, (size_t)B * d.n_bits, hipMemcpyDeviceToHost, s));
-  std::vector<BfFrameT<R>> fr;
+  std::vector<BfFrameT<R>> fr;   // this chain's own capture: the per-frame state
   if (a->cap_H || a->cap_pmi || a->cap_bf_gain) {
     fr.resize(B);
     HIPCHK(hipMemcpyAsync(fr.data(), frd, B * sizeof(BfFrameT<R>), hipMemcpyDeviceToHost, s));
   }
-  HIPCHK(hipStreamSynchronize(s));
-  if (p->timing) collect_timing(p);
+  if (const int e = read_back<R>(p, a, B, n_snr, false, true, cap, RxStreams<R>{})) return e;
   for (int b = 0; b < (int)fr.size(); ++b) {
     if (a->cap_H)   // [n_frames][num_rx][num_tx] complex in the plan's type
       for (int r = 0; r < d.num_rx; ++r)
@@ -2339,12 +1794,8 @@ static int run_bf(lte_plan* p, const lte_run_args* a, int B, int n_snr, const st
     if (a->cap_pmi) a->cap_pmi[b] = fr[b].pmi;
     if (a->cap_bf_gain) a->cap_bf_gain[b] = fr[b].gain_db;
   }
-  if (a->counts)
-    for (size_t i = 0; i < hc.size(); ++i) a->counts[i] += hc[i];
   return LTE_OK;
 }
-
-
 
 // Fading taps, fused TX + channel, first-samples power fix-up and noise power.
 template <class R>
@@ -2501,16 +1952,10 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
     LCHK(launch_rx_chest<R>(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, cseed, inj_z, inj_z_stride, c.H.p,
                             c.pstats.p));
   }
-  V* cap_syms_dev = nullptr;
-  uint8_t* cap_bits_dev = nullptr;
-  if (a->cap_data_syms) {
-    if (c.capbuf.alloc((size_t)B * p->n_sym * p->Nd)) return fail(LTE_ENOMEM, "capture");
-    cap_syms_dev = c.capbuf.p;
-  }
-  if (a->cap_bits_rx) {
-    if (p->cap_bits.alloc((size_t)B * d.n_bits)) return fail(LTE_ENOMEM, "capture");
-    cap_bits_dev = p->cap_bits.p;
-  }
+  Captures<R> cap;
+  if (const int e = capture_bufs<R>(p, a, B, (size_t)p->n_sym * p->Nd, &cap)) return e;
+  V* const cap_syms_dev = cap.syms;
+  uint8_t* const cap_bits_dev = cap.bits;
   const bool zn = path.zn;
   if (coded && !zn && c.llr.alloc((size_t)d.max_frames * p->n_re_bits)) return fail(LTE_ENOMEM, "LLR buffer");
   if (path.rx == RX_FRAME_W) {
@@ -2555,113 +2000,37 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
                            (d.sc_fdm && d.chain == LTE_CHAIN_UNCODED) ? 1 : 0, zn ? zn_nv<R>(p) : nullptr));
   }
   if (coded && do_rx) {
-    const int G = (B + 63) / 64;
     // HARQ: round 0 stores zeros in the rows its map does not cover (an earlier
     // process has left sums there), later rounds add to every row they cover
-    const int hq_add = hq_t >= 1 ? 1 : 0;
-    {
-      Timer t(p, KN_DEMATCH);
-      if (p->harq && hq_t == 0 && p->hq_nz)
-        LCHK(launch_harq_zero<R>(s, p->hq_zmap.p, p->hq_nz, G, c.blk_ptrs.p, p->rows_dev.p, turbo_plan_ch(p)));
-      if (zn)
-        LCHK(launch_dematch_zn<R>(s, zn_z<R>(p), zn_nv<R>(p), p->n_re_bits / d.bps, p->Nd, d.bps, B, rx_map,
-                                  p->n_layers, c.blk_ptrs.p, p->rows_dev.p, turbo_plan_ch(p), 0, 0, hq_add));
-      else
-        LCHK(launch_dematch<R>(s, c.llr.p, p->n_re_bits, B, rx_map, p->n_layers, c.blk_ptrs.p, p->rows_dev.p,
-                                 turbo_plan_ch(p), 0, hq_add));
-    }
-    std::vector<TurboJob> jobs(p->C);
-    for (int r = 0; r < p->C; ++r) {
-      const CbInfo& cb = p->cbs[r];
-      jobs[r] = TurboJob{c.blk[r].p, c.ckpt[r].p, p->decb[r].p, cb.K, cb.f1, cb.f2, G, turbo_plan_ch(p)};
-    }
-    // HARQ rounds >= 1: groups whose frames are all acknowledged return at once
-    // (k_turbo*_skip read k_harq_latch's flags); none left: no decoder launch
-    const bool skip = path.hq_skip && (int)p->hq_skip_h.size() == G;
-    int hq_nskip = 0;
-    if (skip)
-      for (int g = 0; g < G; ++g) hq_nskip += p->hq_skip_h[g] ? 1 : 0;
-    if (!(skip && hq_nskip == G)) {
-      Timer t(p, KN_TURBO);
-      if (skip)
-        LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, sizeof(R) == 8 ? 1 : 0, p->hq_skip.p));
-      else
-        LCHK(plan_launch_turbo(p, s, jobs, B, sizeof(R) == 8 ? 1 : 0));
-    }
-    {
-      Timer t(p, KN_CRC);
-      LCHK(launch_crc_count(s, p->cbi.p, p->C, p->dec_ptrs.p, p->kw_dev.p, B, p->pw.p, p->PW, d.n_bits,
-                            p->frame_err.p, p->frame_crc.p, cap_bits_dev, 0, inj_bits ? nullptr : p->fid.p,
-                            a->seed));
-    }
+    if (const int e = decode_blocks<R>(p, a, B, rx_map, p->Nd, 0, hq_t >= 1 ? 1 : 0, zn, path.hq_skip, cap_bits_dev,
+                                       inj_bits))
+      return e;
     if (p->harq) {
       {
         Timer t(p, KN_HARQ);
         LCHK(launch_harq_latch(s, B, hq_t, p->frame_err.p, p->frame_crc.p, p->hq_tx_used.p, p->hq_err.p, p->hq_crc.p,
                                p->hq_skip.p));
       }
+      const int G = (B + 63) / 64;
       p->hq_skip_h.resize(G);
       HIPCHK(hipMemcpyAsync(p->hq_skip_h.data(), p->hq_skip.p, G * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
       p->hq_last[0] = hq_t;
       p->hq_last[1] = hq_rv;
-      p->hq_last[2] = hq_nskip;
       p->hq_done = hq_t;
     }
   }
-  if (do_rx) {
-    Timer t(p, KN_ACC);
-    LCHK(launch_accumulate(s, B, coded ? 1 : 0, d.n_bits, n_snr, p->snr_idx.p, p->frame_err.p, p->frame_crc.p,
-                           p->counts.p));
-  }
-  // results
-  std::vector<unsigned long long> hc((size_t)4 * n_snr);
-  HIPCHK(hipMemcpyAsync(hc.data(), p->counts.p, hc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-  if (a->frame_errors)
-    HIPCHK(hipMemcpyAsync(a->frame_errors, p->frame_err.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  std::vector<uint32_t> crc;
-  if (a->frame_crc_ok && coded) {
-    crc.resize(B);
-    HIPCHK(hipMemcpyAsync(crc.data(), p->frame_crc.p, B * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  }
+  // this chain's own captures
   if (a->cap_signal_tx)
     HIPCHK(hipMemcpyAsync(a->cap_signal_tx, c.x.p, (size_t)B * p->L * sizeof(V), hipMemcpyDeviceToHost, s));
-  if (a->cap_signal_rx) {
-    DBuf<V> tmp;
-    if (tmp.alloc((size_t)B * rx * p->L)) return fail(LTE_ENOMEM, "capture");
-    {
-      Timer t(p, KN_CAP);
-      hipLaunchKernelGGL(k_cap_rx<R>, dim3(((p->L + 255) / 256) * B, rx), dim3(256), 0, s, p->L, rx, B, ysrc, yrs, yfs,
-                         c.npow.p, p->fid.p, cseed, inj_z, inj_z_stride, tmp.p);
-      LCHK((int)hipGetLastError());
-    }
-    HIPCHK(hipMemcpyAsync(a->cap_signal_rx, tmp.p, (size_t)B * rx * p->L * sizeof(V), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    tmp.release();
-  }
-  if (a->cap_data_syms)
-    HIPCHK(hipMemcpyAsync(a->cap_data_syms, cap_syms_dev, (size_t)B * p->n_sym * p->Nd * sizeof(V),
-                          hipMemcpyDeviceToHost, s));
   if (a->cap_H)
     HIPCHK(hipMemcpyAsync(a->cap_H, c.H.p, (size_t)B * rx * p->n_grp * d.N * sizeof(V), hipMemcpyDeviceToHost, s));
   if (a->cap_pilot_stats)
     HIPCHK(hipMemcpyAsync(a->cap_pilot_stats, c.pstats.p, (size_t)B * rx * p->n_grp * 2 * sizeof(R),
                           hipMemcpyDeviceToHost, s));
-  if (a->cap_bits_rx)
-    HIPCHK(hipMemcpyAsync(a->cap_bits_rx, cap_bits_dev, (size_t)B * d.n_bits, hipMemcpyDeviceToHost, s));
-  if (a->cap_llr && coded)
-    HIPCHK(hipMemcpyAsync(a->cap_llr, c.llr.p, (size_t)B * p->n_re_bits * sizeof(R), hipMemcpyDeviceToHost, s));
   if (a->cap_tx_syms && do_tx)
     HIPCHK(hipMemcpyAsync(a->cap_tx_syms, c.captx.p, (size_t)B * p->n_sym * p->Nd * sizeof(V), hipMemcpyDeviceToHost,
                           s));
-  if (a->cap_noise_power)
-    HIPCHK(hipMemcpyAsync(a->cap_noise_power, c.npow.p, (size_t)B * rx * sizeof(R), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (p->timing) collect_timing(p);
-  if (a->counts)
-    for (size_t i = 0; i < hc.size(); ++i) a->counts[i] += hc[i];
-  if (a->frame_crc_ok && coded)
-    for (int b = 0; b < B; ++b) a->frame_crc_ok[b] = (uint8_t)crc[b];
-  return LTE_OK;
+  return read_back<R>(p, a, B, n_snr, coded, do_rx, cap, RxStreams<R>{rx, ysrc, yrs, yfs, cseed, inj_z, inj_z_stride});
 }
 
 extern "C" {
@@ -2782,480 +2151,6 @@ int lte_run_path(const lte_plan* p, const lte_run_args* a, char* buf, int len) {
     n += std::snprintf(buf + n, len - n, " harq=t%d,rv%d,skip=%d", p->hq_round, p->hq.rv_seq[p->hq_round],
                        select_siso(p, a, knobs).hq_skip ? 1 : 0);
   return n < len ? n : len - 1;
-}
-
-// ------------------------------------------------------------------ stage entry points
-}  // extern "C"
-
-// Stage entry points (host in / out, the chains' device kernels), R = float / double.
-template <class R>
-static int stage_grid(int N, TableSet& t, Grid& g) {
-  g = Grid{};
-  g.N = N;
-  g.log2N = ilog2(N);
-  if (sizeof(R) == 8) {
-    if (upload(t.tw64, make_twiddles64(N))) return -1;
-    g.tw64 = t.tw64.p;
-  } else {
-    if (upload(t.tw, make_twiddles(N))) return -1;
-    g.tw = t.tw.p;
-  }
-  return 0;
-}
-
-template <class R>
-static int fft_host(int N, int inverse, int64_t batch, const R* in, R* out) {
-  if (N < 8 || N > 2048 || (N & (N - 1)) || batch < 0 || (!in && batch) || (!out && batch))
-    return fail(LTE_EINVAL, "bad fft arguments");
-  if (batch == 0) return LTE_OK;
-  if (N < 64) return fail(LTE_EUNSUP, "N < 64");
-  TableSet t;
-  Grid g;
-  if (stage_grid<R>(N, t, g)) return fail(LTE_ENOMEM, "tables");
-  DBuf<cx<R>> di, dout;
-  if (di.alloc(batch * N) || dout.alloc(batch * N)) { t.release(); return fail(LTE_ENOMEM, "fft buffers"); }
-  int rc = LTE_OK;
-  if (hipMemcpy(di.p, in, batch * N * sizeof(cx<R>), hipMemcpyHostToDevice) != hipSuccess ||
-      launch_fft<R>(nullptr, g, inverse, batch, di.p, dout.p) != 0 || hipDeviceSynchronize() != hipSuccess ||
-      hipMemcpy(out, dout.p, batch * N * sizeof(cx<R>), hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(LTE_EHIP, "fft failed");
-  di.release(); dout.release(); t.release();
-  return rc;
-}
-
-template <class R>
-static int dft_host(int M, int inverse, int64_t batch, const R* in, R* out) {
-  if (M < 1 || M > 1024 || batch < 0 || (!in && batch) || (!out && batch)) return fail(LTE_EINVAL, "bad dft arguments");
-  if (batch == 0) return LTE_OK;
-  int N = 64;
-  while (N < 2 * M - 1) N <<= 1;
-  TableSet t;
-  Grid g;
-  bool bad = stage_grid<R>(N, t, g) != 0;
-  if (!bad && sizeof(R) == 8) {
-    std::vector<double2> ch, bh;
-    make_bluestein64(N, M, ch, bh);
-    bad = upload(t.chirp64, ch) || upload(t.bhat64, bh);
-    g.chirp64 = t.chirp64.p;
-    g.bhat64 = t.bhat64.p;
-  } else if (!bad) {
-    std::vector<float2> ch, bh;
-    make_bluestein(N, M, ch, bh);
-    bad = upload(t.chirp, ch) || upload(t.bhat, bh);
-    g.chirp = t.chirp.p;
-    g.bhat = t.bhat.p;
-  }
-  if (bad) { t.release(); return fail(LTE_ENOMEM, "tables"); }
-  g.Nd = M;
-  DBuf<cx<R>> di, dout;
-  if (di.alloc(batch * M) || dout.alloc(batch * M)) { t.release(); return fail(LTE_ENOMEM, "dft buffers"); }
-  int rc = LTE_OK;
-  if (hipMemcpy(di.p, in, batch * M * sizeof(cx<R>), hipMemcpyHostToDevice) != hipSuccess ||
-      launch_dft<R>(nullptr, g, inverse, batch, di.p, dout.p) != 0 || hipDeviceSynchronize() != hipSuccess ||
-      hipMemcpy(out, dout.p, batch * M * sizeof(cx<R>), hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(LTE_EHIP, "dft failed");
-  di.release(); dout.release(); t.release();
-  return rc;
-}
-
-template <class R>
-static int llr_host(int bps, int64_t n, const R* syms, const R* nv, R* llr) {
-  if ((bps != 2 && bps != 4 && bps != 6) || n < 0) return fail(LTE_EINVAL, "bad llr arguments");
-  if (n == 0) return LTE_OK;
-  DBuf<cx<R>> ds;
-  DBuf<R> dn, dl;
-  if (ds.alloc(n) || dn.alloc(n) || dl.alloc(n * bps)) return fail(LTE_ENOMEM, "llr buffers");
-  int rc = LTE_OK;
-  if (hipMemcpy(ds.p, syms, n * sizeof(cx<R>), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(dn.p, nv, n * sizeof(R), hipMemcpyHostToDevice) != hipSuccess ||
-      launch_llr<R>(nullptr, bps, n, ds.p, dn.p, dl.p) ||
-      hipMemcpy(llr, dl.p, n * bps * sizeof(R), hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(LTE_EHIP, "llr failed");
-  ds.release(); dn.release(); dl.release();
-  return rc;
-}
-
-template <class R>
-static int hard_host(int bps, int64_t n, const R* syms, uint8_t* bits) {
-  if ((bps != 2 && bps != 4 && bps != 6) || n < 0) return fail(LTE_EINVAL, "bad hard arguments");
-  if (n == 0) return LTE_OK;
-  DBuf<cx<R>> ds;
-  DBuf<uint8_t> db;
-  if (ds.alloc(n) || db.alloc(n * bps)) return fail(LTE_ENOMEM, "buffers");
-  int rc = LTE_OK;
-  if (hipMemcpy(ds.p, syms, n * sizeof(cx<R>), hipMemcpyHostToDevice) != hipSuccess ||
-      launch_hard<R>(nullptr, bps, n, ds.p, db.p) ||
-      hipMemcpy(bits, db.p, n * bps, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(LTE_EHIP, "hard failed");
-  ds.release(); db.release();
-  return rc;
-}
-
-// QAMModulator.bits_to_symbols (core/modulator.py:61-88) on n whole symbols
-static int qam_map_host(int bps, int64_t n, const uint8_t* bits, double* out) {
-  if ((bps != 2 && bps != 4 && bps != 6) || n < 0 || (n && (!bits || !out)))
-    return fail(LTE_EINVAL, "bad qam map arguments");
-  if (n == 0) return LTE_OK;
-  DBuf<uint8_t> db;
-  DBuf<double2> dout;
-  if (db.alloc((size_t)n * bps) || dout.alloc(n)) return fail(LTE_ENOMEM, "qam map buffers");
-  int rc = LTE_OK;
-  if (hipMemcpy(db.p, bits, (size_t)n * bps, hipMemcpyHostToDevice) != hipSuccess ||
-      launch_qam_map(nullptr, bps, n, db.p, dout.p) || hipDeviceSynchronize() != hipSuccess ||
-      hipMemcpy(out, dout.p, (size_t)n * 16, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(LTE_EHIP, "qam map failed");
-  db.release(); dout.release();
-  return rc;
-}
-
-// QAMModulator.symbols_to_bits (core/modulator.py:90-112), the reference's
-// own distance and argmin
-static int hard_argmin_host(int bps, int64_t n, const double* syms, uint8_t* bits) {
-  if ((bps != 2 && bps != 4 && bps != 6) || n < 0 || (n && (!syms || !bits)))
-    return fail(LTE_EINVAL, "bad decision arguments");
-  if (n == 0) return LTE_OK;
-  DBuf<double2> ds;
-  DBuf<uint8_t> db;
-  if (ds.alloc(n) || db.alloc((size_t)n * bps)) return fail(LTE_ENOMEM, "decision buffers");
-  const bool ok = hipMemcpy(ds.p, syms, (size_t)n * 16, hipMemcpyHostToDevice) == hipSuccess &&
-                  launch_hard_argmin(nullptr, bps, n, ds.p, db.p) == 0 && hipDeviceSynchronize() == hipSuccess &&
-                  hipMemcpy(bits, db.p, (size_t)n * bps, hipMemcpyDeviceToHost) == hipSuccess;
-  ds.release(); db.release();
-  return ok ? LTE_OK : fail(LTE_EHIP, "decisions failed");
-}
-
-// LTEChannelEstimator.estimate_channel + _interpolate_channel
-// (core/lte_receiver.py:40-133) on batch received grids of N subcarriers
-static int chest_host(int N, int P, const int32_t* pidx, const double* known, int64_t batch, const double* Y,
-                      double* H, double* hp, double* stats) {
-  if (N < 1 || P < 1 || P > 4096 || batch < 0 || !pidx || !known || (batch && (!Y || !H)))
-    return fail(LTE_EINVAL, "bad channel estimation arguments");
-  for (int p = 0; p < P; ++p)
-    if (pidx[p] < 0 || pidx[p] >= N || (p && pidx[p] <= pidx[p - 1]))
-      return fail(LTE_EINVAL, "pilot indices must be ascending and inside [0, N)");
-  if (batch == 0) return LTE_OK;
-  DBuf<int32_t> dp;
-  DBuf<double2> dk, dy, dh, dhp;
-  DBuf<double> dst;
-  const size_t ny = (size_t)batch * N;
-  if (dp.alloc(P) || dk.alloc(P) || dy.alloc(ny) || dh.alloc(ny) || (hp && dhp.alloc((size_t)batch * P)) ||
-      (stats && dst.alloc((size_t)batch * 2)))
-    return fail(LTE_ENOMEM, "channel estimation buffers");
-  bool ok = hipMemcpy(dp.p, pidx, (size_t)P * 4, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(dk.p, known, (size_t)P * 16, hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(dy.p, Y, ny * 16, hipMemcpyHostToDevice) == hipSuccess &&
-            launch_chest(nullptr, N, P, dp.p, dk.p, batch, dy.p, dh.p, hp ? dhp.p : nullptr,
-                         stats ? dst.p : nullptr) == 0 &&
-            hipDeviceSynchronize() == hipSuccess && hipMemcpy(H, dh.p, ny * 16, hipMemcpyDeviceToHost) == hipSuccess;
-  if (ok && hp) ok = hipMemcpy(hp, dhp.p, (size_t)batch * P * 16, hipMemcpyDeviceToHost) == hipSuccess;
-  if (ok && stats) ok = hipMemcpy(stats, dst.p, (size_t)batch * 2 * 8, hipMemcpyDeviceToHost) == hipSuccess;
-  dp.release(); dk.release(); dy.release(); dh.release(); dhp.release(); dst.release();
-  return ok ? LTE_OK : fail(LTE_EHIP, "channel estimation failed");
-}
-
-// LTEEqualizerZF.equalize (core/lte_receiver.py:154-180): Y / (H + reg)
-static int zf_host(int64_t n, const double* Y, const double* H, double reg, double* out) {
-  if (n < 0 || (n && (!Y || !H || !out))) return fail(LTE_EINVAL, "bad equalizer arguments");
-  if (n == 0) return LTE_OK;
-  DBuf<double2> dy, dh, dout;
-  if (dy.alloc(n) || dh.alloc(n) || dout.alloc(n)) return fail(LTE_ENOMEM, "equalizer buffers");
-  const bool ok = hipMemcpy(dy.p, Y, (size_t)n * 16, hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(dh.p, H, (size_t)n * 16, hipMemcpyHostToDevice) == hipSuccess &&
-                  launch_zf(nullptr, n, dy.p, dh.p, reg, dout.p) == 0 && hipDeviceSynchronize() == hipSuccess &&
-                  hipMemcpy(out, dout.p, (size_t)n * 16, hipMemcpyDeviceToHost) == hipSuccess;
-  dy.release(); dh.release(); dout.release();
-  return ok ? LTE_OK : fail(LTE_EHIP, "equalizer failed");
-}
-
-extern "C" {
-
-int lte_qam_map_host64(int bps, int64_t n, const uint8_t* bits, double* out) {
-  return qam_map_host(bps, n, bits, out);
-}
-int lte_nearest_host64(int bps, int64_t n, const double* syms, uint8_t* bits) {
-  return hard_argmin_host(bps, n, syms, bits);
-}
-int lte_chest_host64(int N, int n_pilots, const int32_t* pilot_idx, const double* known, int64_t batch,
-                     const double* Y, double* H, double* pilot_ls, double* stats) {
-  return chest_host(N, n_pilots, pilot_idx, known, batch, Y, H, pilot_ls, stats);
-}
-int lte_zf_host64(int64_t n, const double* Y, const double* H, double regularization, double* out) {
-  return zf_host(n, Y, H, regularization, out);
-}
-int lte_rsc_encode_host(int64_t n, const uint8_t* bits, int termination, uint8_t* systematic, uint8_t* parity) {
-  if (n < 0 || (n && !bits) || !systematic || !parity) return fail(LTE_EINVAL, "bad rsc arguments");
-  const int64_t m = n + (termination ? 3 : 0);
-  if (m == 0) return LTE_OK;
-  DBuf<uint8_t> du, ds, dp;
-  if (du.alloc(n ? n : 1) || ds.alloc(m) || dp.alloc(m)) return fail(LTE_ENOMEM, "rsc buffers");
-  const bool ok = (n == 0 || hipMemcpy(du.p, bits, n, hipMemcpyHostToDevice) == hipSuccess) &&
-                  launch_rsc(nullptr, n, du.p, termination ? 1 : 0, ds.p, dp.p) == 0 &&
-                  hipMemcpy(systematic, ds.p, m, hipMemcpyDeviceToHost) == hipSuccess &&
-                  hipMemcpy(parity, dp.p, m, hipMemcpyDeviceToHost) == hipSuccess;
-  du.release(); ds.release(); dp.release();
-  return ok ? LTE_OK : fail(LTE_EHIP, "rsc failed");
-}
-
-int lte_fft_host(int N, int inverse, int64_t batch, const float* in, float* out) {
-  return fft_host<float>(N, inverse, batch, in, out);
-}
-int lte_fft_host64(int N, int inverse, int64_t batch, const double* in, double* out) {
-  return fft_host<double>(N, inverse, batch, in, out);
-}
-int lte_dft_host(int M, int inverse, int64_t batch, const float* in, float* out) {
-  return dft_host<float>(M, inverse, batch, in, out);
-}
-int lte_dft_host64(int M, int inverse, int64_t batch, const double* in, double* out) {
-  return dft_host<double>(M, inverse, batch, in, out);
-}
-int lte_llr_host(int bps, int64_t n, const float* syms, const float* nv, float* llr) {
-  return llr_host<float>(bps, n, syms, nv, llr);
-}
-int lte_llr_host64(int bps, int64_t n, const double* syms, const double* nv, double* llr) {
-  return llr_host<double>(bps, n, syms, nv, llr);
-}
-int lte_hard_host(int bps, int64_t n, const float* syms, uint8_t* bits) { return hard_host<float>(bps, n, syms, bits); }
-int lte_hard_host64(int bps, int64_t n, const double* syms, uint8_t* bits) {
-  return hard_host<double>(bps, n, syms, bits);
-}
-
-int lte_crc_host(int64_t n, const uint8_t* bits, uint32_t poly, int len, uint32_t* crc) {
-  if (n < 0 || !crc || (n && !bits)) return fail(LTE_EINVAL, "bad crc arguments");
-  if ((poly != 0x1864CFBu && poly != 0x1800063u) || len != 24) {
-    // any other CRC (CRC-16 0x11021, crc.py:187-209): the serial device kernel
-    if (len < 1 || len > 31 || (poly >> len) != 1u)
-      return fail(LTE_EUNSUP, "CRC length 1..31 with the x^len term in poly");
-    DBuf<uint8_t> db;
-    DBuf<uint32_t> dout;
-    if (db.alloc(n ? n : 1) || dout.alloc(1)) return fail(LTE_ENOMEM, "buffers");
-    const bool ok = (n == 0 || hipMemcpy(db.p, bits, n, hipMemcpyHostToDevice) == hipSuccess) &&
-                    launch_crc_serial(nullptr, n, db.p, poly & ((1u << len) - 1u), len, dout.p) == 0 &&
-                    hipMemcpy(crc, dout.p, 4, hipMemcpyDeviceToHost) == hipSuccess;
-    db.release(); dout.release();
-    return ok ? LTE_OK : fail(LTE_EHIP, "crc failed");
-  }
-  const int nw = (int)((n + 24 + 31) / 32) + 1;
-  std::vector<uint32_t> w(nw, 0);
-  pack_bits(bits, (int)n, w.data(), nw);
-  DBuf<uint32_t> dpw, dinj;
-  DBuf<uint64_t> dfid;
-  if (dpw.alloc(nw) || dinj.alloc(nw) || dfid.alloc(1)) return fail(LTE_ENOMEM, "buffers");
-  int rc = LTE_OK;
-  std::vector<uint32_t> o(nw);
-  if (hipMemcpy(dinj.p, w.data(), nw * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemset(dfid.p, 0, 8) != hipSuccess ||
-      launch_payload(nullptr, dpw.p, nw, (int)n, (int)(poly & 0xFFFFFFu), dfid.p, 0, 1, dinj.p, 0) ||
-      hipMemcpy(o.data(), dpw.p, nw * 4, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(LTE_EHIP, "crc failed");
-  if (rc == LTE_OK) {
-    uint32_t v = 0;
-    for (int t = 0; t < 24; ++t) {
-      const int64_t q = n + t;
-      v = (v << 1) | ((o[q >> 5] >> (31 - (q & 31))) & 1u);
-    }
-    *crc = v;
-  }
-  dpw.release(); dinj.release(); dfid.release();
-  return rc;
-}
-
-int lte_turbo_encode_host(int K, int64_t ncb, const uint8_t* bits, uint8_t* out) {
-  int f1, f2;
-  if (!qpp_lookup(K, &f1, &f2)) return fail(LTE_EINVAL, "Invalid code block size K=" + std::to_string(K));
-  if (ncb < 0 || (ncb && (!bits || !out))) return fail(LTE_EINVAL, "bad arguments");
-  if (ncb == 0) return LTE_OK;
-  const int PW = (K + 31) / 32 + 1, KW = PW, EW = (K + 6 + 31) / 32;
-  std::vector<uint32_t> w((size_t)ncb * PW);
-  for (int64_t c = 0; c < ncb; ++c) pack_bits(bits + c * K, K, &w[c * PW], PW);
-  CbInfo ci{K, 0, K, 0, 0, f1, f2, 3 * K + 12};
-  DBuf<uint32_t> dpw, denc;
-  DBuf<CbInfo> dci;
-  DBuf<uint16_t> dqm;
-  std::vector<CbInfo> vci{ci};
-  std::vector<uint16_t> qm(K + 32);
-  encode_qmask(&ci, 1, K + 32, qm.data());
-  if (dpw.alloc(w.size()) || denc.alloc((size_t)ncb * 3 * EW) || upload(dci, vci) || upload(dqm, qm)) {
-    dpw.release(); denc.release(); dci.release(); dqm.release();
-    return fail(LTE_ENOMEM, "buffers");
-  }
-  std::vector<uint32_t> e((size_t)ncb * 3 * EW);
-  int rc = LTE_OK;
-  if (hipMemcpy(dpw.p, w.data(), w.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      launch_encode(nullptr, dpw.p, PW, KW, denc.p, EW, dci.p, 1, (int)ncb, dqm.p, K + 32) ||
-      hipMemcpy(e.data(), denc.p, e.size() * 4, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(LTE_EHIP, "encode failed");
-  if (rc == LTE_OK) {
-    for (int64_t c = 0; c < ncb; ++c) {
-      const uint32_t* d0 = &e[c * 3 * EW];
-      const uint32_t* d1 = d0 + EW;
-      const uint32_t* d2 = d1 + EW;
-      auto gb = [](const uint32_t* w, int i) -> uint8_t { return (w[i >> 5] >> (31 - (i & 31))) & 1u; };
-      uint8_t* o = out + c * (3 * K + 12);
-      for (int k = 0; k < K; ++k) { o[3 * k] = gb(d0, k); o[3 * k + 1] = gb(d1, k); o[3 * k + 2] = gb(d2, k); }
-      for (int t = 0; t < 3; ++t) {
-        o[3 * K + t] = gb(d0, K + t);
-        o[3 * K + 3 + t] = gb(d1, K + t);
-        o[3 * K + 6 + t] = gb(d0, K + 3 + t);
-        o[3 * K + 9 + t] = gb(d2, K + t);
-      }
-    }
-  }
-  dpw.release(); denc.release(); dci.release(); dqm.release();
-  return rc;
-}
-
-}  // extern "C"
-
-// Host-side layout conversion [ncb][3K+12] -> decoder rows, shared by the
-// turbo entry points.  T = float (fast mode) / double (the reference's precision).
-// es_used set (mode TM_DEC1): the early-stop decoder with generator es_poly
-// (CRC24A_POLY / CRC24B_POLY), the iterations used per code block to es_used.
-template <class T>
-static int turbo_host_run(int K, int iters, int64_t ncb, const T* llr, const T* ls, const T* lp, const T* la,
-                          int mode, uint8_t* bits, T* app, uint32_t es_poly = 0, uint8_t* es_used = nullptr) {
-  int f1, f2;
-  if (!qpp_lookup(K, &f1, &f2)) return fail(LTE_EINVAL, "Invalid interleaver size K=" + std::to_string(K));
-  if (ncb < 0) return fail(LTE_EINVAL, "bad ncb");
-  if (ncb == 0) return LTE_OK;
-  const int f64 = sizeof(T) == 8;
-  const int G = (int)((ncb + 63) / 64);
-  const int ch = turbo_chunk(G);   // fewer than TURBO_CH groups: contiguous blocks, no padding
-  const int64_t rows = turbo_rows(K);
-  std::vector<T> h((size_t)turbo_galloc(G) * rows * 64, (T)0);
-  auto at = [&](int64_t c, int64_t row) -> T& { return h[turbo_elem_ch(ch, rows, c / 64, row) + (c % 64)]; };
-  // decoder rows hold LLR/2 (exact; lte_decoder.hip gam)
-  auto put = [&](int64_t c, int64_t row, T v) { at(c, row) = (T)0.5 * v; };
-  for (int64_t c = 0; c < ncb; ++c) {
-    if (mode == TM_APP) {
-      const T* s = ls + c * (K + 3);
-      const T* q = lp + c * (K + 3);
-      const T* A = la + c * (K + 3);
-      for (int k = 0; k < K + 3; ++k) { put(c, trow_ls(K, k), s[k]); put(c, trow_lp(K, 1, k), q[k]); }
-      for (int k = 0; k < K; ++k) put(c, trow_le(K, k), A[k]);
-    } else {
-      const T* l = llr + c * (3 * K + 12);
-      for (int k = 0; k < K; ++k) {
-        put(c, trow_ls(K, k), l[3 * k]);
-        put(c, trow_lp(K, 1, k), l[3 * k + 1]);
-        put(c, trow_lp(K, 2, k), l[3 * k + 2]);
-      }
-      for (int t = 0; t < 3; ++t) {
-        put(c, trow_ls(K, K + t), l[3 * K + t]);
-        put(c, trow_lp(K, 1, K + t), l[3 * K + 3 + t]);
-        put(c, trow_ls2t(K, t), l[3 * K + 6 + t]);
-        put(c, trow_lp(K, 2, K + t), l[3 * K + 9 + t]);
-      }
-    }
-  }
-  DBuf<T> db, dck;
-  DBuf<uint32_t> dbits, dused;
-  const int KW = turbo_kw(K);
-  if (db.alloc(h.size()) || dck.alloc((size_t)turbo_galloc(G) * turbo_nwin(K) * turbo_ck_rows(f64) * 64) ||
-      dbits.alloc((size_t)G * KW * 64) || (es_used && dused.alloc((size_t)G * 64))) {
-    db.release(); dck.release(); dbits.release(); dused.release();
-    return fail(LTE_ENOMEM, "turbo buffers");
-  }
-  int rc = LTE_OK;
-  std::vector<uint32_t> hb((size_t)G * KW * 64);
-  const TurboJob job{db.p, dck.p, dbits.p, K, f1, f2, G, ch};
-  const int nv = (int)ncb;
-  if (hipMemcpy(db.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess ||
-      (es_used ? launch_turbo_jobs_es(nullptr, &job, &dused.p, &nv, 1, iters, f64, es_poly)
-               : launch_turbo_jobs(nullptr, &job, 1, iters, mode, f64)) ||
-      hipDeviceSynchronize() != hipSuccess)
-    rc = fail(LTE_EHIP, std::string("turbo failed: ") + hipGetErrorString(hipGetLastError()));
-  if (rc == LTE_OK && es_used) {
-    std::vector<uint32_t> hu((size_t)G * 64);
-    if (hipMemcpy(hu.data(), dused.p, hu.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(LTE_EHIP, "copy");
-    for (int64_t c = 0; c < ncb && rc == LTE_OK; ++c) es_used[c] = (uint8_t)hu[c];
-  }
-  if (rc == LTE_OK) {
-    if (mode == TM_APP) {
-      if (hipMemcpy(h.data(), db.p, h.size() * sizeof(T), hipMemcpyDeviceToHost) != hipSuccess)
-        rc = fail(LTE_EHIP, "copy");
-      for (int64_t c = 0; c < ncb && rc == LTE_OK; ++c)
-        for (int k = 0; k < K; ++k) app[c * K + k] = at(c, trow_le(K, k));
-    } else {
-      if (hipMemcpy(hb.data(), dbits.p, hb.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = fail(LTE_EHIP, "copy");
-      for (int64_t c = 0; c < ncb && rc == LTE_OK; ++c)
-        for (int k = 0; k < K; ++k) {
-          const uint32_t w = hb[((c / 64) * KW + (k >> 5)) * 64 + (c % 64)];
-          bits[c * K + k] = (w >> (31 - (k & 31))) & 1u;
-        }
-    }
-  }
-  db.release(); dck.release(); dbits.release(); dused.release();
-  return rc;
-}
-
-// argument checks of the early-stop entries, all before the device is touched;
-// crc_poly with its x^24 term (as lte_crc_host takes it) -> *poly without
-static int turbo_es_args(int K, int iters, int64_t ncb, const void* llr, uint32_t crc_poly, const uint8_t* bits,
-                         const uint8_t* used, uint32_t* poly) {
-  int f1, f2;
-  if (!qpp_lookup(K, &f1, &f2)) return fail(LTE_EINVAL, "Invalid interleaver size K=" + std::to_string(K));
-  if (iters < 0 || iters > 255) return fail(LTE_EINVAL, "iters must be in 0..255");
-  if (ncb < 0 || ncb > (int64_t)1 << 30) return fail(LTE_EINVAL, "bad ncb");
-  if (crc_poly != 0x1864CFBu && crc_poly != 0x1800063u)
-    return fail(LTE_EINVAL, "crc_poly must be gCRC24A (0x1864CFB) or gCRC24B (0x1800063)");
-  if (!llr || !bits || !used) return fail(LTE_EINVAL, "null argument");
-  if (logmap_on()) return fail(LTE_EUNSUP, "CRC early termination runs the max-log decoders only");
-  *poly = crc_poly & 0xFFFFFFu;
-  return LTE_OK;
-}
-
-extern "C" {
-
-int lte_turbo_decode_es_host(int K, int iters, int64_t ncb, const float* llr, uint32_t crc_poly, uint8_t* bits,
-                             uint8_t* iters_used) {
-  uint32_t poly;
-  const int rc = turbo_es_args(K, iters, ncb, llr, crc_poly, bits, iters_used, &poly);
-  if (rc) return rc;
-  return turbo_host_run<float>(K, iters, ncb, llr, nullptr, nullptr, nullptr, TM_DEC1, bits, nullptr, poly, iters_used);
-}
-
-int lte_turbo_decode_es_host64(int K, int iters, int64_t ncb, const double* llr, uint32_t crc_poly, uint8_t* bits,
-                               uint8_t* iters_used) {
-  uint32_t poly;
-  const int rc = turbo_es_args(K, iters, ncb, llr, crc_poly, bits, iters_used, &poly);
-  if (rc) return rc;
-  return turbo_host_run<double>(K, iters, ncb, llr, nullptr, nullptr, nullptr, TM_DEC1, bits, nullptr, poly,
-                                iters_used);
-}
-
-int lte_turbo_decode_host(int K, int iters, int64_t ncb, const float* llr, uint8_t* bits) {
-  if (iters < 0 || (ncb > 0 && (!llr || !bits))) return fail(LTE_EINVAL, "bad arguments");
-  if (logmap_on()) return fail(LTE_EUNSUP, "exact log-MAP runs in float64 only (the f32 decoder is max-log)");
-  return turbo_host_run<float>(K, iters, ncb, llr, nullptr, nullptr, nullptr, TM_DEC1, bits, nullptr);
-}
-
-int lte_turbo_decode_host64(int K, int iters, int64_t ncb, const double* llr, uint8_t* bits) {
-  if (iters < 0 || (ncb > 0 && (!llr || !bits))) return fail(LTE_EINVAL, "bad arguments");
-  return turbo_host_run<double>(K, iters, ncb, llr, nullptr, nullptr, nullptr, TM_DEC1, bits, nullptr);
-}
-
-int lte_bcjr_host(int K, int64_t ncb, const float* ls, const float* lp, const float* la, float* app) {
-  if (ncb > 0 && (!ls || !lp || !la || !app)) return fail(LTE_EINVAL, "bad arguments");
-  if (logmap_on()) return fail(LTE_EUNSUP, "exact log-MAP runs in float64 only (the f32 decoder is max-log)");
-  return turbo_host_run<float>(K, 0, ncb, nullptr, ls, lp, la, TM_APP, nullptr, app);
-}
-
-int lte_bcjr_host64(int n, int64_t ncb, const double* ls, const double* lp, const double* la, double* app) {
-  if (n < 0 || ncb < 0 || (n > 0 && ncb > 0 && (!ls || !lp || !la || !app))) return fail(LTE_EINVAL, "bad arguments");
-  if (ncb == 0 || n == 0) return LTE_OK;   // K = 0: empty decisions and LLRs, like the reference
-  const size_t sz = (size_t)ncb * n;
-  DBuf<double> dls, dlp, dla, dal, dapp;
-  if (dls.alloc(sz) || dlp.alloc(sz) || dla.alloc(sz) || dal.alloc(sz * 8) || dapp.alloc(sz))
-    return fail(LTE_ENOMEM, "bcjr buffers");
-  int rc = LTE_OK;
-  if (hipMemcpy(dls.p, ls, sz * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(dlp.p, lp, sz * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(dla.p, la, sz * 8, hipMemcpyHostToDevice) != hipSuccess ||
-      launch_bcjr64(nullptr, dls.p, dlp.p, dla.p, n, (int)ncb, dal.p, dapp.p) ||
-      hipDeviceSynchronize() != hipSuccess || hipMemcpy(app, dapp.p, sz * 8, hipMemcpyDeviceToHost) != hipSuccess)
-    rc = fail(LTE_EHIP, std::string("bcjr failed: ") + hipGetErrorString(hipGetLastError()));
-  dls.release(); dlp.release(); dla.release(); dal.release(); dapp.release();
-  return rc;
 }
 
 }  // extern "C"

@@ -84,6 +84,11 @@ int launch_channel(hipStream_t s, const Grid& g, int B, int num_rx, int rayleigh
 template <class R>
 int launch_npow(hipStream_t s, int B, int num_rx, const R* pow_part, int nblk, int L, const R* snr_lin, R* npow);
 int channel_nblk(int L);   // power partials per (frame, rx) written by launch_channel
+// capture of the received streams [B][num_rx][L] with their noise added (k_cap_rx): y as the
+// receivers read it (strides in samples), the receivers' noise draws (Philox, or inj_z)
+template <class R>
+int launch_cap_rx(hipStream_t s, int L, int num_rx, int B, const cx<R>* y, int64_t y_rx_stride, int64_t y_frame_stride,
+                  const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z, int64_t inj_stride, cx<R>* out);
 // OFDM TX with the static-tap multipath channel fused in (SISO, fD = 0, every
 // delay <= CP, N >= 512): k_ofdm_tx<.., CH> writes the received stream outside
 // each symbol's CP (the only samples the receiver reads) and the power of the

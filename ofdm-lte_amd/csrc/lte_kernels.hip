@@ -1182,6 +1182,36 @@ int launch_npow(hipStream_t s, int B, int num_rx, const R* pow_part, int nblk, i
   return (int)hipGetLastError();
 }
 
+// received stream with its noise, as the reference returns it (signal + noise)
+template <class R>
+__global__ void k_cap_rx(int L, int num_rx, int B, const cx<R>* __restrict__ y, int64_t y_rx_stride,
+                         int64_t y_frame_stride, const R* __restrict__ npow, const uint64_t* __restrict__ fid,
+                         uint64_t seed, const R* __restrict__ inj_z, int64_t inj_stride, cx<R>* __restrict__ out) {
+  const int nb = (L + 255) / 256;
+  const int n = (blockIdx.x % nb) * blockDim.x + threadIdx.x;
+  const int rx = blockIdx.y, b = blockIdx.x / nb;
+  if (n >= L) return;
+  const R sigma = sqrt(npow[(size_t)b * num_rx + rx] / (R)2);
+  cx<R> z;
+  if (inj_z) {
+    const R* zf = inj_z + (size_t)b * inj_stride + (size_t)rx * 2 * L;
+    z = mkc(zf[n], zf[L + n]);
+  } else {
+    const u32x4 r = rng4(seed, fid[b], RNG_STREAM_NOISE + (uint32_t)rx, (uint32_t)(n >> 1));
+    z = (n & 1) ? gauss2<R>(r.z, r.w) : gauss2<R>(r.x, r.y);
+  }
+  const cx<R> v = y[b * y_frame_stride + rx * y_rx_stride + n];
+  out[((size_t)b * num_rx + rx) * L + n] = mkc(v.x + sigma * z.x, v.y + sigma * z.y);
+}
+
+template <class R>
+int launch_cap_rx(hipStream_t s, int L, int num_rx, int B, const cx<R>* y, int64_t y_rx_stride, int64_t y_frame_stride,
+                  const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z, int64_t inj_stride, cx<R>* out) {
+  hipLaunchKernelGGL(k_cap_rx<R>, dim3(((L + 255) / 256) * B, num_rx), dim3(256), 0, s, L, num_rx, B, y, y_rx_stride,
+                     y_frame_stride, npow, fid, seed, inj_z, inj_stride, out);
+  return (int)hipGetLastError();
+}
+
 template <class R>
 int launch_rx_chest(hipStream_t s, const Grid& g, int B, int num_rx, const cx<R>* y, int64_t y_rx_stride,
                     int64_t y_frame_stride, const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z,
@@ -2086,7 +2116,7 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
   return (int)hipGetLastError();
 }
 
-// explicit instances of the precision-templated launchers (lte_capi.hip)
+// explicit instances of the precision-templated launchers (lte_capi.hip, lte_stages.hip)
 #define LTE_INST(R)                                                                                                   \
   template int launch_ofdm_tx<R>(hipStream_t, const Grid&, int, const uint32_t*, int, const uint32_t*, int,          \
                                  const int32_t*, cx<R>*, int, cx<R>*, int, int);                                    \
@@ -2101,6 +2131,8 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
   template int launch_channel<R>(hipStream_t, const Grid&, int, int, int, int, const int32_t*, const R*, R, R,       \
                                  const R*, const cx<R>*, const cx<R>*, cx<R>*, R*, int, int);                       \
   template int launch_npow<R>(hipStream_t, int, int, const R*, int, int, const R*, R*);                             \
+  template int launch_cap_rx<R>(hipStream_t, int, int, int, const cx<R>*, int64_t, int64_t, const R*,                \
+                                const uint64_t*, uint64_t, const R*, int64_t, cx<R>*);                               \
   template int launch_rx_chest<R>(hipStream_t, const Grid&, int, int, const cx<R>*, int64_t, int64_t, const R*,      \
                                   const uint64_t*, uint64_t, const R*, int64_t, cx<R>*, R*);                        \
   template int launch_rx_data<R>(hipStream_t, const Grid&, int, int, int, int, const cx<R>*, int64_t, int64_t,       \

@@ -1,0 +1,212 @@
+// Host side of liblte_hip.so shared by lte_capi.hip (plans, run drivers) and
+// lte_stages.hip (stand-alone stage entry points): error reporting, owning
+// device buffers, the host table builders, and the plan itself.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <atomic>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "lte_common.h"
+#include "lte_internal.h"
+
+namespace lte {
+
+// records msg for lte_last_error() and returns code
+int fail(int code, const std::string& msg);
+
+#define HIPCHK(expr)                                                                         \
+  do {                                                                                       \
+    hipError_t _e = (expr);                                                                  \
+    if (_e != hipSuccess) return fail(LTE_EHIP, std::string(#expr ": ") + hipGetErrorString(_e)); \
+  } while (0)
+#define LCHK(expr)                                                                           \
+  do {                                                                                       \
+    int _e = (expr);                                                                         \
+    if (_e != 0) return fail(LTE_EHIP, std::string(#expr ": ") + hipGetErrorString((hipError_t)_e)); \
+  } while (0)
+
+// ------------------------------------------------------------------ buffers
+// bytes the process's DBufs hold at this moment (lte_device_bytes_held)
+extern std::atomic<int64_t> g_dev_bytes;
+
+// Owning device array: freed when it goes out of scope (hipFree waits for the
+// device, so work still pending on a buffer is never cut off), movable, not
+// copyable.  alloc only ever grows it; release frees early.
+template <class T>
+struct DBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  DBuf() = default;
+  DBuf(const DBuf&) = delete;
+  DBuf& operator=(const DBuf&) = delete;
+  DBuf(DBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DBuf& operator=(DBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      std::swap(p, o.p);
+      std::swap(n, o.n);
+    }
+    return *this;
+  }
+  ~DBuf() { release(); }
+  int alloc(size_t count) {
+    if (count <= n && p) return 0;
+    release();
+    if (count == 0) return 0;
+    if (hipMalloc(&p, count * sizeof(T)) != hipSuccess) {
+      p = nullptr;
+      return -1;
+    }
+    n = count;
+    g_dev_bytes += (int64_t)(n * sizeof(T));
+    return 0;
+  }
+  void release() {
+    if (p) {
+      (void)hipFree(p);
+      g_dev_bytes -= (int64_t)(n * sizeof(T));
+    }
+    p = nullptr;
+    n = 0;
+  }
+};
+
+template <class T>
+int upload(DBuf<T>& d, const std::vector<T>& h) {
+  if (d.alloc(std::max<size_t>(h.size(), 1))) return -1;
+  if (!h.empty() && hipMemcpy(d.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return -1;
+  return 0;
+}
+
+struct TableSet {  // device copies of the static grid tables for one N (f64 copies in f64 plans)
+  DBuf<int32_t> data, pilot, seg, kinfo;
+  DBuf<float> inv_gap;
+  DBuf<float2> pilots, tw, constel, chirp, bhat;
+  DBuf<double> inv_gap64;
+  DBuf<double2> pilots64, tw64, chirp64, bhat64;
+};
+
+// per-precision device buffers of the signal chains (R = float / double)
+template <class R>
+struct ChainBufs {
+  DBuf<cx<R>> x, y, coef, H, capbuf, captx, xh, tcoef;
+  DBuf<R> gains, phases, pow_part, pstats, npow, llr, snr_lin, inj_ph, inj_z;
+  // multi-antenna chains: received data SCs [B][n_sym][num_rx][n_dsc] (H holds
+  // the estimates [B][num_rx][n_est][num_tx][n_dsc]), transmit_mimo's link
+  // power partials / noise sigmas, link injections
+  DBuf<cx<R>> Ym;
+  DBuf<R> link_part, link_sigma, inj_lz, inj_lh;
+  std::vector<DBuf<R>> blk, ckpt;
+  DBuf<R*> blk_ptrs;
+};
+
+// ------------------------------------------------------------------ host tables (lte_capi.hip)
+int ilog2(int n);
+bool qpp_lookup(int K, int* f1, int* f2);   // QPP f1, f2 of interleaver size K (false: no such size)
+// sub_block_interleaver index map (rate_matching.py:25-94): v[i] = d[perm[i]]
+std::vector<int> subblock_perm(int n);
+// Where coded bit i of CB (K, rv) comes from: stream (0/1/2) and index in that
+// stream, or stream -1 (padding of v1/v2).  rate_matching.py:249-297.
+struct RmSrc { int stream, idx; };
+void rm_source(int K, int rv, int E, std::vector<RmSrc>& out);
+void make_pilots(int cell, int n, std::vector<double>& re_im);
+std::vector<double2> make_twiddles64(int N);
+std::vector<float2> make_twiddles(int N);
+void make_bluestein64(int N, int M, std::vector<double2>& chirp, std::vector<double2>& bhat);
+void make_bluestein(int N, int M, std::vector<float2>& chirp, std::vector<float2>& bhat);
+
+struct GridHost {
+  int N, Nc, cp, Nd, Np;
+  std::vector<int32_t> data, pilot, seg;
+  std::vector<float> inv_gap;
+};
+
+// launch families of lte_timing_read, in KNAMES' order (lte_capi.hip)
+enum { KN_PAYLOAD, KN_ENCODE, KN_OFDM_TX, KN_FADING, KN_CHANNEL, KN_RX_CHEST, KN_RX_DATA, KN_DEMATCH, KN_TURBO,
+       KN_CRC, KN_ACC, KN_CAP, KN_HARQ, KN_COUNT };
+
+struct Plan {
+  lte_plan_desc d;
+  int L, n_sym, Nd, Np, n_grp, nblk, PW, C = 0, KWmax = 0, EW = 0, enc_words = 0;
+  int coded_len = 0, n_re_bits = 0;
+  int log2N;
+  GridHost gh;
+  TableSet tabs;
+  Grid grid;
+  hipStream_t stream = nullptr;
+  int f64 = 0;                       // signal chain + decoder in float64 (every chain but beamforming)
+  int n_layers = 1;                  // rx_map layers (> 1: rate-matching repetition, E > N_cb)
+  std::vector<CbInfo> cbs;
+  // device
+  DBuf<CbInfo> cbi;
+  DBuf<int32_t> tx_map, rx_map, delays;
+  DBuf<int32_t> txf_map, txf_re;   // k_ofdm_txf's bank-aware lane order (empty: RE order)
+  double txf_model[2] = {0, 0};     // modelled extra LDS cycles per 32-lane gather: RE order, lane order
+  DBuf<uint32_t> pw, enc, inj_bits;
+  DBuf<uint8_t> inj_bytes;   // the caller's payload bits as given (packed on the device)
+  DBuf<uint16_t> enc_qmask;   // encoder 2's per-bit segment-state contributions (encode_qmask)
+  int qstride = 0;
+  ChainBufs<float> c32;              // f32 plans (and the beamforming chain)
+  ChainBufs<double> c64;             // f64 plans
+  DBuf<uint32_t> frame_err, frame_crc;
+  DBuf<int32_t> snr_idx;
+  DBuf<double> nvar;                 // spatial detectors' noise variance 10 ** (-snr_db / 10), float64
+  DBuf<uint64_t> fid;
+  DBuf<unsigned long long> counts;
+  DBuf<uint8_t> cap_bits;
+  std::vector<DBuf<uint32_t>> decb;
+  DBuf<int64_t> rows_dev;
+  DBuf<uint32_t*> dec_ptrs;
+  DBuf<int> kw_dev;
+  // CRC early termination (lte_plan_set_early_stop): per CB slot the iterations
+  // used [G][64] words; es_frames: frames of the last decoded run (0: none yet)
+  bool early_stop = false;
+  std::vector<DBuf<uint32_t>> es_used;
+  int es_frames = 0;
+  // HARQ (lte_plan_create_harq).  tx_map / rx_map hold one map per distinct rv
+  // of rv_seq back to back (n_re_bits entries each, hq_slot[rv] its index).
+  // hq_round: the next lte_run's transmission; hq_done: last completed round
+  // (-1: none in this process); hq_fids: round 0's frame ids.  Per frame
+  // [max_frames]: tx_used, latched errors / verdict (a passing verdict is the
+  // acknowledgement); hq_skip [G]: 1 = every frame of the group is acknowledged
+  // (k_harq_latch)
+  bool harq = false;
+  lte_harq_desc hq{};
+  int hq_slot[4] = {0, 0, 0, 0};
+  int hq_round = 0, hq_done = -1;
+  int hq_last[3] = {-1, 0, 0};       // last run: round, rv, decoder groups skipped
+  std::vector<uint64_t> hq_fids;
+  DBuf<uint32_t> hq_tx_used, hq_err, hq_crc, hq_skip;
+  std::vector<uint32_t> hq_skip_h;   // hq_skip after the last round
+  DBuf<int32_t> hq_zmap;             // decoder input rows (r << 24 | row) rv_seq[0]'s map leaves unwritten
+  int hq_nz = 0;
+  // multi-antenna chains (lte_mimo.hip)
+  bool mimo = false;
+  // beamforming chain (lte_bf.hip)
+  bool bf = false;
+  int bf_ncb = 0;
+  DBuf<double> bf_cb;
+  DBuf<BfFrameT<float>> bf_fr;
+  DBuf<BfFrameT<double>> bf_fr64;
+  int res = 0;                       // QAM symbols per OFDM symbol (= Nd for SISO / SIMO)
+  MimoGrid mg{};
+  DBuf<int32_t> m_np, m_ppos, m_pseg;
+  DBuf<float2> m_pval;
+  DBuf<double2> m_pval64;
+  DBuf<float> m_pig;
+  DBuf<double> m_pig64, m_W;
+  // timing
+  bool timing = false;
+  double kms[KN_COUNT] = {0};
+  int64_t klaunch[KN_COUNT] = {0};
+  std::vector<hipEvent_t> evpool;
+  std::vector<std::pair<int, int>> evuse;  // (kernel id, first event index)
+};
+
+}  // namespace lte
+
+struct lte_plan : lte::Plan {};   // the C ABI's opaque handle (include/lte_phy.h)

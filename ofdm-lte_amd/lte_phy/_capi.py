@@ -68,6 +68,7 @@ _SIGS = {
     'lte_device_init': (ctypes.c_int, [ctypes.c_int]),
     'lte_version': (ctypes.c_int, []),
     'lte_abi_check': (ctypes.c_int, [ctypes.c_int]),
+    'lte_device_bytes_held': (c_i64, []),
     'lte_plan_create': (ctypes.c_int, [P(PlanDesc), P(ctypes.c_void_p)]),
     'lte_plan_destroy': (ctypes.c_int, [ctypes.c_void_p]),
     'lte_plan_info': (ctypes.c_int, [ctypes.c_void_p, P(c_i64)]),
