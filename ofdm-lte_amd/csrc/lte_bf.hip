@@ -178,11 +178,10 @@ int launch_bf(hipStream_t s, int B, int n_sym, int Nd, int bps, int num_tx, int 
                      fid, seed, inj_h, inj_h_stride, fr);
   const int64_t n = (int64_t)B * n_sym * Nd;
   const dim3 grid((unsigned)((n + BWG - 1) / BWG));
-#define LTE_BFD(B_)                                                                                                \
-  hipLaunchKernelGGL((k_bf_data<R, B_>), grid, dim3(BWG), 0, s, B, n_sym, Nd, num_tx, num_rx, fr, sigma, pw, PW,  \
-                     n_bits, fid, seed, inj_z, inj_z_stride, frame_err, cap_syms, cap_bits)
-  if (bps == 2) LTE_BFD(2); else if (bps == 4) LTE_BFD(4); else LTE_BFD(6);
-#undef LTE_BFD
+  with_int_or<6, 2, 4>(bps, [&](auto Q) {
+    hipLaunchKernelGGL((k_bf_data<R, Q()>), grid, dim3(BWG), 0, s, B, n_sym, Nd, num_tx, num_rx, fr, sigma, pw, PW,
+                       n_bits, fid, seed, inj_z, inj_z_stride, frame_err, cap_syms, cap_bits);
+  });
   return (int)hipGetLastError();
 }
 

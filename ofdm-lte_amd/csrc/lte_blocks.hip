@@ -35,11 +35,9 @@ __global__ __launch_bounds__(BWG) void k_qam_map_stage(int64_t n, const uint8_t*
 int launch_qam_map(hipStream_t s, int bps, int64_t n, const uint8_t* bits, double2* out) {
   if (n <= 0) return 0;
   const dim3 grid((unsigned)((n + BWG - 1) / BWG));
-  if (bps == 2) hipLaunchKernelGGL(k_qam_map_stage<2>, grid, dim3(BWG), 0, s, n, bits, out);
-  else if (bps == 4) hipLaunchKernelGGL(k_qam_map_stage<4>, grid, dim3(BWG), 0, s, n, bits, out);
-  else if (bps == 6) hipLaunchKernelGGL(k_qam_map_stage<6>, grid, dim3(BWG), 0, s, n, bits, out);
-  else return (int)hipErrorInvalidValue;
-  return (int)hipGetLastError();
+  return launch_status(with_bps(bps, [&](auto Q) {
+    hipLaunchKernelGGL(k_qam_map_stage<Q()>, grid, dim3(BWG), 0, s, n, bits, out);
+  }));
 }
 
 // QAMModulator.symbols_to_bits / LTEReceiver._detect_symbols exactly as the
@@ -81,11 +79,9 @@ __global__ __launch_bounds__(BWG) void k_hard_argmin_stage(int64_t n, const doub
 int launch_hard_argmin(hipStream_t s, int bps, int64_t n, const double2* y, uint8_t* bits) {
   if (n <= 0) return 0;
   const dim3 grid((unsigned)((n + BWG - 1) / BWG));
-  if (bps == 2) hipLaunchKernelGGL(k_hard_argmin_stage<2>, grid, dim3(BWG), 0, s, n, y, bits);
-  else if (bps == 4) hipLaunchKernelGGL(k_hard_argmin_stage<4>, grid, dim3(BWG), 0, s, n, y, bits);
-  else if (bps == 6) hipLaunchKernelGGL(k_hard_argmin_stage<6>, grid, dim3(BWG), 0, s, n, y, bits);
-  else return (int)hipErrorInvalidValue;
-  return (int)hipGetLastError();
+  return launch_status(with_bps(bps, [&](auto Q) {
+    hipLaunchKernelGGL(k_hard_argmin_stage<Q()>, grid, dim3(BWG), 0, s, n, y, bits);
+  }));
 }
 
 // NumPy's pairwise summation (numpy/_core/src/umath/loops_utils.h.src

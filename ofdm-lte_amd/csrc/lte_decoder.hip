@@ -715,23 +715,23 @@ int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int
     if (skip) {   // every job has the flags' group count
       for (int i = 1; i < J.n; ++i)
         if (J.j[i].G != J.j[0].G) return (int)hipErrorInvalidValue;
-      if (ch == TURBO_CH && f64) hipLaunchKernelGGL(k_turbo64_skip<TURBO_CH>, grid, dim3(256), 0, s, J, iters, mode, skip);
-      else if (ch == TURBO_CH) hipLaunchKernelGGL(k_turbo_skip<TURBO_CH>, grid, dim3(256), 0, s, J, iters, mode, skip);
-      else if (ch == 1 && f64) hipLaunchKernelGGL(k_turbo64_skip<1>, grid, dim3(256), 0, s, J, iters, mode, skip);
-      else if (ch == 1) hipLaunchKernelGGL(k_turbo_skip<1>, grid, dim3(256), 0, s, J, iters, mode, skip);
-      else return (int)hipErrorInvalidValue;
-    } else if (ch == TURBO_CH) {
-      if (f64 && g_logmap) hipLaunchKernelGGL(k_turbo64_logmap<TURBO_CH>, grid, dim3(256), 0, s, J, iters, mode);
-      else if (f64) hipLaunchKernelGGL(k_turbo64<TURBO_CH>, grid, dim3(256), 0, s, J, iters, mode);
-      else hipLaunchKernelGGL(k_turbo<TURBO_CH>, grid, dim3(256), 0, s, J, iters, mode);
-    } else if (ch == 1) {
-      if (f64 && g_logmap) hipLaunchKernelGGL(k_turbo64_logmap<1>, grid, dim3(256), 0, s, J, iters, mode);
-      else if (f64) hipLaunchKernelGGL(k_turbo64<1>, grid, dim3(256), 0, s, J, iters, mode);
-      else hipLaunchKernelGGL(k_turbo<1>, grid, dim3(256), 0, s, J, iters, mode);
-    } else {
-      return (int)hipErrorInvalidValue;
     }
-    const int e = (int)hipGetLastError();
+    // the chunk width and the precision; skip and plain decoders in a dispatch
+    // each, which keeps their instances in the order they have been emitted in
+    auto with_form = [&](auto&& f) {
+      return with_int<TURBO_CH, 1>(ch, [&](auto CH) { with_bool(f64, [&](auto F64) { f(CH, F64); }); });
+    };
+    const int e = launch_status(skip ? with_form([&](auto CH, auto F64) {
+      if constexpr (F64()) hipLaunchKernelGGL(k_turbo64_skip<CH()>, grid, dim3(256), 0, s, J, iters, mode, skip);
+      else hipLaunchKernelGGL(k_turbo_skip<CH()>, grid, dim3(256), 0, s, J, iters, mode, skip);
+    }) : with_form([&](auto CH, auto F64) {
+      if constexpr (F64()) {
+        if (g_logmap) hipLaunchKernelGGL(k_turbo64_logmap<CH()>, grid, dim3(256), 0, s, J, iters, mode);
+        else hipLaunchKernelGGL(k_turbo64<CH()>, grid, dim3(256), 0, s, J, iters, mode);
+      } else {
+        hipLaunchKernelGGL(k_turbo<CH()>, grid, dim3(256), 0, s, J, iters, mode);
+      }
+    }));
     if (e) return e;
   }
   return 0;
@@ -759,16 +759,12 @@ int launch_turbo_jobs_es(hipStream_t s, const TurboJob* jobs, uint32_t* const* u
     for (int i = 1; i < J.n; ++i)
       if (J.j[i].ch != ch) return (int)hipErrorInvalidValue;
     const dim3 grid(waves), block(64);   // one wave per block (turbo_body_es)
-    if (ch == TURBO_CH) {
-      if (f64) hipLaunchKernelGGL(k_turbo64_es<TURBO_CH>, grid, block, 0, s, J, E, iters);
-      else hipLaunchKernelGGL(k_turbo_es<TURBO_CH>, grid, block, 0, s, J, E, iters);
-    } else if (ch == 1) {
-      if (f64) hipLaunchKernelGGL(k_turbo64_es<1>, grid, block, 0, s, J, E, iters);
-      else hipLaunchKernelGGL(k_turbo_es<1>, grid, block, 0, s, J, E, iters);
-    } else {
-      return (int)hipErrorInvalidValue;
-    }
-    const int e = (int)hipGetLastError();
+    const int e = launch_status(with_int<TURBO_CH, 1>(ch, [&](auto CH) {
+      with_bool(f64, [&](auto F64) {
+        if constexpr (F64()) hipLaunchKernelGGL(k_turbo64_es<CH()>, grid, block, 0, s, J, E, iters);
+        else hipLaunchKernelGGL(k_turbo_es<CH()>, grid, block, 0, s, J, E, iters);
+      });
+    }));
     if (e) return e;
   }
   return 0;
@@ -822,10 +818,9 @@ __global__ __launch_bounds__(64) void k_bcjr64(const double* __restrict__ ls, co
 int launch_bcjr64(hipStream_t s, const double* ls, const double* lp, const double* la, int n, int ncb,
                   double* alpha_scratch, double* app) {
   if (n < 1 || ncb < 1) return (int)hipErrorInvalidValue;
-  if (g_logmap)
-    hipLaunchKernelGGL(k_bcjr64<true>, dim3((ncb + 63) / 64), dim3(64), 0, s, ls, lp, la, n, ncb, alpha_scratch, app);
-  else
-    hipLaunchKernelGGL(k_bcjr64<false>, dim3((ncb + 63) / 64), dim3(64), 0, s, ls, lp, la, n, ncb, alpha_scratch, app);
+  with_bool(g_logmap, [&](auto LM) {
+    hipLaunchKernelGGL(k_bcjr64<LM()>, dim3((ncb + 63) / 64), dim3(64), 0, s, ls, lp, la, n, ncb, alpha_scratch, app);
+  });
   return (int)hipGetLastError();
 }
 

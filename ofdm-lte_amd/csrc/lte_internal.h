@@ -6,8 +6,13 @@
 #include "../../include/lte_phy.h"
 #include "lte_common.h"
 #include "lte_knobs.h"
+#include "lte_dispatch.h"
 
 namespace lte {
+
+// What a launcher returns after its dispatch: no instance for the run-time
+// values is an invalid argument, else the launch's own status.
+inline int launch_status(bool matched) { return matched ? (int)hipGetLastError() : (int)hipErrorInvalidValue; }
 
 // Per code-block-slot description (one entry per CB index r of a frame).
 struct CbInfo {

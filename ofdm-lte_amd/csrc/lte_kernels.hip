@@ -393,64 +393,20 @@ int launch_ofdm_tx(hipStream_t s, const Grid& g, int coded, const uint32_t* pw, 
   const size_t enc_shm = tx_enc_shm(coded, spw, enc_words, stage);
   const int stage_enc = enc_shm > 0;
   const size_t shm = (sc_fdm ? 2 : 1) * spw * g.N * sizeof(cx<R>) + enc_shm;
-#define LTE_TX(C_, B_, S_)                                                                                      \
-  hipLaunchKernelGGL((k_ofdm_tx<R, C_, B_, S_>), dim3(blocks), dim3(WG), shm, s, g, pw, PW, enc, enc_words, tx_map, \
-                     x, B, cap_syms, stage_enc, TxChannelT<R>{})
-  if (coded) {
-    if (g.bps == 2) LTE_TX(1, 2, false); else if (g.bps == 4) LTE_TX(1, 4, false); else LTE_TX(1, 6, false);
-  } else if (sc_fdm) {
-    if (g.bps == 2) LTE_TX(0, 2, true); else if (g.bps == 4) LTE_TX(0, 4, true); else LTE_TX(0, 6, true);
-  } else {
-    if (g.bps == 2) LTE_TX(0, 2, false); else if (g.bps == 4) LTE_TX(0, 4, false); else LTE_TX(0, 6, false);
-  }
-#undef LTE_TX
-  return (int)hipGetLastError();
+  return launch_status(with_bps(g.bps, [&](auto Q) {
+    with_bool(coded, [&](auto C) {
+      with_bool(sc_fdm, [&](auto S) {
+        constexpr bool SCF = S() && !C();   // SC-FDM is the uncoded chains' (checked above)
+        hipLaunchKernelGGL((k_ofdm_tx<R, C(), Q(), SCF>), dim3(blocks), dim3(WG), shm, s, g, pw, PW, enc, enc_words,
+                           tx_map, x, B, cap_syms, stage_enc, TxChannelT<R>{});
+      });
+    });
+  }));
 }
 
 bool txch_supported(const Grid& g, int n_paths, int max_delay) {
   return g.N >= 512 && n_paths >= 1 && n_paths <= TXCH_MAXP && max_delay >= 0 && max_delay <= g.cp &&
          2 * max_delay < g.N + g.cp;
-}
-
-// one k_ofdm_tx<.., CH> launch; float64 static taps (CH 1) of the ITU path
-// counts 4 and 6 with the count at compile time (tx_channel NP)
-template <class R, int C_, int B_, bool S_, int CH_, int NC_>
-static void ofdm_tx_ch_np(hipStream_t s, int blocks, size_t shm, const Grid& g, const uint32_t* pw, int PW,
-                          const uint32_t* enc, int enc_words, const int32_t* tx_map, int B, cx<R>* cap_syms,
-                          int stage_enc, const TxChannelT<R>& ch) {
-  if constexpr (CH_ == 1 && !S_ && sizeof(R) == 8) {
-    if (ch.n_paths == 4) {
-      hipLaunchKernelGGL((k_ofdm_tx<R, C_, B_, S_, CH_, NC_, 4>), dim3(blocks), dim3(WG), shm, s, g, pw, PW, enc,
-                         enc_words, tx_map, (cx<R>*)nullptr, B, cap_syms, stage_enc, ch);
-      return;
-    }
-    if (ch.n_paths == 6) {
-      hipLaunchKernelGGL((k_ofdm_tx<R, C_, B_, S_, CH_, NC_, 6>), dim3(blocks), dim3(WG), shm, s, g, pw, PW, enc,
-                         enc_words, tx_map, (cx<R>*)nullptr, B, cap_syms, stage_enc, ch);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((k_ofdm_tx<R, C_, B_, S_, CH_, NC_>), dim3(blocks), dim3(WG), shm, s, g, pw, PW, enc, enc_words,
-                     tx_map, (cx<R>*)nullptr, B, cap_syms, stage_enc, ch);
-}
-// compile-time N: 2048 (20 MHz), and 1024 (10 MHz, config 3) for the uncoded
-// OFDM transmitters with static taps
-template <class R, int C_, int B_, bool S_, int CH_>
-static void ofdm_tx_ch_go(hipStream_t s, int blocks, size_t shm, const Grid& g, const uint32_t* pw, int PW,
-                          const uint32_t* enc, int enc_words, const int32_t* tx_map, int B, cx<R>* cap_syms,
-                          int stage_enc, const TxChannelT<R>& ch) {
-  if (g.N == 2048) {
-    ofdm_tx_ch_np<R, C_, B_, S_, CH_, 2048>(s, blocks, shm, g, pw, PW, enc, enc_words, tx_map, B, cap_syms, stage_enc, ch);
-    return;
-  }
-  if constexpr (CH_ == 1 && !S_ && !C_) {
-    if (g.N == 1024) {
-      ofdm_tx_ch_np<R, C_, B_, S_, CH_, 1024>(s, blocks, shm, g, pw, PW, enc, enc_words, tx_map, B, cap_syms, stage_enc,
-                                              ch);
-      return;
-    }
-  }
-  ofdm_tx_ch_np<R, C_, B_, S_, CH_, 0>(s, blocks, shm, g, pw, PW, enc, enc_words, tx_map, B, cap_syms, stage_enc, ch);
 }
 
 template <class R>
@@ -469,22 +425,28 @@ int launch_ofdm_tx_ch(hipStream_t s, const Grid& g, int coded, const uint32_t* p
   const size_t enc_shm = tx_enc_shm(coded, spw, enc_words, stage);
   const int stage_enc = enc_shm > 0;
   const size_t shm = (sc_fdm ? 2 : 1) * (size_t)spw * g.N * sizeof(cx<R>) + enc_shm;
-#define LTE_TXC2(C_, B_, S_, CH_) \
-  ofdm_tx_ch_go<R, C_, B_, S_, CH_>(s, blocks, shm, g, pw, PW, enc, enc_words, tx_map, B, cap_syms, stage_enc, ch)
-#define LTE_TXC(C_, B_, S_)                                                                                      \
-  do {                                                                                                             \
-    if (ch.tcoef) { LTE_TXC2(C_, B_, S_, 2); } else { LTE_TXC2(C_, B_, S_, 1); }                                   \
-  } while (0)
-  if (coded) {
-    if (g.bps == 2) LTE_TXC(1, 2, false); else if (g.bps == 4) LTE_TXC(1, 4, false); else LTE_TXC(1, 6, false);
-  } else if (sc_fdm) {   // SC-FDM (uncoded SISO / SIMO transmitters): DFT precoding, then the same channel
-    if (g.bps == 2) LTE_TXC(0, 2, true); else if (g.bps == 4) LTE_TXC(0, 4, true); else LTE_TXC(0, 6, true);
-  } else {
-    if (g.bps == 2) LTE_TXC(0, 2, false); else if (g.bps == 4) LTE_TXC(0, 4, false); else LTE_TXC(0, 6, false);
-  }
-#undef LTE_TXC
-#undef LTE_TXC2
-  return (int)hipGetLastError();
+  return launch_status(with_bps(g.bps, [&](auto Q) {
+    with_bool(coded, [&](auto C) {
+      with_bool(sc_fdm, [&](auto S) {
+        with_bool(ch.tcoef != nullptr, [&](auto TV) {
+          with_n<2048, 1024>(g.N, [&](auto N) {
+            with_int_or<0, 4, 6>(ch.n_paths, [&](auto P) {
+              constexpr bool SCF = S() && !C();   // SC-FDM is the uncoded chains' (checked above)
+              constexpr int CH = TV() ? 2 : 1;    // tx_channel: static / time-varying taps
+              // compile-time N: 2048 (20 MHz), and 1024 (10 MHz, config 3) for the
+              // uncoded OFDM transmitters with static taps
+              constexpr int NC = N() == 1024 && !(CH == 1 && !SCF && !C()) ? 0 : N();
+              // float64 static taps of the ITU path counts 4 and 6: the count at
+              // compile time (tx_channel NP)
+              constexpr int NP = CH == 1 && !SCF && sizeof(R) == 8 ? P() : 0;
+              hipLaunchKernelGGL((k_ofdm_tx<R, C(), Q(), SCF, CH, NC, NP>), dim3(blocks), dim3(WG), shm, s, g, pw, PW,
+                                 enc, enc_words, tx_map, (cx<R>*)nullptr, B, cap_syms, stage_enc, ch);
+            });
+          });
+        });
+      });
+    });
+  }));
 }
 
 // Coded OFDM TX + static-tap channel, one slot per frame walking its OFDM
@@ -628,25 +590,19 @@ int launch_ofdm_txf(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_w
   // symbol pairs (LTE_TXF_SP = 2): two grids and one staged copy per frame
   const size_t shm2 = 2 * (size_t)g.N * sizeof(cx<R>) + (TXF_STAGE ? (size_t)enc_words * sizeof(uint32_t) : 0);
   const int blocks = (B + spw - 1) / spw;
-#define LTE_TXF(BPS_, NC_)                                                                                      \
-  do {                                                                                                          \
-    if (ch.tcoef)                                                                                               \
-      hipLaunchKernelGGL((k_ofdm_txf<R, BPS_, NC_, true>), dim3(blocks), dim3(WG), shm, s, g, enc, enc_words,   \
-                         tx_map, txf_map, txf_re, B, cap_syms, ch);                              \
-    else if (NC_ == 2048 && ch.n_paths == 4 && sizeof(R) == 8)                                                  \
-      txf_peda_launch<R, BPS_, NC_ == 2048 ? LTE_TXF_SP : 1>(s, g, enc, enc_words, tx_map, txf_map, txf_re, B,     \
-                                                            cap_syms, ch, blocks, shm, shm2);                   \
-    else                                                                                                        \
-      hipLaunchKernelGGL((k_ofdm_txf<R, BPS_, NC_>), dim3(blocks), dim3(WG), shm, s, g, enc, enc_words, tx_map, \
-                         txf_map, txf_re, B, cap_syms, ch);                                      \
-  } while (0)
-  if (g.N == 2048) {
-    if (g.bps == 2) LTE_TXF(2, 2048); else if (g.bps == 4) LTE_TXF(4, 2048); else LTE_TXF(6, 2048);
-  } else {
-    if (g.bps == 2) LTE_TXF(2, 0); else if (g.bps == 4) LTE_TXF(4, 0); else LTE_TXF(6, 0);
-  }
-#undef LTE_TXF
-  return (int)hipGetLastError();
+  return launch_status(with_bps(g.bps, [&](auto Q) {
+    with_n<2048>(g.N, [&](auto NC) {
+      if (ch.tcoef)
+        hipLaunchKernelGGL((k_ofdm_txf<R, Q(), NC(), true>), dim3(blocks), dim3(WG), shm, s, g, enc, enc_words,
+                           tx_map, txf_map, txf_re, B, cap_syms, ch);
+      else if (NC() == 2048 && ch.n_paths == 4 && sizeof(R) == 8)
+        txf_peda_launch<R, Q(), NC() == 2048 ? LTE_TXF_SP : 1>(s, g, enc, enc_words, tx_map, txf_map, txf_re, B,
+                                                              cap_syms, ch, blocks, shm, shm2);
+      else
+        hipLaunchKernelGGL((k_ofdm_txf<R, Q(), NC()>), dim3(blocks), dim3(WG), shm, s, g, enc, enc_words, tx_map,
+                           txf_map, txf_re, B, cap_syms, ch);
+    });
+  }));
 }
 
 // Power of each symbol's first max_delay channel-output samples (their delayed
@@ -1220,12 +1176,10 @@ int launch_rx_chest(hipStream_t s, const Grid& g, int B, int num_rx, const cx<R>
   const int64_t total = (int64_t)B * num_rx * g.n_grp;
   const int blocks = (int)((total + spw - 1) / spw);
   const size_t shm = (size_t)spw * (g.N + g.Np) * sizeof(cx<R>);
-  if (g.N == 2048)
-    hipLaunchKernelGGL((k_rx_chest<R, 2048>), dim3(blocks), dim3(WG), shm, s, g, B, num_rx, y, y_rx_stride,
+  with_n<2048>(g.N, [&](auto NC) {
+    hipLaunchKernelGGL((k_rx_chest<R, NC()>), dim3(blocks), dim3(WG), shm, s, g, B, num_rx, y, y_rx_stride,
                        y_frame_stride, npow, fid, seed, inj_z, inj_stride, H, pstats);
-  else
-    hipLaunchKernelGGL((k_rx_chest<R, 0>), dim3(blocks), dim3(WG), shm, s, g, B, num_rx, y, y_rx_stride,
-                       y_frame_stride, npow, fid, seed, inj_z, inj_stride, H, pstats);
+  });
   return (int)hipGetLastError();
 }
 
@@ -1599,33 +1553,18 @@ int launch_rx_frame(hipStream_t s, const Grid& g, int chain, int rayleigh, int B
   const int spw = WG / (g.N >> 3);
   const int blocks = (B + spw - 1) / spw;
   const size_t shm = (size_t)spw * (g.N + g.Np) * sizeof(cx<R>);
-#define LTE_RXF(CH_, BPS_, NC_)                                                                                      \
-  do {                                                                                                               \
-    if (CH_ == LTE_CHAIN_CODED && nv_out)                                                                            \
-      hipLaunchKernelGGL((k_rx_frame<R, CH_, BPS_, NC_, CH_ == LTE_CHAIN_CODED>), dim3(blocks), dim3(WG), shm, s, g, rayleigh, B, y,   \
-                         y_frame_stride, npow, snr_lin, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,    \
-                         llr, cap_syms, cap_bits, nv_out, H, pstats);                                                \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_rx_frame<R, CH_, BPS_, NC_>), dim3(blocks), dim3(WG), shm, s, g, rayleigh, B, y,         \
-                         y_frame_stride, npow, snr_lin, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,    \
-                         llr, cap_syms, cap_bits, nv_out, H, pstats);                                                \
-  } while (0)
-#define LTE_RXF_BPS(CH_, NC_)                                                                                        \
-  do {                                                                                                               \
-    if (g.bps == 2) LTE_RXF(CH_, 2, NC_);                                                                            \
-    else if (g.bps == 4) LTE_RXF(CH_, 4, NC_);                                                                       \
-    else LTE_RXF(CH_, 6, NC_);                                                                                       \
-  } while (0)
-  if (chain == LTE_CHAIN_CODED) {
-    if (g.N == 2048) LTE_RXF_BPS(LTE_CHAIN_CODED, 2048);   // the headline chain
-    else LTE_RXF_BPS(LTE_CHAIN_CODED, 0);
-  } else {
-    if (g.N == 2048) LTE_RXF_BPS(LTE_CHAIN_UNCODED, 2048);
-    else LTE_RXF_BPS(LTE_CHAIN_UNCODED, 0);
-  }
-#undef LTE_RXF_BPS
-#undef LTE_RXF
-  return (int)hipGetLastError();
+  return launch_status(with_int<LTE_CHAIN_CODED, LTE_CHAIN_UNCODED>(chain, [&](auto CH) {
+    with_bps(g.bps, [&](auto Q) {
+      with_n<2048>(g.N, [&](auto NC) {   // 2048: the headline chain
+        with_bool(nv_out != nullptr, [&](auto NV) {
+          constexpr bool ZN = CH() == LTE_CHAIN_CODED && NV();   // the (z, nv) hand-off is the coded chain's
+          hipLaunchKernelGGL((k_rx_frame<R, CH(), Q(), NC(), ZN>), dim3(blocks), dim3(WG), shm, s, g, rayleigh, B, y,
+                             y_frame_stride, npow, snr_lin, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,
+                             llr, cap_syms, cap_bits, nv_out, H, pstats);
+        });
+      });
+    });
+  }));
 }
 
 // Fused SIMO MRC receiver (simulate_simo, core/ofdm_core.py:1405-1534): one
@@ -2026,64 +1965,32 @@ int launch_rx_frame_simo(hipStream_t s, const Grid& g, int B, int num_rx, const 
     const bool xin = xc && xc->x_out;
     const size_t shm2 = (2 * (size_t)g.N + RXS_MAXRX * g.Np + (xin ? g.N : 0)) * sizeof(cx<R>);
     const TxChannelT<R> xcv = xin ? *xc : TxChannelT<R>{};
-#define LTE_RXS2_GO(BPS_, XIN_, SOFT_)                                                                               \
-  hipLaunchKernelGGL((k_rx_frame_simo2<R, BPS_, 1024, XIN_, SOFT_>), dim3(B), dim3(WG), shm2, s, g, B, num_rx, y,    \
-                     y_rx_stride, y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,     \
-                     cap_syms, cap_bits, xcv, snr_lin, llr, nv_out)
-#define LTE_RXS2(BPS_)                                                                                               \
-  do {                                                                                                               \
-    if (xin) LTE_RXS2_GO(BPS_, true, RXS_HARD);                                                                      \
-    else if (soft == RXS_SOFT_LLR) LTE_RXS2_GO(BPS_, false, RXS_SOFT_LLR);                                           \
-    else if (soft == RXS_SOFT_ZN) LTE_RXS2_GO(BPS_, false, (BPS_ == 2 ? RXS_SOFT_LLR : RXS_SOFT_ZN));                \
-    else LTE_RXS2_GO(BPS_, false, RXS_HARD);                                                                         \
-  } while (0)
-    if (g.bps == 2) LTE_RXS2(2); else if (g.bps == 4) LTE_RXS2(4); else LTE_RXS2(6);
-#undef LTE_RXS2
-#undef LTE_RXS2_GO
-    return (int)hipGetLastError();
+    return launch_status(with_bps(g.bps, [&](auto Q) {
+      with_bool(xin, [&](auto XIN) {
+        with_int<RXS_HARD, RXS_SOFT_LLR, RXS_SOFT_ZN>(soft, [&](auto S) {
+          // the symbol hand-over is uncoded only (soft with xin: refused above); no QPSK (z, nv) instance
+          constexpr int SOFT = XIN() ? RXS_HARD : Q() == 2 && S() == RXS_SOFT_ZN ? RXS_SOFT_LLR : S();
+          hipLaunchKernelGGL((k_rx_frame_simo2<R, Q(), 1024, XIN(), SOFT>), dim3(B), dim3(WG), shm2, s, g, B, num_rx,
+                             y, y_rx_stride, y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits,
+                             frame_err, cap_syms, cap_bits, xcv, snr_lin, llr, nv_out);
+        });
+      });
+    }));
   }
   if (xc && xc->x_out) return (int)hipErrorInvalidValue;   // the symbol handoff needs the paired receiver
   const int spw = WG / (g.N >> 3);
   const int blocks = (B + spw - 1) / spw;
   const size_t shm = (size_t)spw * (g.N + RXS_MAXRX * g.Np) * sizeof(cx<R>);
-#define LTE_RXS_GO(BPS_, NC_, SOFT_)                                                                                 \
-  hipLaunchKernelGGL((k_rx_frame_simo<R, BPS_, NC_, SOFT_>), dim3(blocks), dim3(WG), shm, s, g, B, num_rx, y,        \
-                     y_rx_stride, y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,     \
-                     cap_syms, cap_bits, H, pstats, snr_lin, llr, nv_out)
-#define LTE_RXS(BPS_, NC_)                                                                                           \
-  do {                                                                                                               \
-    if (soft == RXS_SOFT_LLR) LTE_RXS_GO(BPS_, NC_, RXS_SOFT_LLR);                                                   \
-    else if (soft == RXS_SOFT_ZN) LTE_RXS_GO(BPS_, NC_, (BPS_ == 2 ? RXS_SOFT_LLR : RXS_SOFT_ZN));                   \
-    else LTE_RXS_GO(BPS_, NC_, RXS_HARD);                                                                            \
-  } while (0)
-#define LTE_RXS_BPS(NC_)                                                                                             \
-  do {                                                                                                               \
-    if (g.bps == 2) LTE_RXS(2, NC_);                                                                                 \
-    else if (g.bps == 4) LTE_RXS(4, NC_);                                                                            \
-    else LTE_RXS(6, NC_);                                                                                            \
-  } while (0)
-  if (g.N == 1024) LTE_RXS_BPS(1024);   // config 3 (10 MHz)
-  else LTE_RXS_BPS(0);
-#undef LTE_RXS_BPS
-#undef LTE_RXS
-#undef LTE_RXS_GO
-  return (int)hipGetLastError();
-}
-
-template <class R, int CHAIN, bool SCF = false, int NC = 0>
-static void rx_data_bps(int bps, hipStream_t s, int blocks, size_t shm, const Grid& g, int rayleigh, int B,
-                        int num_rx, const cx<R>* y, int64_t y_rx_stride, int64_t y_frame_stride, const cx<R>* H,
-                        const R* npow, const R* snr_lin, const uint64_t* fid, uint64_t seed, const R* inj_z,
-                        int64_t inj_stride, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err, R* llr,
-                        cx<R>* cap_syms, uint8_t* cap_bits, R* nvo) {
-#define LTE_RXD(BPS_)                                                                                             \
-  hipLaunchKernelGGL((k_rx_data<R, CHAIN, BPS_, SCF, NC>), dim3(blocks), dim3(WG), shm, s, g, rayleigh, B, num_rx, y, \
-                     y_rx_stride, y_frame_stride, H, npow, snr_lin, fid, seed, inj_z, inj_stride, pw, PW, n_bits,   \
-                     frame_err, llr, cap_syms, cap_bits, nvo)
-  if (bps == 2) LTE_RXD(2);
-  else if (bps == 4) LTE_RXD(4);
-  else LTE_RXD(6);
-#undef LTE_RXD
+  return launch_status(with_bps(g.bps, [&](auto Q) {
+    with_n<1024>(g.N, [&](auto NC) {   // 1024: config 3 (10 MHz)
+      with_int<RXS_HARD, RXS_SOFT_LLR, RXS_SOFT_ZN>(soft, [&](auto S) {
+        constexpr int SOFT = Q() == 2 && S() == RXS_SOFT_ZN ? RXS_SOFT_LLR : S();   // no QPSK (z, nv) instance
+        hipLaunchKernelGGL((k_rx_frame_simo<R, Q(), NC(), SOFT>), dim3(blocks), dim3(WG), shm, s, g, B, num_rx, y,
+                           y_rx_stride, y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,
+                           cap_syms, cap_bits, H, pstats, snr_lin, llr, nv_out);
+      });
+    });
+  }));
 }
 
 template <class R>
@@ -2102,18 +2009,20 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
   if (total > 0x7FFFFFFF - spw) return (int)hipErrorInvalidValue;
   const int blocks = (int)((total + spw - 1) / spw);
   const size_t shm = spw * g.N * sizeof(cx<R>);
-#define LTE_RXA(CH_, SCF_, NC_)                                                                                   \
-  rx_data_bps<R, CH_, SCF_, NC_>(g.bps, s, blocks, shm, g, rayleigh, B, num_rx, y, y_rx_stride, y_frame_stride, H, \
-                                 npow, snr_lin, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err, llr,      \
-                                 cap_syms, cap_bits, nv_out)
-  if (chain == LTE_CHAIN_CODED && g.N == 2048) LTE_RXA(LTE_CHAIN_CODED, false, 2048);   // the headline chain
-  else if (chain == LTE_CHAIN_CODED) LTE_RXA(LTE_CHAIN_CODED, false, 0);
-  else if (chain == LTE_CHAIN_SIMO) LTE_RXA(LTE_CHAIN_SIMO, false, 0);
-  else if (chain == LTE_CHAIN_SIMO_CODED) LTE_RXA(LTE_CHAIN_SIMO_CODED, false, 0);
-  else if (sc_fdm) LTE_RXA(LTE_CHAIN_UNCODED, true, 0);
-  else LTE_RXA(LTE_CHAIN_UNCODED, false, 0);
-#undef LTE_RXA
-  return (int)hipGetLastError();
+  // any other chain's data symbols are received as the uncoded chain's
+  return launch_status(with_bps(g.bps, [&](auto Q) {
+    with_int_or<LTE_CHAIN_UNCODED, LTE_CHAIN_CODED, LTE_CHAIN_SIMO, LTE_CHAIN_SIMO_CODED>(chain, [&](auto CH) {
+      with_bool(sc_fdm, [&](auto S) {
+        with_n<2048>(g.N, [&](auto N) {
+          constexpr bool SCF = S() && CH() == LTE_CHAIN_UNCODED;   // SC-FDM is the uncoded chain's
+          constexpr int NC = CH() == LTE_CHAIN_CODED ? N() : 0;    // compile-time N: the headline chain
+          hipLaunchKernelGGL((k_rx_data<R, CH(), Q(), SCF, NC>), dim3(blocks), dim3(WG), shm, s, g, rayleigh, B,
+                             num_rx, y, y_rx_stride, y_frame_stride, H, npow, snr_lin, fid, seed, inj_z, inj_stride,
+                             pw, PW, n_bits, frame_err, llr, cap_syms, cap_bits, nv_out);
+        });
+      });
+    });
+  }));
 }
 
 // explicit instances of the precision-templated launchers (lte_capi.hip, lte_stages.hip)
@@ -2238,11 +2147,9 @@ __global__ void k_llr(int64_t n, const cx<R>* __restrict__ syms, const R* __rest
 template <class R>
 int launch_llr(hipStream_t s, int bps, int64_t n, const cx<R>* syms, const R* nv, R* llr) {
   const dim3 grid((unsigned)((n + WG - 1) / WG));
-  if (bps == 2) hipLaunchKernelGGL((k_llr<R, 2>), grid, dim3(WG), 0, s, n, syms, nv, llr);
-  else if (bps == 4) hipLaunchKernelGGL((k_llr<R, 4>), grid, dim3(WG), 0, s, n, syms, nv, llr);
-  else if (bps == 6) hipLaunchKernelGGL((k_llr<R, 6>), grid, dim3(WG), 0, s, n, syms, nv, llr);
-  else return (int)hipErrorInvalidValue;
-  return (int)hipGetLastError();
+  return launch_status(with_bps(bps, [&](auto Q) {
+    hipLaunchKernelGGL((k_llr<R, Q()>), grid, dim3(WG), 0, s, n, syms, nv, llr);
+  }));
 }
 
 template <class R, int BPS>
@@ -2257,11 +2164,9 @@ __global__ void k_hard(int64_t n, const cx<R>* __restrict__ syms, uint8_t* __res
 template <class R>
 int launch_hard(hipStream_t s, int bps, int64_t n, const cx<R>* syms, uint8_t* bits) {
   const dim3 grid((unsigned)((n + WG - 1) / WG));
-  if (bps == 2) hipLaunchKernelGGL((k_hard<R, 2>), grid, dim3(WG), 0, s, n, syms, bits);
-  else if (bps == 4) hipLaunchKernelGGL((k_hard<R, 4>), grid, dim3(WG), 0, s, n, syms, bits);
-  else if (bps == 6) hipLaunchKernelGGL((k_hard<R, 6>), grid, dim3(WG), 0, s, n, syms, bits);
-  else return (int)hipErrorInvalidValue;
-  return (int)hipGetLastError();
+  return launch_status(with_bps(bps, [&](auto Q) {
+    hipLaunchKernelGGL((k_hard<R, Q()>), grid, dim3(WG), 0, s, n, syms, bits);
+  }));
 }
 
 // ---------------------------------------------------------------------------

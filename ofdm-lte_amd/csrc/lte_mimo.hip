@@ -549,17 +549,13 @@ int launch_ofdm_txch_flat(hipStream_t s, const Grid& g, const MimoGrid& m, int c
       if (waves > 0x7FFFFFFF - TXMW_WAVES) return (int)hipErrorInvalidValue;
       const unsigned wb = (unsigned)((waves + TXMW_WAVES - 1) / TXMW_WAVES);
       const size_t wshm = (size_t)TXMW_WAVES * TXMW_LDS * sizeof(double);
-#define LTE_TXFW(C_, B_)                                                                                             \
-  hipLaunchKernelGGL((k_ofdm_txch_flat_w<C_, B_>), dim3(wb), dim3(64 * TXMW_WAVES), wshm, s, g, m, pw, PW, enc,      \
-                     enc_words, tx_map, reinterpret_cast<const double2*>(coef), reinterpret_cast<double2*>(y),       \
-                     reinterpret_cast<double*>(pow_part), nblk, B)
-      if (coded) {
-        if (g.bps == 2) LTE_TXFW(1, 2); else if (g.bps == 4) LTE_TXFW(1, 4); else LTE_TXFW(1, 6);
-      } else {
-        if (g.bps == 2) LTE_TXFW(0, 2); else if (g.bps == 4) LTE_TXFW(0, 4); else LTE_TXFW(0, 6);
-      }
-#undef LTE_TXFW
-      return (int)hipGetLastError();
+      return launch_status(with_bps(g.bps, [&](auto Q) {
+        with_bool(coded, [&](auto C) {
+          hipLaunchKernelGGL((k_ofdm_txch_flat_w<C(), Q()>), dim3(wb), dim3(64 * TXMW_WAVES), wshm, s, g, m, pw, PW,
+                             enc, enc_words, tx_map, reinterpret_cast<const double2*>(coef),
+                             reinterpret_cast<double2*>(y), reinterpret_cast<double*>(pow_part), nblk, B);
+        });
+      }));
     }
     return (int)hipErrorInvalidValue;
   }
@@ -567,28 +563,19 @@ int launch_ofdm_txch_flat(hipStream_t s, const Grid& g, const MimoGrid& m, int c
   const size_t enc_shm = (size_t)spw * enc_words * sizeof(uint32_t);
   const int stage_enc = coded && enc_shm <= 32768;
   const size_t shm = spw * g.N * sizeof(cx<R>) + (stage_enc ? enc_shm : 0);
-#define LTE_TXF(M_, C_, B_)                                                                                          \
-  do {                                                                                                               \
-    if (g.N == 2048 && pr)                                                                                           \
-      hipLaunchKernelGGL((k_ofdm_txch_flat<R, M_, C_, B_, 2048, true>), dim3(blocks), dim3(MWG), shm, s, g, m, pw,   \
-                         PW, enc, enc_words, tx_map, coef, y, pow_part, nblk, B, stage_enc);                         \
-    else if (g.N == 2048)                                                                                            \
-      hipLaunchKernelGGL((k_ofdm_txch_flat<R, M_, C_, B_, 2048>), dim3(blocks), dim3(MWG), shm, s, g, m, pw, PW, enc, \
-                         enc_words, tx_map, coef, y, pow_part, nblk, B, stage_enc);                                  \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_ofdm_txch_flat<R, M_, C_, B_>), dim3(blocks), dim3(MWG), shm, s, g, m, pw, PW, enc,      \
-                         enc_words, tx_map, coef, y, pow_part, nblk, B, stage_enc);                                  \
-  } while (0)
-#define LTE_TXF_BPS(M_, C_) \
-  do { if (g.bps == 2) LTE_TXF(M_, C_, 2); else if (g.bps == 4) LTE_TXF(M_, C_, 4); else LTE_TXF(M_, C_, 6); } while (0)
-  if (m.mode == MIMO_SFBC) {
-    if (coded) LTE_TXF_BPS(MIMO_SFBC, 1); else LTE_TXF_BPS(MIMO_SFBC, 0);
-  } else {
-    if (coded) LTE_TXF_BPS(MIMO_SPATIAL, 1); else LTE_TXF_BPS(MIMO_SPATIAL, 0);
-  }
-#undef LTE_TXF_BPS
-#undef LTE_TXF
-  return (int)hipGetLastError();
+  return launch_status(with_bps(g.bps, [&](auto Q) {
+    with_int_or<MIMO_SPATIAL, MIMO_SFBC>(m.mode, [&](auto M) {
+      with_bool(coded, [&](auto C) {
+        with_n<2048>(g.N, [&](auto NC) {
+          with_bool(pr, [&](auto P) {
+            constexpr bool PR = P() && NC() == 2048;   // the per-RX slots are N = 2048's (checked above)
+            hipLaunchKernelGGL((k_ofdm_txch_flat<R, M(), C(), Q(), NC(), PR>), dim3(blocks), dim3(MWG), shm, s, g, m,
+                               pw, PW, enc, enc_words, tx_map, coef, y, pow_part, nblk, B, stage_enc);
+          });
+        });
+      });
+    });
+  }));
 }
 
 // The link power of the first max_delay samples of every symbol (their taps
@@ -641,27 +628,20 @@ int launch_ofdm_tx_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int cod
   if (per_frame && !tx_mimo_frame_supported(g, coded, enc_words)) return (int)hipErrorInvalidValue;
   const bool pf = per_frame != 0;
   const int blocks = pf ? (B + spw - 1) / spw : (int)((total + spw - 1) / spw);
-#define LTE_TXM(M_, C_, B_)                                                                                          \
-  do {                                                                                                               \
-    if (g.N == 2048 && pf)                                                                                           \
-      hipLaunchKernelGGL((k_ofdm_tx_mimo<R, M_, C_, B_, 2048, true>), dim3(blocks), dim3(MWG), shm, s, g, m, pw, PW, \
-                         enc, enc_words, tx_map, x, B, stage_enc, lp);                                               \
-    else if (g.N == 2048)   /* 20 MHz: compile-time N (unrolled passes, twiddle recurrence) */                       \
-      hipLaunchKernelGGL((k_ofdm_tx_mimo<R, M_, C_, B_, 2048>), dim3(blocks), dim3(MWG), shm, s, g, m, pw, PW, enc,  \
-                         enc_words, tx_map, x, B, stage_enc, lp);                                                    \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_ofdm_tx_mimo<R, M_, C_, B_>), dim3(blocks), dim3(MWG), shm, s, g, m, pw, PW, enc,        \
-                         enc_words, tx_map, x, B, stage_enc, lp);                                                    \
-  } while (0)
-#define LTE_TXM_BPS(M_, C_) \
-  do { if (g.bps == 2) LTE_TXM(M_, C_, 2); else if (g.bps == 4) LTE_TXM(M_, C_, 4); else LTE_TXM(M_, C_, 6); } while (0)
-  if (m.mode == MIMO_SFBC) {
-    if (coded) LTE_TXM_BPS(MIMO_SFBC, 1); else LTE_TXM_BPS(MIMO_SFBC, 0);
-  } else {
-    if (coded) LTE_TXM_BPS(MIMO_SPATIAL, 1); else LTE_TXM_BPS(MIMO_SPATIAL, 0);
-  }
-#undef LTE_TXM_BPS
-#undef LTE_TXM
+  const bool matched = with_bps(g.bps, [&](auto Q) {
+    with_int_or<MIMO_SPATIAL, MIMO_SFBC>(m.mode, [&](auto M) {
+      with_bool(coded, [&](auto C) {
+        with_n<2048>(g.N, [&](auto NC) {   // 20 MHz: compile-time N (unrolled passes, twiddle recurrence)
+          with_bool(pf, [&](auto P) {
+            constexpr bool PF = P() && NC() == 2048;   // one slot per frame is N = 2048's (checked above)
+            hipLaunchKernelGGL((k_ofdm_tx_mimo<R, M(), C(), Q(), NC(), PF>), dim3(blocks), dim3(MWG), shm, s, g, m,
+                               pw, PW, enc, enc_words, tx_map, x, B, stage_enc, lp);
+          });
+        });
+      });
+    });
+  });
+  if (!matched) return (int)hipErrorInvalidValue;
   if (lp.part && lp.max_delay > 0) {
     const int e = (int)hipGetLastError();
     if (e) return e;
@@ -1349,24 +1329,21 @@ int launch_ofdm_txch_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int c
   const int stage_enc = coded && enc_shm <= 32768;
   const size_t shm = (2 * (size_t)g.N + 2 * SFX_TL + (size_t)m.num_rx * 2 * TXCH_MAXP) * sizeof(cx<R>) +
                      (stage_enc ? enc_shm : 0);
-#define LTE_SFX(C_, B_, NR_)                                                                                          \
-  do {                                                                                                                \
-    const int tpb = lp.n_paths == 4 ? LTE_SFX_TPB : MWG;                                                              \
-    auto k = lp.n_paths == 4 ? (lp.merged ? k_ofdm_txch_sfbc<R, C_, B_, NR_, 4, LTE_SFX_TPB, 2048, true>          \
-                                          : k_ofdm_txch_sfbc<R, C_, B_, NR_, 4, LTE_SFX_TPB>)                         \
-                             : (lp.merged ? k_ofdm_txch_sfbc<R, C_, B_, NR_, 0, MWG, 2048, true>                     \
-                                          : k_ofdm_txch_sfbc<R, C_, B_, NR_, 0>);                                    \
-    (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);                  \
-    hipLaunchKernelGGL(k, dim3(B), dim3(tpb), shm, s, g, m, pw, PW, enc, enc_words, tx_map, lp, y, B, stage_enc);     \
-  } while (0)
-#define LTE_SFX_NR(C_, B_) do { if (m.num_rx == 1) LTE_SFX(C_, B_, 1); else LTE_SFX(C_, B_, 2); } while (0)
-#define LTE_SFX_B(C_) \
-  do { if (g.bps == 2) LTE_SFX_NR(C_, 2); else if (g.bps == 4) LTE_SFX_NR(C_, 4); else LTE_SFX_NR(C_, 6); } while (0)
-  if (coded) LTE_SFX_B(1); else LTE_SFX_B(0);
-#undef LTE_SFX_B
-#undef LTE_SFX_NR
-#undef LTE_SFX
-  return (int)hipGetLastError();
+  return launch_status(with_bps(g.bps, [&](auto Q) {
+    with_bool(coded, [&](auto C) {
+      with_int<1, 2>(m.num_rx, [&](auto NR) {
+        with_int_or<0, 4>(lp.n_paths, [&](auto NP) {   // 4 paths at compile time, on wider blocks
+          with_bool(lp.merged, [&](auto MRG) {
+            constexpr int TPB = NP() == 4 ? LTE_SFX_TPB : MWG;
+            auto k = k_ofdm_txch_sfbc<R, C(), Q(), NR(), NP(), TPB, 2048, MRG()>;
+            (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+            hipLaunchKernelGGL(k, dim3(B), dim3(TPB), shm, s, g, m, pw, PW, enc, enc_words, tx_map, lp, y, B,
+                               stage_enc);
+          });
+        });
+      });
+    });
+  }));
 }
 
 template <class R>
@@ -1697,40 +1674,21 @@ static int launch_channel_tay(hipStream_t s, int B, int nch, int L, const MimoGr
   if (m.exact_jakes || shm > 32768 || J < 1 || J > 3 || G < 1 || G > 4 || m.num_rx % G != 0 ||
       (sel.econ && !(sizeof(R) == 8 && tay && J == 3 && channel_tay_econ(m, sym_len, fs))))
     return (int)hipErrorInvalidValue;
-#define LTE_CHT(J_, G_, T_, E_)                                                                                      \
-  do {                                                                                                               \
-    if (link_sigma)                                                                                                  \
-      hipLaunchKernelGGL((k_channel_tay<R, J_, G_, T_, true, E_>), dim3(nch * B), dim3(MWG), shm, s, L, m.num_rx,   \
-                         m.num_tx, np, m.n_cs, sym_len, delays, coef, x, y, link_sigma, fid, seed, inj_lz,          \
-                         inj_lz_stride, pow_part, nch);                                                              \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_channel_tay<R, J_, G_, T_, false, E_>), dim3(nch * B), dim3(MWG), shm, s, L, m.num_rx,  \
-                         m.num_tx, np, m.n_cs, sym_len, delays, coef, x, y, nullptr, fid, seed, nullptr, 0,         \
-                         pow_part, nch);                                                                             \
-  } while (0)
-#define LTE_CHT_G(J_, T_, E_)                                                                                        \
-  do {                                                                                                               \
-    switch (G) {                                                                                                     \
-      case 4: LTE_CHT(J_, 4, T_, E_); break;                                                                         \
-      case 3: LTE_CHT(J_, 3, T_, E_); break;                                                                         \
-      case 2: LTE_CHT(J_, 2, T_, E_); break;                                                                         \
-      default: LTE_CHT(J_, 1, T_, E_); break;                                                                        \
-    }                                                                                                                \
-  } while (0)
-#define LTE_CHT_J(T_)                                                                                                \
-  do {                                                                                                               \
-    if (J == 1) LTE_CHT_G(1, T_, false); else if (J == 2) LTE_CHT_G(2, T_, false); else LTE_CHT_G(3, T_, false);     \
-  } while (0)
-  if constexpr (sizeof(R) == 8) {   // the economised degree-4 sets (f64 Taylor path, J = 3)
-    if (sel.econ) {
-      LTE_CHT_G(3, true, true);
-      return (int)hipSuccess;
-    }
-  }
-  if (tay) LTE_CHT_J(true); else LTE_CHT_J(false);
-#undef LTE_CHT_J
-#undef LTE_CHT_G
-#undef LTE_CHT
+  with_bool(tay, [&](auto T) {   // J in 1..3, G in 1..4 (checked above)
+    with_int_or<3, 1, 2>(J, [&](auto JC) {
+      with_int_or<1, 4, 3, 2>(G, [&](auto GC) {
+        with_bool(link_sigma != nullptr, [&](auto LN) {
+          with_bool(sel.econ, [&](auto EC) {
+            // the economised degree-4 sets (f64 Taylor path, J = 3; checked above)
+            constexpr bool E = EC() && sizeof(R) == 8 && T() && JC() == 3;
+            hipLaunchKernelGGL((k_channel_tay<R, JC(), GC(), T(), LN(), E>), dim3(nch * B), dim3(MWG), shm, s, L,
+                               m.num_rx, m.num_tx, np, m.n_cs, sym_len, delays, coef, x, y, link_sigma, fid, seed,
+                               LN() ? inj_lz : nullptr, LN() ? inj_lz_stride : 0, pow_part, nch);
+          });
+        });
+      });
+    });
+  });
   return (int)hipSuccess;
 }
 
@@ -1742,7 +1700,6 @@ int launch_channel_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, 
                         int link_part_done) {
   const int sym_len = g.N + g.cp;
   if (m.num_rx > MC_MAXRX) return (int)hipErrorInvalidValue;
-  int tay_err = 0;
   const int nch = mimo_channel_nblk(g.L, sym_len);
   if (nch > nblk) return (int)hipErrorInvalidValue;   // partial buffers are sized for nblk blocks
   const R* ph = m.exact_jakes ? phases : nullptr;
@@ -1757,44 +1714,34 @@ int launch_channel_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, 
   const int jn = (sym_len + MWG - 1) / MWG;
   const int jmax = sizeof(R) == 8 ? 2 : 3;
   const int J = jn <= 1 ? 1 : jn <= 2 || jmax == 2 ? 2 : 3;
-#define LTE_CHM_EX(J_, EX_)                                                                                         \
-  do {                                                                                                             \
-    if (LTE_CHM_G2 && m.num_rx <= 2) LTE_CHM_EXG(J_, EX_, 2);                                                     \
-    else LTE_CHM_EXG(J_, EX_, MC_RXG);                                                                             \
-  } while (0)
-#define LTE_CHM_EXG(J_, EX_, G_)                                                                                    \
-  do {                                                                                                             \
-    if (link_noise) {                                                                                              \
-      if (!link_part_done)   /* else k_ofdm_tx_mimo + k_link_power_fix wrote the partials */                      \
-        hipLaunchKernelGGL((k_link_power<R, J_, EX_, G_>), dim3(nch * B, m.num_tx), dim3(MWG), 0, s, g.L,         \
-                           m.num_rx, m.num_tx, n_paths, m.n_cs, sym_len, delays, coef, ph, gains, fs, m, x,        \
-                           link_part, nch);                                                                        \
-      const int nl = B * m.num_rx * m.num_tx;                                                                      \
-      hipLaunchKernelGGL(k_link_sigma<R>, dim3((nl + 255) / 256), dim3(256), 0, s, nl, link_part, nch, g.L,        \
-                         link_sigma);                                                                              \
-    }                                                                                                              \
-    if (sel.tay)                                                                                                   \
-      tay_err = launch_channel_tay<R>(s, B, nch, g.L, m, n_paths, sym_len, fs, delays, coef, x, y, link_noise ? link_sigma : nullptr, \
-                                      fid, seed, inj_lz, inj_lz_stride, pow_part, sel);                            \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_channel_mimo<R, J_, EX_, G_>), dim3(nch * B), dim3(MWG), 0, s, g.L, m.num_rx,         \
-                         m.num_tx, n_paths, m.n_cs, sym_len, delays, coef, ph, gains, fs, m, x, y,                 \
-                         link_noise ? link_sigma : nullptr, fid, seed, inj_lz, inj_lz_stride, pow_part, nch);      \
-  } while (0)
-#define LTE_CHM(J_)                                                                                                 \
-  do {                                                                                                             \
-    if (m.exact_jakes) { LTE_CHM_EX(J_, true); break; }                                                            \
-    LTE_CHM_EX(J_, false);                                                                                         \
-  } while (0)
-  switch (J) {
-    case 1: LTE_CHM(1); break;
-    case 2: LTE_CHM(2); break;
-    default: LTE_CHM(3); break;
+  const R* sigma = link_noise ? link_sigma : nullptr;
+  // k_link_power and k_channel_mimo share their form (J, exact Jakes, receive
+  // antennas per group: 2 up to two antennas with LTE_CHM_G2, else MC_RXG) and
+  // one dispatch: instantiated alternately, as their instances are emitted
+  with_int_or<3, 1, 2>(J, [&](auto JC) {
+    with_bool(m.exact_jakes, [&](auto EX) {
+      with_int_or<MC_RXG, 2>(LTE_CHM_G2 && m.num_rx <= 2 ? 2 : MC_RXG, [&](auto GC) {
+        if (link_noise) {
+          if (!link_part_done)   // else k_ofdm_tx_mimo + k_link_power_fix wrote the partials
+            hipLaunchKernelGGL((k_link_power<R, JC(), EX(), GC()>), dim3(nch * B, m.num_tx), dim3(MWG), 0, s, g.L,
+                               m.num_rx, m.num_tx, n_paths, m.n_cs, sym_len, delays, coef, ph, gains, fs, m, x,
+                               link_part, nch);
+          const int nl = B * m.num_rx * m.num_tx;
+          hipLaunchKernelGGL(k_link_sigma<R>, dim3((nl + 255) / 256), dim3(256), 0, s, nl, link_part, nch, g.L,
+                             link_sigma);
+        }
+        if (!sel.tay)
+          hipLaunchKernelGGL((k_channel_mimo<R, JC(), EX(), GC()>), dim3(nch * B), dim3(MWG), 0, s, g.L, m.num_rx,
+                             m.num_tx, n_paths, m.n_cs, sym_len, delays, coef, ph, gains, fs, m, x, y, sigma, fid,
+                             seed, inj_lz, inj_lz_stride, pow_part, nch);
+      });
+    });
+  });
+  if (sel.tay) {
+    const int e = launch_channel_tay<R>(s, B, nch, g.L, m, n_paths, sym_len, fs, delays, coef, x, y, sigma, fid, seed,
+                                        inj_lz, inj_lz_stride, pow_part, sel);
+    if (e) return e;
   }
-#undef LTE_CHM
-#undef LTE_CHM_EX
-#undef LTE_CHM_EXG
-  if (tay_err) return tay_err;
   return (int)hipGetLastError();
 }
 
@@ -1858,13 +1805,11 @@ int launch_link_stats(hipStream_t s, const Grid& g, const MimoGrid& m, int B, in
                       R* part, int nblk, R* stats) {
   if (nblk < (g.L + MWG - 1) / MWG) return (int)hipErrorInvalidValue;
   if (m.exact_jakes && !phases) return (int)hipErrorInvalidValue;
-#define LTE_LSP(EX_)                                                                                                 \
-  hipLaunchKernelGGL((k_link_stats_part<R, EX_>), dim3(nblk * B, m.num_rx * m.num_tx), dim3(MWG), 0, s, g.L,         \
-                     m.num_rx, m.num_tx, n_paths, m.n_cs, g.N + g.cp, delays, coef, phases, gains, fs, m, x,          \
-                     link_sigma, fid, seed, inj_lz, inj_lz_stride, part, nblk)
-  if (m.exact_jakes) LTE_LSP(true);
-  else LTE_LSP(false);
-#undef LTE_LSP
+  with_bool(m.exact_jakes, [&](auto EX) {
+    hipLaunchKernelGGL((k_link_stats_part<R, EX()>), dim3(nblk * B, m.num_rx * m.num_tx), dim3(MWG), 0, s, g.L,
+                       m.num_rx, m.num_tx, n_paths, m.n_cs, g.N + g.cp, delays, coef, phases, gains, fs, m, x,
+                       link_sigma, fid, seed, inj_lz, inj_lz_stride, part, nblk);
+  });
   const int n = B * m.num_rx * m.num_tx * 4;
   hipLaunchKernelGGL(k_link_stats_fin<R>, dim3((n + 255) / 256), dim3(256), 0, s, n, part, nblk, g.L, stats);
   return (int)hipGetLastError();
@@ -1993,18 +1938,12 @@ int launch_rx_fft_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, c
   if (total > 0x7FFFFFFF - spw) return (int)hipErrorInvalidValue;
   const int blocks = (int)((total + spw - 1) / spw);
   const size_t shm = spw * (g.N + m.num_tx * m.maxP) * sizeof(cx<R>);
-  if (g.N == 2048 && h_pilots)
-    hipLaunchKernelGGL((k_rx_fft_mimo<R, 2048, true>), dim3(blocks), dim3(MWG), shm, s, g, m, B, y, npow, fid, seed,
-                       inj_z, inj_stride, Y, H);
-  else if (h_pilots)
-    hipLaunchKernelGGL((k_rx_fft_mimo<R, 0, true>), dim3(blocks), dim3(MWG), shm, s, g, m, B, y, npow, fid, seed, inj_z,
-                       inj_stride, Y, H);
-  else if (g.N == 2048)   // 20 MHz: compile-time N (unrolled passes, twiddle recurrence)
-    hipLaunchKernelGGL((k_rx_fft_mimo<R, 2048>), dim3(blocks), dim3(MWG), shm, s, g, m, B, y, npow, fid, seed, inj_z,
-                       inj_stride, Y, H);
-  else
-    hipLaunchKernelGGL((k_rx_fft_mimo<R>), dim3(blocks), dim3(MWG), shm, s, g, m, B, y, npow, fid, seed, inj_z,
-                       inj_stride, Y, H);
+  with_bool(h_pilots, [&](auto HP) {
+    with_n<2048>(g.N, [&](auto NC) {   // 20 MHz: compile-time N (unrolled passes, twiddle recurrence)
+      hipLaunchKernelGGL((k_rx_fft_mimo<R, NC(), HP()>), dim3(blocks), dim3(MWG), shm, s, g, m, B, y, npow, fid, seed,
+                         inj_z, inj_stride, Y, H);
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -2136,15 +2075,12 @@ int launch_det_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, 
   if (zo && (!coded || !nvo || (m.res & 1) || m.n_dsc > m.res)) return (int)hipErrorInvalidValue;
   const int64_t n = (int64_t)B * g.n_sym * (m.n_dsc >> 1);
   const dim3 grid((unsigned)((n + MWG - 1) / MWG));
-#define LTE_DS(C_, B_) \
-  hipLaunchKernelGGL((k_det_sfbc<R, C_, B_>), grid, dim3(MWG), 0, s, g, m, B, Y, H, snr_lin, pw, PW, n_bits, \
-                     frame_err, llr, cap_syms, cap_bits, zo, nvo)
-  if (coded) {
-    if (g.bps == 2) LTE_DS(1, 2); else if (g.bps == 4) LTE_DS(1, 4); else LTE_DS(1, 6);
-  } else {
-    if (g.bps == 2) LTE_DS(0, 2); else if (g.bps == 4) LTE_DS(0, 4); else LTE_DS(0, 6);
-  }
-#undef LTE_DS
+  with_int_or<6, 2, 4>(g.bps, [&](auto Q) {
+    with_bool(coded, [&](auto C) {
+      hipLaunchKernelGGL((k_det_sfbc<R, C(), Q()>), grid, dim3(MWG), 0, s, g, m, B, Y, H, snr_lin, pw, PW, n_bits,
+                         frame_err, llr, cap_syms, cap_bits, zo, nvo);
+    });
+  });
   return (int)hipGetLastError();
 }
 
@@ -2269,16 +2205,12 @@ int launch_rx_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, i
                    uint32_t* frame_err, cx<R>* zo, R* nvo) {
   if (!rx_sfbc_supported<R>(g, m) || (coded && (!zo || !nvo))) return (int)hipErrorInvalidValue;
   const size_t shm = ((size_t)g.N + (size_t)m.num_rx * m.num_tx * m.maxP) * sizeof(cx<R>);
-#define LTE_RS(C_, B_)                                                                                        \
-  hipLaunchKernelGGL((k_rx_sfbc<R, C_, B_>), dim3(B), dim3(MWG), shm, s, g, m, B, y, npow, fid, seed, snr_lin, pw, \
-                     PW, n_bits, frame_err, zo, nvo)
-  if (coded) {
-    if (g.bps == 2) LTE_RS(1, 2); else if (g.bps == 4) LTE_RS(1, 4); else LTE_RS(1, 6);
-  } else {
-    if (g.bps == 2) LTE_RS(0, 2); else if (g.bps == 4) LTE_RS(0, 4); else LTE_RS(0, 6);
-  }
-#undef LTE_RS
-  return (int)hipGetLastError();
+  return launch_status(with_bps(g.bps, [&](auto Q) {
+    with_bool(coded, [&](auto C) {
+      hipLaunchKernelGGL((k_rx_sfbc<R, C(), Q()>), dim3(B), dim3(MWG), shm, s, g, m, B, y, npow, fid, seed, snr_lin,
+                         pw, PW, n_bits, frame_err, zo, nvo);
+    });
+  }));
 }
 
 // ---------------------------------------------------------------------------
@@ -2601,23 +2533,17 @@ int launch_det_spatial(hipStream_t s, const Grid& g, const MimoGrid& m, int B, c
   if (stage && !det_spatial_stage_supported(m, sizeof(R) == 8, g.n_sym, B, h_pilots)) return (int)hipErrorInvalidValue;
   const bool stg = stage != 0;
   const dim3 sgrid((unsigned)((int64_t)B * g.n_sym));
-#define LTE_DSP(B_, S_)                                                                                            \
-  do {                                                                                                             \
-    if (stg)                                                                                                       \
-      hipLaunchKernelGGL((k_det_spatial<R, B_, S_, true, true>), sgrid, dim3(MWG), hshm, s, g, m, B, Y, H, nvar,   \
-                         pw, PW, n_bits, frame_err, cap_syms, cap_bits);                                           \
-    else if (h_pilots)                                                                                             \
-      hipLaunchKernelGGL((k_det_spatial<R, B_, S_, true>), grid, dim3(MWG), 0, s, g, m, B, Y, H, nvar, pw, PW,      \
-                         n_bits, frame_err, cap_syms, cap_bits);                                                   \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_det_spatial<R, B_, S_>), grid, dim3(MWG), 0, s, g, m, B, Y, H, nvar, pw, PW, n_bits,    \
-                         frame_err, cap_syms, cap_bits);                                                           \
-  } while (0)
-  const bool sic = m.det == LTE_DET_SIC;
-  if (g.bps == 2) { if (sic) LTE_DSP(2, true); else LTE_DSP(2, false); }
-  else if (g.bps == 4) { if (sic) LTE_DSP(4, true); else LTE_DSP(4, false); }
-  else { if (sic) LTE_DSP(6, true); else LTE_DSP(6, false); }
-#undef LTE_DSP
+  with_int_or<6, 2, 4>(g.bps, [&](auto Q) {
+    with_bool(m.det == LTE_DET_SIC, [&](auto SIC) {
+      with_bool(stg, [&](auto STG) {
+        with_bool(h_pilots, [&](auto P) {
+          constexpr bool HP = P() || STG();   // the staged estimates are the pilots' (checked above)
+          hipLaunchKernelGGL((k_det_spatial<R, Q(), SIC(), HP, STG()>), STG() ? sgrid : grid, dim3(MWG),
+                             STG() ? hshm : 0, s, g, m, B, Y, H, nvar, pw, PW, n_bits, frame_err, cap_syms, cap_bits);
+        });
+      });
+    });
+  });
   return (int)hipGetLastError();
 }
 

@@ -157,13 +157,10 @@ int launch_dematch_zn(hipStream_t s, const cx<R>* z, const R* nv, int n_re, int 
   const int T = n_re * bps;
   for (int k = 0; k < n_layers; ++k) {
     const int32_t* mp = rx_map + (size_t)k * T;
-    if (bps == 4)
-      hipLaunchKernelGGL((k_dematch_zn<R, 4>), grid, dim3(256), 0, s, z, nv, n_re, nd, n_nv, nv_grp, nv_sh, B, mp,
+    const int e = launch_status(with_int<4, 6>(bps, [&](auto Q) {   // (z, nv) is 16 / 64-QAM's
+      hipLaunchKernelGGL((k_dematch_zn<R, Q()>), grid, dim3(256), 0, s, z, nv, n_re, nd, n_nv, nv_grp, nv_sh, B, mp,
                          k > 0 || add0 ? 1 : 0, blk, rows, ch, g0);
-    else
-      hipLaunchKernelGGL((k_dematch_zn<R, 6>), grid, dim3(256), 0, s, z, nv, n_re, nd, n_nv, nv_grp, nv_sh, B, mp,
-                         k > 0 || add0 ? 1 : 0, blk, rows, ch, g0);
-    const int e = (int)hipGetLastError();
+    }));
     if (e) return e;
   }
   return 0;

@@ -865,19 +865,6 @@ bool tx_simo_w_supported(const Grid& g, int f64, int coded, int sc_fdm, int n_pa
          (!TXSW_HALF || (max_delay <= 64 && g.cp <= 512 && num_rx <= 4));
 }
 
-template <int BPS, int NP>
-static void tx_simo_w_go(hipStream_t s, unsigned blocks, const Grid& g, const uint32_t* pw, int PW, int B,
-                         double2* cap_syms, const TxChannelT<double>& ch) {
-  hipLaunchKernelGGL((k_ofdm_tx_simo_w<BPS, NP>), dim3(blocks), dim3(64 * TXSW_WAVES),
-                     (size_t)TXSW_WAVES * TXSW_XS * sizeof(double2), s, g, pw, PW, B, cap_syms, ch);
-}
-template <int BPS>
-static void tx_simo_w_np(hipStream_t s, unsigned blocks, const Grid& g, const uint32_t* pw, int PW, int B,
-                         double2* cap_syms, const TxChannelT<double>& ch) {
-  if (ch.n_paths == 6) tx_simo_w_go<BPS, 6>(s, blocks, g, pw, PW, B, cap_syms, ch);
-  else if (ch.n_paths == 4) tx_simo_w_go<BPS, 4>(s, blocks, g, pw, PW, B, cap_syms, ch);
-  else tx_simo_w_go<BPS, 0>(s, blocks, g, pw, PW, B, cap_syms, ch);
-}
 int launch_ofdm_tx_simo_w(hipStream_t s, const Grid& g, const uint32_t* pw, int PW, int B, double2* cap_syms,
                           const TxChannelT<double>& ch) {
   if (!tx_simo_w_supported(g, 1, 0, 0, ch.n_paths, ch.max_delay, ch.num_rx, ch.tcoef != nullptr, ch.x_out != nullptr))
@@ -885,10 +872,12 @@ int launch_ofdm_tx_simo_w(hipStream_t s, const Grid& g, const uint32_t* pw, int 
   const int64_t waves = TXSW_FRAME ? (int64_t)B : (int64_t)B * g.n_sym;
   if (waves > 0x7FFFFFFF - TXSW_WAVES) return (int)hipErrorInvalidValue;
   const unsigned blocks = (unsigned)((waves + TXSW_WAVES - 1) / TXSW_WAVES);
-  if (g.bps == 2) tx_simo_w_np<2>(s, blocks, g, pw, PW, B, cap_syms, ch);
-  else if (g.bps == 4) tx_simo_w_np<4>(s, blocks, g, pw, PW, B, cap_syms, ch);
-  else tx_simo_w_np<6>(s, blocks, g, pw, PW, B, cap_syms, ch);
-  return (int)hipGetLastError();
+  return launch_status(with_bps(g.bps, [&](auto Q) {
+    with_int_or<0, 4, 6>(ch.n_paths, [&](auto NP) {   // the ITU path counts at compile time
+      hipLaunchKernelGGL((k_ofdm_tx_simo_w<Q(), NP()>), dim3(blocks), dim3(64 * TXSW_WAVES),
+                         (size_t)TXSW_WAVES * TXSW_XS * sizeof(double2), s, g, pw, PW, B, cap_syms, ch);
+    });
+  }));
 }
 
 int launch_rx_frame_simo_w(hipStream_t s, const Grid& g, int B, int num_rx, const double2* y, int64_t y_rx_stride,
@@ -899,15 +888,11 @@ int launch_rx_frame_simo_w(hipStream_t s, const Grid& g, int B, int num_rx, cons
   const int yrow = g.Nd > SIMOW_ROW_MIN ? g.Nd : SIMOW_ROW_MIN;
   const size_t shm = ((size_t)SIMOW_WAVES * yrow + (size_t)num_rx * g.Np) * sizeof(double2) +
                      (size_t)2 * 64 * SIMOW_WAVES * sizeof(int2) + (size_t)g.Np * sizeof(double);
-#define LTE_SIMOW(BPS_)                                                                                             \
-  hipLaunchKernelGGL(k_rx_frame_simo_w<BPS_>, dim3(B), dim3(64 * SIMOW_WAVES), shm, s, g, B, num_rx, yrow, y,       \
-                     y_rx_stride, y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,    \
-                     cap_syms, cap_bits)
-  if (g.bps == 2) LTE_SIMOW(2);
-  else if (g.bps == 4) LTE_SIMOW(4);
-  else LTE_SIMOW(6);
-#undef LTE_SIMOW
-  return (int)hipGetLastError();
+  return launch_status(with_bps(g.bps, [&](auto Q) {
+    hipLaunchKernelGGL(k_rx_frame_simo_w<Q()>, dim3(B), dim3(64 * SIMOW_WAVES), shm, s, g, B, num_rx, yrow, y,
+                       y_rx_stride, y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,
+                       cap_syms, cap_bits);
+  }));
 }
 
 int launch_rx_frame_w(hipStream_t s, const Grid& g, int rayleigh, int B, const double2* y, int64_t y_frame_stride,
@@ -923,29 +908,19 @@ int launch_rx_frame_w(hipStream_t s, const Grid& g, int rayleigh, int B, const d
   return (int)hipGetLastError();
 }
 
-template <int BPS, bool STAGE>
-static int txf_w_go(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_words, const int32_t* tx_map, int B,
-                    double2* cap_syms, const TxChannelT<double>& ch) {
-  const size_t shm = (size_t)TXW_WAVES * (TXW_XS + (STAGE ? 4 * (size_t)((enc_words + 3) & ~3) : 0));
-  if (shm > 160 * 1024) return (int)hipErrorInvalidValue;
-  auto k = k_ofdm_txf_w<BPS, 4, STAGE>;
-  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-  hipLaunchKernelGGL(k, dim3((B + TXW_WAVES - 1) / TXW_WAVES), dim3(64 * TXW_WAVES), shm, s, g, enc, enc_words,
-                     tx_map, B, cap_syms, ch);
-  return (int)hipGetLastError();
-}
-
 int launch_ofdm_txf_w(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_words, const int32_t* tx_map, int B,
                       double2* cap_syms, const TxChannelT<double>& ch, int stage) {
   if (!txf_w_supported(g, 1, ch.n_paths, ch.max_delay, ch.num_rx, ch.tcoef != nullptr)) return (int)hipErrorInvalidValue;
-  if (stage) {
-    if (g.bps == 2) return txf_w_go<2, true>(s, g, enc, enc_words, tx_map, B, cap_syms, ch);
-    if (g.bps == 4) return txf_w_go<4, true>(s, g, enc, enc_words, tx_map, B, cap_syms, ch);
-    return txf_w_go<6, true>(s, g, enc, enc_words, tx_map, B, cap_syms, ch);
-  }
-  if (g.bps == 2) return txf_w_go<2, false>(s, g, enc, enc_words, tx_map, B, cap_syms, ch);
-  if (g.bps == 4) return txf_w_go<4, false>(s, g, enc, enc_words, tx_map, B, cap_syms, ch);
-  return txf_w_go<6, false>(s, g, enc, enc_words, tx_map, B, cap_syms, ch);
+  const size_t shm = (size_t)TXW_WAVES * (TXW_XS + (stage ? 4 * (size_t)((enc_words + 3) & ~3) : 0));
+  if (shm > 160 * 1024) return (int)hipErrorInvalidValue;
+  return launch_status(with_bps(g.bps, [&](auto Q) {
+    with_bool(stage, [&](auto STAGE) {
+      auto k = k_ofdm_txf_w<Q(), 4, STAGE()>;
+      (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+      hipLaunchKernelGGL(k, dim3((B + TXW_WAVES - 1) / TXW_WAVES), dim3(64 * TXW_WAVES), shm, s, g, enc, enc_words,
+                         tx_map, B, cap_syms, ch);
+    });
+  }));
 }
 
 int launch_rx_fft_mimo_w(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const double2* y, const double* npow,
