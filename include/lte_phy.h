@@ -72,6 +72,39 @@ enum {
    *     (lte_plan_create_harq: LTE_EUNSUP). */
   LTE_CHAIN_SIMO_CODED = 7
 };
+/* Chain kinds, continued (an addition to ABI 3; the same value space). */
+enum {
+  /* Coded TM4 spatial multiplexing with soft MMSE output: this library's
+   * composition (the reference has no coded spatial driver), LTE_CHAIN_CODED's
+   * coding chain around LTE_CHAIN_SPATIAL's transmitter, link and estimator.  A
+   * multi-antenna chain (num_tx 2 / 4, num_rx <= 4, rank <= min(num_tx, num_rx),
+   * precoder and detector as LTE_CHAIN_SPATIAL; desc.num_tx < 2: LTE_EINVAL).
+   *   TX: LTE_CHAIN_CODED's coding -- CRC-24A, segmentation, turbo encoding,
+   *     rate matching at rv 0 with E = 3K + 12, QAM, the T/F interleaver with
+   *     cols = Nd (padding symbols are zeros); n_sym follows from the coded
+   *     length (desc.n_sym = 0).  Each OFDM symbol's Nd interleaved QAM symbols
+   *     then go through LTE_CHAIN_SPATIAL's transmitter unchanged: layer map at
+   *     rank R onto the first ceil(Nd / R) data subcarriers, x = W layers, CRS
+   *     pilots per TX (cell t % 4).
+   *   Link, FFT, per-symbol CRS estimate, H_eff = H W: LTE_CHAIN_SPATIAL's;
+   *     injected draws (phases, link_h, noise) and Philox streams are that chain's.
+   *   Soft detector, per subcarrier, float64 in both plan precisions, s2 =
+   *     10^(-SNR/10) (float64) in the solve and in the variance:
+   *       MMSE / IRC  A = He^H He + s2 I, s = A^-1 He^H y, q_l = (A^-1)_ll,
+   *                   e_l = s2 q_l, mu_l = max(1 - e_l, 1e-6),
+   *                   z_l = s_l / mu_l (unbiased), nv_l = e_l / mu_l
+   *       ZF          A = He^H He, z = s, nv_l = s2 min((A^-1)_ll, 1e6)
+   *       MRC         (rank 1) z = conj(h) y / ||h||^2, nv = s2 min(1 / ||h||^2, 1e6)
+   *       SIC         lte_plan_create: LTE_EUNSUP (soft SIC is not built)
+   *   Then max-log LLRs of (z_l, nv_l) in RE order (layer t of subcarrier j is RE
+   *     R j + t of the symbol, dropped past Nd), T/F de-interleave, dematch,
+   *     turbo_iters iterations, desegmentation, CRC-24A.  counts, frame_errors,
+   *     frame_crc_ok and cap_bits_rx as LTE_CHAIN_CODED; cap_data_syms holds z,
+   *     cap_llr the LLRs.  lte_plan_set_early_stop applies; HARQ does not
+   *     (lte_plan_create_harq: LTE_EUNSUP).  The LLR path always
+   *     (lte_run_path: dematch=llr). */
+  LTE_CHAIN_SPATIAL_CODED = 8
+};
 /* MIMODetector.detector_type (core/mimo_detector.py:116-133); IRC == MMSE */
 enum { LTE_DET_MMSE = 0, LTE_DET_ZF = 1, LTE_DET_SIC = 2, LTE_DET_MRC = 3 };
 enum { LTE_CH_AWGN = 0, LTE_CH_RAYLEIGH = 1 }; /* core/channel.py:10-245 */

@@ -754,7 +754,11 @@ static int plan_mimo_tables(lte_plan* p) {
 // The chains that run the coding chain (encoder, dematch, turbo decoder, CRC),
 // and those of them that run_siso serves.
 static bool siso_coded(int chain) { return chain == LTE_CHAIN_CODED || chain == LTE_CHAIN_SIMO_CODED; }
-static bool chain_is_coded(int chain) { return siso_coded(chain) || chain == LTE_CHAIN_SFBC_CODED; }
+static bool chain_is_coded(int chain) {
+  return siso_coded(chain) || chain == LTE_CHAIN_SFBC_CODED || chain == LTE_CHAIN_SPATIAL_CODED;
+}
+// the TM4 chains (run_mimo, MIMO_SPATIAL): hard and soft detection
+static bool chain_is_spatial(int chain) { return chain == LTE_CHAIN_SPATIAL || chain == LTE_CHAIN_SPATIAL_CODED; }
 
 // Device workspace of the SISO / SIMO chains in precision R.  The TX signal x
 // is allocated on first use (the fused TX + channel path never writes it).
@@ -815,7 +819,7 @@ static bool alloc_mimo(lte_plan* p, bool coded) {
   bad |= c.y.alloc(B * m.num_rx * p->L) != 0;
   bad |= c.coef.alloc(B * links * (ray ? d.n_paths : 1) * m.n_cs * (p->f64 ? mimo_ncf<double>() : mimo_ncf<float>())) != 0;
   if (ray && m.exact_jakes) bad |= c.phases.alloc(B * links * d.n_paths * 16) != 0;
-  if (ray && d.chain != LTE_CHAIN_SPATIAL) {
+  if (ray && !chain_is_spatial(d.chain)) {
     bad |= c.link_part.alloc(B * links * p->nblk) != 0;
     bad |= c.link_sigma.alloc(B * links) != 0;
   }
@@ -911,11 +915,16 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
   if (d.N < 128 || d.N > 2048 || (d.N & (d.N - 1))) return fail(LTE_EUNSUP, "N must be a power of two in [128, 2048]");
   if (d.Nc <= 0 || d.Nc >= d.N || d.cp_len < 0 || d.cp_len > d.N) return fail(LTE_EINVAL, "bad Nc / cp_len");
   if (d.bps != 2 && d.bps != 4 && d.bps != 6) return fail(LTE_EINVAL, "Unsupported modulation");
-  if (d.chain < 0 || d.chain > LTE_CHAIN_SIMO_CODED) return fail(LTE_EINVAL, "bad chain");
+  if (d.chain < 0 || d.chain > LTE_CHAIN_SPATIAL_CODED) return fail(LTE_EINVAL, "bad chain");
+  // the converse of "num_tx > 1 needs a multi-antenna chain" below, for the chain added last (the
+  // older multi-antenna chains keep the refusals they had for such a descriptor)
+  if (d.chain == LTE_CHAIN_SPATIAL_CODED && d.num_tx < 2)
+    return fail(LTE_EINVAL, "bad chain for num_tx < 2: LTE_CHAIN_SPATIAL_CODED is a multi-antenna chain (2 or 4 TX)");
   if (d.channel != LTE_CH_AWGN && d.channel != LTE_CH_RAYLEIGH) return fail(LTE_EINVAL, "Tipo de canal desconocido");
   if (d.num_rx < 1 || d.num_rx > 16) return fail(LTE_EINVAL, "num_rx must be >= 1");
   const bool bf = d.chain == LTE_CHAIN_BEAMFORMING;
   // LTE_CHAIN_SIMO_CODED is a SISO-family chain (one TX, run_siso) numbered after the multi-antenna ones
+  // (LTE_CHAIN_SPATIAL_CODED, numbered after it, is a multi-antenna chain again)
   const bool mimo = d.chain >= LTE_CHAIN_SFBC && !bf && d.chain != LTE_CHAIN_SIMO_CODED;
   const int num_tx = d.num_tx > 0 ? d.num_tx : 1;
   if (!mimo && !bf && num_tx != 1) return fail(LTE_EINVAL, "num_tx > 1 needs a multi-antenna chain");
@@ -928,8 +937,8 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
     return fail(LTE_EINVAL, "Alamouti SFBC requires exactly 2 TX antennas");
   if ((d.chain == LTE_CHAIN_SFBC || d.chain == LTE_CHAIN_SFBC_CODED) && d.num_rx > 8)
     return fail(LTE_EUNSUP, "SFBC: at most 8 RX antennas");
-  const int rank = d.chain == LTE_CHAIN_SPATIAL ? (d.rank > 0 ? d.rank : num_tx) : 0;
-  if (d.chain == LTE_CHAIN_SPATIAL) {
+  const int rank = chain_is_spatial(d.chain) ? (d.rank > 0 ? d.rank : num_tx) : 0;
+  if (chain_is_spatial(d.chain)) {
     if (d.num_rx < rank)
       return fail(LTE_EINVAL, "num_rx (" + std::to_string(d.num_rx) + ") debe ser >= num_layers (" +
                                   std::to_string(rank) + ")");
@@ -937,6 +946,8 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
     if (d.detector == LTE_DET_MRC && rank != 1) return fail(LTE_EINVAL, "MRC solo soporta num_layers=1 (rank-1)");
     if ((num_tx != 2 && num_tx != 4) || d.num_rx > 4 || rank < 1 || rank > num_tx)
       return fail(LTE_EUNSUP, "spatial multiplexing on the GPU path: 2 or 4 TX, 1-4 RX, rank <= num_tx");
+    if (d.chain == LTE_CHAIN_SPATIAL_CODED && d.detector == LTE_DET_SIC)
+      return fail(LTE_EUNSUP, "the coded spatial chain has no soft SIC: MMSE, ZF or MRC");
   }
   if (d.channel == LTE_CH_RAYLEIGH && (d.n_paths < 1 || d.n_paths > LTE_MAX_PATHS))
     return fail(LTE_EINVAL, "bad n_paths");
@@ -1374,7 +1385,7 @@ static MimoPath select_mimo(const lte_plan* p, const lte_run_args* a, const Knob
   const lte_plan_desc& d = p->d;
   const Grid& g = p->grid;
   const MimoGrid& m = p->mg;
-  const bool coded = d.chain == LTE_CHAIN_SFBC_CODED, ray = d.channel == LTE_CH_RAYLEIGH, sfbc = m.mode == MIMO_SFBC;
+  const bool coded = chain_is_coded(d.chain), ray = d.channel == LTE_CH_RAYLEIGH, sfbc = m.mode == MIMO_SFBC;
   const bool link_noise = sfbc && ray;  // transmit_mimo's per-link 100 dB ChannelSimulator (core/ofdm_core.py:490-503)
   const bool inj_lz = a->link_noise && link_noise, inj_z = a->noise != nullptr;
   const int maxd = ray ? *std::max_element(d.delays, d.delays + d.n_paths) : 0;
@@ -1583,7 +1594,7 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, in
   const MimoGrid& m = p->mg;
   ChainBufs<R>& c = cbuf<R>(p);
   hipStream_t s = p->stream;
-  const bool coded = d.chain == LTE_CHAIN_SFBC_CODED;
+  const bool coded = chain_is_coded(d.chain);   // SFBC or spatial + the coding chain
   const bool ray = d.channel == LTE_CH_RAYLEIGH;
   const bool sfbc = m.mode == MIMO_SFBC;
   const bool link_noise = sfbc && ray;  // transmit_mimo's per-link 100 dB ChannelSimulator (core/ofdm_core.py:490-503)
@@ -1711,12 +1722,14 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, in
       LCHK(launch_det_sfbc<R>(s, g, m, coded ? 1 : 0, ray ? 1 : 0, B, c.Ym.p, c.H.p, c.snr_lin.p, p->pw.p, p->PW,
                               d.n_bits, p->frame_err.p, c.llr.p, cap.syms, coded ? nullptr : cap.bits,
                               zn ? zn_z<R>(p) : nullptr, zn ? zn_nv<R>(p) : nullptr));
-    else
+    else   // (coded: the soft instance -- LLRs for k_dematch; the received bits come from k_crc_count)
       LCHK(launch_det_spatial<R>(s, g, m, B, c.Ym.p, c.H.p, p->nvar.p, p->pw.p, p->PW, d.n_bits, p->frame_err.p,
-                                 cap.syms, cap.bits, h_pilots ? 1 : 0, path.det_stage ? 1 : 0));
+                                 cap.syms, coded ? nullptr : cap.bits, h_pilots ? 1 : 0, path.det_stage ? 1 : 0,
+                                 coded ? c.llr.p : nullptr));
   }
-  if (coded)   // (k_det_sfbc's noise variances are per Alamouti RE pair)
-    if (const int e = decode_blocks<R>(p, a, B, p->rx_map.p, m.res, 1, 0, zn, false, cap.bits, inj_bits)) return e;
+  if (coded)   // (k_det_sfbc's noise variances are per Alamouti RE pair; m.res = Nd for spatial)
+    if (const int e = decode_blocks<R>(p, a, B, p->rx_map.p, m.res, sfbc ? 1 : 0, 0, zn, false, cap.bits, inj_bits))
+      return e;
   // this chain's own captures; lpart / lstats live until read_back has synchronised
   if (a->cap_signal_tx)
     HIPCHK(hipMemcpyAsync(a->cap_signal_tx, c.x.p, (size_t)B * m.num_tx * p->L * sizeof(V), hipMemcpyDeviceToHost, s));
@@ -2143,7 +2156,7 @@ int lte_run_path(const lte_plan* p, const lte_run_args* a, char* buf, int len) {
       std::snprintf(ch, sizeof ch, "%s", s.ch_sep ? "k_channel_mimo" : "fused");
     n = std::snprintf(buf, len, "tx=%s lp_fuse=%d ch=%s link_merge=%d rx=%s h_pilots=%d det_stage=%d dematch=%s",
                       MIMO_TX_NAME[s.tx], s.lp_fuse, ch, s.sfbc_merge, MIMO_RX_NAME[s.rx], s.h_pilots, s.det_stage,
-                      p->d.chain != LTE_CHAIN_SFBC_CODED ? "none" : s.zn ? "zn" : "llr");
+                      !chain_is_coded(p->d.chain) ? "none" : s.zn ? "zn" : "llr");
   }
   // the decoder family is named only when it is not the default one
   if (p->early_stop && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " turbo=es");

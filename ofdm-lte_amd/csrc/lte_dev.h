@@ -158,6 +158,21 @@ __device__ __forceinline__ void soft_demap(V y, re_t<V> nv, re_t<V>* out) {
   }
 }
 
+// The BPS max-log LLRs of one RE stored at lo (RE order) as 8-B pairs (float32
+// 16-QAM: one 16-B store): the LLR output of every SISO / SIMO receiver and
+// of the soft spatial detector.
+template <class R, int BPS>
+__device__ __forceinline__ void store_llrs(R* lo, cx<R> z, R nv) {
+  R o[BPS];
+  soft_demap<BPS>(z, nv, o);
+  if constexpr (BPS == 4 && sizeof(R) == 4) {
+    *reinterpret_cast<float4*>(lo) = make_float4(o[0], o[1], o[2], o[3]);
+  } else {
+#pragma unroll
+    for (int m = 0; m < BPS; m += 2) *reinterpret_cast<cx<R>*>(lo + m) = mkc(o[m], o[m + 1]);
+  }
+}
+
 // y / h (lte_receiver.py:154-180 divides by H + 1e-6): multiply by the conjugate
 // over |h|^2; f32 relative error a few ulp (no over/underflow at these magnitudes).
 __device__ __forceinline__ float2 zf_div(float2 y, float2 h) {

@@ -475,10 +475,13 @@ template <class R>
 int launch_det_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, int rayleigh, int B, const cx<R>* Y,
                     const cx<R>* H, const R* snr_lin, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
                     R* llr, cx<R>* cap_syms, uint8_t* cap_bits, cx<R>* zo = nullptr, R* nvo = nullptr);
+// llr set (LTE_CHAIN_SPATIAL_CODED; MMSE / ZF / MRC): the soft detector -- cap_syms
+// gets the unbiased estimates, llr [B][n_sym * res][bps] the max-log LLRs in RE
+// order; frame_err and cap_bits are not written
 template <class R>
 int launch_det_spatial(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const cx<R>* Y, const cx<R>* H,
                        const double* nvar, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                       cx<R>* cap_syms, uint8_t* cap_bits, int h_pilots, int stage);
+                       cx<R>* cap_syms, uint8_t* cap_bits, int h_pilots, int stage, R* llr = nullptr);
 bool det_spatial_stage_supported(const MimoGrid& m, int f64, int n_sym, int B, int h_pilots);
 // SFBCAlamouti.encode (decode = 0: a = symbols -> o0 = TX0, o1 = TX1) / .decode
 // (decode = 1: a = rx, h0 / h1 the per-SC estimates -> o0), float64 [n] complex, n even

@@ -1205,19 +1205,7 @@ __device__ __forceinline__ re_t<V> abs2_ref(V h) {
 // ---------------------------------------------------------------------------
 // Hard decision / soft demap.  Natural-binary QAM, I-level-major index
 // (modulator.py:28-59, Q9): bits = [I-level bits | Q-level bits], MSB first.
-// The BPS max-log LLRs of one RE stored at lo (RE order) as 8-B pairs (float32
-// 16-QAM: one 16-B store): the LLR output of every SISO / SIMO receiver.
-template <class R, int BPS>
-__device__ __forceinline__ void store_llrs(R* lo, cx<R> z, R nv) {
-  R o[BPS];
-  soft_demap<BPS>(z, nv, o);
-  if constexpr (BPS == 4 && sizeof(R) == 4) {
-    *reinterpret_cast<float4*>(lo) = make_float4(o[0], o[1], o[2], o[3]);
-  } else {
-#pragma unroll
-    for (int m = 0; m < BPS; m += 2) *reinterpret_cast<cx<R>*>(lo + m) = mkc(o[m], o[m + 1]);
-  }
-}
+// (store_llrs, the LLR output of every receiver: lte_dev.h)
 
 // ---------------------------------------------------------------------------
 // Data path: one slot per (frame, OFDM symbol).  Per RX: CP-remove + noise +

@@ -19,7 +19,8 @@
 //                 on estimation symbols LS at each TX's pilot subset + linear
 //                 interpolation (MIMOChannelEstimatorPeriodic); data SCs to HBM
 //             DET SFBC combine averaged over RX -> hard bits / LLRs, or a
-//                 float64 MMSE / ZF / SIC / MRC per subcarrier -> hard bits.
+//                 float64 MMSE / ZF / SIC / MRC per subcarrier -> hard bits, or
+//                 (coded spatial chain) the soft MMSE / ZF / MRC -> LLRs.
 #include "lte_common.h"
 #include "lte_internal.h"
 #include "lte_dev.h"
@@ -2242,8 +2243,13 @@ constexpr int DMAX = 4;   // num_rx, rank <= 4 on the GPU path
 
 // Solve (He_m^H He_m + s2 I) s = He_m^H y over the columns with mask bit set
 // (others -> 0) by Cholesky; s2 = 0 gives the ZF normal equations.
-__device__ __forceinline__ void masked_solve(const dc (&He)[DMAX][DMAX], const dc (&y)[DMAX], int mask, double s2,
-                                             dc (&sv)[DMAX]) {
+// DIAG (the soft detector): qd[l] = (A^-1)_ll of the matrix A it factored, from
+// the triangular inverse of the factor, A^-1 = L^-H L^-1 so (A^-1)_ll =
+// sum_{k >= l} |(L^-1)_kl|^2 -- unrolled in registers like the solve.  A
+// masked-out column has the unit diagonal: qd = 1 there.
+template <bool DIAG>
+__device__ __forceinline__ void masked_solve_t(const dc (&He)[DMAX][DMAX], const dc (&y)[DMAX], int mask, double s2,
+                                               dc (&sv)[DMAX], double (&qd)[DMAX]) {
   dc A[DMAX][DMAX], rhs[DMAX];
 #pragma unroll
   for (int a = 0; a < DMAX; ++a) {
@@ -2304,6 +2310,28 @@ __device__ __forceinline__ void masked_solve(const dc (&He)[DMAX][DMAX], const d
     for (int k = i + 1; k < DMAX; ++k) v = dsub(v, dmulc(sv[k], Lm[k][i]));  // conj(L[k][i]) s[k]
     sv[i] = ((mask >> i) & 1) ? dc{v.x / ld[i], v.y / ld[i]} : dc{0.0, 0.0};
   }
+  if constexpr (DIAG) {
+    dc Li[DMAX][DMAX];   // L^-1, lower triangular: column k by forward substitution on e_k
+#pragma unroll
+    for (int k = 0; k < DMAX; ++k) {
+      Li[k][k] = {1.0 / ld[k], 0.0};
+      double q = Li[k][k].x * Li[k][k].x;
+#pragma unroll
+      for (int i = k + 1; i < DMAX; ++i) {
+        dc v = {0.0, 0.0};
+#pragma unroll
+        for (int j = k; j < i; ++j) v = dsub(v, dmul(Lm[i][j], Li[j][k]));
+        Li[i][k] = {v.x / ld[i], v.y / ld[i]};
+        q += Li[i][k].x * Li[i][k].x + Li[i][k].y * Li[i][k].y;
+      }
+      qd[k] = q;
+    }
+  }
+}
+__device__ __forceinline__ void masked_solve(const dc (&He)[DMAX][DMAX], const dc (&y)[DMAX], int mask, double s2,
+                                             dc (&sv)[DMAX]) {
+  double qd[DMAX];
+  masked_solve_t<false>(He, y, mask, s2, sv, qd);
 }
 
 // nearest constellation point in float64 (QAMModulator constellation,
@@ -2404,6 +2432,43 @@ __device__ __forceinline__ void detect_sc(const dc (&He)[DMAX][DMAX], const dc (
     if (l >= R) sv[l] = {0.0, 0.0};
 }
 
+// One subcarrier of the soft detector (LTE_CHAIN_SPATIAL_CODED, include/lte_phy.h):
+// the unbiased estimate z_l and its error variance nv_l per layer, s2 the nominal
+// noise variance of the solve.
+//   MMSE / IRC  A = He^H He + s2 I, q_l = (A^-1)_ll, e_l = s2 q_l,
+//               mu_l = max(1 - e_l, 1e-6), z_l = s_l / mu_l, nv_l = e_l / mu_l
+//   ZF          A = He^H He, z = s, nv_l = s2 min((A^-1)_ll, 1e6)
+//   MRC         z = conj(h) y / ||h||^2, nv = s2 min(1 / ||h||^2, 1e6)
+__device__ __forceinline__ void detect_soft_sc(const dc (&He)[DMAX][DMAX], const dc (&y)[DMAX], int R, int det,
+                                               double s2, dc (&z)[DMAX], double (&nv)[DMAX]) {
+  if (det == LTE_DET_MRC) {   // detect_sc's sums
+    double n2 = 0.0;
+    dc acc = {0.0, 0.0};
+#pragma unroll
+    for (int r = 0; r < DMAX; ++r) {
+      n2 += He[r][0].x * He[r][0].x + He[r][0].y * He[r][0].y;
+      const dc p = dmulc(y[r], He[r][0]);
+      acc.x += p.x; acc.y += p.y;
+    }
+#pragma unroll
+    for (int l = 0; l < DMAX; ++l) { z[l] = {0.0, 0.0}; nv[l] = s2; }
+    z[0] = {acc.x / n2, acc.y / n2};
+    nv[0] = s2 * fmin(1.0 / n2, 1e6);
+    return;
+  }
+  const bool zf = det == LTE_DET_ZF;
+  dc sv[DMAX];
+  double q[DMAX];
+  masked_solve_t<true>(He, y, (1 << R) - 1, zf ? 0.0 : s2, sv, q);
+#pragma unroll
+  for (int l = 0; l < DMAX; ++l) {
+    const double e = s2 * q[l];
+    const double mu = zf ? 1.0 : fmax(1.0 - e, 1e-6);
+    z[l] = zf ? sv[l] : dc{sv[l].x / mu, sv[l].y / mu};
+    nv[l] = zf ? s2 * fmin(q[l], 1e6) : e / mu;
+  }
+}
+
 #ifndef LTE_DSP_WAVES
 #define LTE_DSP_WAVES 4
 #endif
@@ -2417,15 +2482,28 @@ __device__ __forceinline__ void detect_sc(const dc (&He)[DMAX][DMAX], const dc (
 #ifndef LTE_DSP_STG_WAVES   // the staged form's register budget (waves per SIMD)
 #define LTE_DSP_STG_WAVES 3
 #endif
-template <class R, int BPS, bool SIC_ON, bool HPI = false, bool STG = false>
-__global__ __launch_bounds__(MWG) __attribute__((amdgpu_waves_per_eu(SIC_ON ? 1 : (STG ? LTE_DSP_STG_WAVES : LTE_DSP_WAVES))))
+// SOFT (LTE_CHAIN_SPATIAL_CODED): detect_soft_sc instead of the hard slicer --
+// each layer's unbiased estimate (cap_syms) and the max-log LLRs of (z_l, nv_l)
+// in the plan's type at llr [b][n_sym * res][BPS], RE order; no bit errors
+// here (k_crc_count counts the decoded ones).  Its register budget is
+// LTE_DSP_SOFT_WAVES / LTE_DSP_SOFT_STG_WAVES waves per SIMD.
+#ifndef LTE_DSP_SOFT_WAVES
+#define LTE_DSP_SOFT_WAVES 3
+#endif
+#ifndef LTE_DSP_SOFT_STG_WAVES
+#define LTE_DSP_SOFT_STG_WAVES 3
+#endif
+template <class R, int BPS, bool SIC_ON, bool HPI = false, bool STG = false, bool SOFT = false>
+__global__ __launch_bounds__(MWG) __attribute__((amdgpu_waves_per_eu(
+    SIC_ON ? 1 : SOFT ? (STG ? LTE_DSP_SOFT_STG_WAVES : LTE_DSP_SOFT_WAVES) : (STG ? LTE_DSP_STG_WAVES : LTE_DSP_WAVES))))
 void k_det_spatial(Grid g, MimoGrid m, int B, const cx<R>* __restrict__ Y,
                                                      const cx<R>* __restrict__ H, const double* __restrict__ nvar,
                                                      const uint32_t* __restrict__ pw, int PW, int n_bits,
                                                      uint32_t* __restrict__ frame_err, cx<R>* __restrict__ cap_syms,
-                                                     uint8_t* __restrict__ cap_bits) {
+                                                     uint8_t* __restrict__ cap_bits, R* __restrict__ llr) {
   using V = cx<R>;
   static_assert(!STG || HPI, "staging is of the pilot estimates");
+  static_assert(!SOFT || !SIC_ON, "soft SIC is not built");
   const int NR = m.num_rx, NT = m.num_tx, R_ = m.rank;
   const int64_t per = (int64_t)g.n_sym * m.n_dsc;
   V* hs = mimo_lds<V>();   // STG: [NR][NT][maxP] this symbol's pilot estimates
@@ -2488,6 +2566,23 @@ void k_det_spatial(Grid g, MimoGrid m, int B, const cx<R>* __restrict__ Y,
         if (c < R_) He[r][c] = dadd(He[r][c], dmul(h, dc{m.W[(t * DMAX + c) * 2], m.W[(t * DMAX + c) * 2 + 1]}));
     }
   }
+  if constexpr (SOFT) {
+    dc zs[DMAX];
+    double nvl[DMAX];
+    detect_soft_sc(He, yv, R_, m.det, nvar[b], zs, nvl);
+#pragma unroll
+    for (int t = 0; t < DMAX; ++t) {
+      const int qi = R_ * j + t;
+      if (t >= R_ || qi >= m.res) break;
+      const V z = mkc((R)zs[t].x, (R)zs[t].y);
+      const size_t re = (size_t)b * g.n_sym * m.res + (size_t)l * m.res + qi;
+      if (act) {
+        if (cap_syms) cap_syms[re] = z;
+        store_llrs<R, BPS>(llr + re * BPS, z, (R)nvl[t]);
+      }
+    }
+    continue;
+  }
   dc sv[DMAX];
   detect_sc<SIC_ON>(He, yv, R_, m.det, nvar[b], BPS, sv);
   const uint32_t* fb = pw + (size_t)b * PW;
@@ -2522,10 +2617,12 @@ bool det_spatial_stage_supported(const MimoGrid& m, int f64, int n_sym, int B, i
 template <class R>
 int launch_det_spatial(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const cx<R>* Y, const cx<R>* H,
                        const double* nvar, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                       cx<R>* cap_syms, uint8_t* cap_bits, int h_pilots, int stage) {
+                       cx<R>* cap_syms, uint8_t* cap_bits, int h_pilots, int stage, R* llr) {
   if (m.num_tx < 1 || m.num_tx > DMAX || m.num_rx < 1 || m.num_rx > DMAX || m.rank < 1 || m.rank > m.num_rx ||
       m.rank > m.num_tx || !m.W)
     return (int)hipErrorInvalidValue;
+  // llr set: the soft detector (linear detectors only)
+  if (llr && m.det == LTE_DET_SIC) return (int)hipErrorInvalidValue;
   const int64_t n = (int64_t)B * g.n_sym * m.n_dsc;
   const dim3 grid((unsigned)((n + MWG - 1) / MWG));
   // the pilot estimates staged per (frame, symbol) (stage = 0: gathered per RE)
@@ -2534,12 +2631,13 @@ int launch_det_spatial(hipStream_t s, const Grid& g, const MimoGrid& m, int B, c
   const bool stg = stage != 0;
   const dim3 sgrid((unsigned)((int64_t)B * g.n_sym));
   with_int_or<6, 2, 4>(g.bps, [&](auto Q) {
-    with_bool(m.det == LTE_DET_SIC, [&](auto SIC) {
+    with_int_or<0, 1, 2>(llr ? 2 : m.det == LTE_DET_SIC ? 1 : 0, [&](auto K) {   // linear / SIC / soft
       with_bool(stg, [&](auto STG) {
         with_bool(h_pilots, [&](auto P) {
           constexpr bool HP = P() || STG();   // the staged estimates are the pilots' (checked above)
-          hipLaunchKernelGGL((k_det_spatial<R, Q(), SIC(), HP, STG()>), STG() ? sgrid : grid, dim3(MWG),
-                             STG() ? hshm : 0, s, g, m, B, Y, H, nvar, pw, PW, n_bits, frame_err, cap_syms, cap_bits);
+          hipLaunchKernelGGL((k_det_spatial<R, Q(), K() == 1, HP, STG(), K() == 2>), STG() ? sgrid : grid, dim3(MWG),
+                             STG() ? hshm : 0, s, g, m, B, Y, H, nvar, pw, PW, n_bits, frame_err, cap_syms, cap_bits,
+                             llr);
         });
       });
     });
@@ -2661,7 +2759,8 @@ int launch_det_stage(hipStream_t s, int det, int NR, int NT, int R, int bps, int
                                   const cx<R>*, const R*, const uint32_t*, int, int, uint32_t*, R*, cx<R>*,        \
                                   uint8_t*, cx<R>*, R*);                                                           \
   template int launch_det_spatial<R>(hipStream_t, const Grid&, const MimoGrid&, int, const cx<R>*, const cx<R>*,   \
-                                     const double*, const uint32_t*, int, int, uint32_t*, cx<R>*, uint8_t*, int, int);
+                                     const double*, const uint32_t*, int, int, uint32_t*, cx<R>*, uint8_t*, int, int, \
+                                     R*);
 LTE_MIMO_INST(float)
 LTE_MIMO_INST(double)
 #undef LTE_MIMO_INST

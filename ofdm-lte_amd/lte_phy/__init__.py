@@ -8,7 +8,7 @@ decoder run as hand-written gfx950 HIP kernels in liblte_hip.so.
 from .config import (CP_VALUES, ITU_CHANNEL_MODELS, LTE_PROFILES, MODULATION_SCHEMES, SUBCARRIER_SPACING,
                      LTEConfig)
 from .ofdm_core import (ChannelSimulator, OFDMChannel, OFDMReceiver, OFDMSimulator, OFDMTransmitter,
-                        simulate_spatial_multiplexing)
+                        simulate_spatial_multiplexing, simulate_spatial_multiplexing_coded)
 from .ofdm_module import OFDMModule
 from . import channel_coding
 from .tm4 import LTECodebook, LayerMapper, MIMODetector, RankAdaptation
@@ -26,7 +26,8 @@ from .mimo_channel_estimator_periodic import MIMOChannelEstimatorPeriodic
 
 __version__ = '0.1.0'
 __all__ = ['LTEConfig', 'OFDMModule', 'OFDMSimulator', 'OFDMTransmitter', 'OFDMReceiver', 'OFDMChannel',
-           'ChannelSimulator', 'simulate_spatial_multiplexing', 'channel_coding', 'LTECodebook', 'LayerMapper',
+           'ChannelSimulator', 'simulate_spatial_multiplexing', 'simulate_spatial_multiplexing_coded',
+           'channel_coding', 'LTECodebook', 'LayerMapper',
            'MIMODetector', 'RankAdaptation', 'BeamformingPrecoder', 'AdaptiveBeamforming', 'CSIFeedback',
            'ImageProcessor', 'SFBCAlamouti', 'SFBCResourceMapper', 'MODULATION_SCHEMES', 'ITU_CHANNEL_MODELS',
            'LTE_PROFILES', 'CP_VALUES', 'SUBCARRIER_SPACING',

@@ -19,6 +19,20 @@ from . import _capi as C
 # SIMO chain decodes but is a SISO-family chain (one TX, the SISO capture shapes)
 CODED_CHAINS = (C.CHAIN_CODED, C.CHAIN_SFBC_CODED, C.CHAIN_SIMO_CODED)
 MIMO_CHAINS = (C.CHAIN_SFBC, C.CHAIN_SFBC_CODED, C.CHAIN_SPATIAL)
+# The coded TM4 chain is both coded and multi-antenna.  It stands in a tuple of
+# its own: tests/test_simo_coded_host.py holds the two above to the chains that
+# existed with the coded SIMO chain.
+CODED_MIMO_CHAINS = (C.CHAIN_SPATIAL_CODED,)
+
+
+def chain_is_coded(chain):
+    """Plan.coded: the chain runs the coding chain (encoder, dematch, turbo, CRC)."""
+    return chain in CODED_CHAINS or chain in CODED_MIMO_CHAINS
+
+
+def chain_is_mimo(chain):
+    """Plan.mimo: a multi-antenna chain (run_mimo, the multi-antenna capture shapes)."""
+    return chain in MIMO_CHAINS or chain in CODED_MIMO_CHAINS
 
 
 class RunResult(dict):
@@ -91,9 +105,9 @@ class Plan:
         self.num_rx, self.N, self.bps, self.n_bits, self.max_frames = num_rx, N, bps, int(n_bits), int(max_frames)
         self.chain = chain
         self.num_tx = int(num_tx)
-        self.coded = chain in CODED_CHAINS
+        self.coded = chain_is_coded(chain)
         self.bf = chain == C.CHAIN_BEAMFORMING
-        self.mimo = chain in MIMO_CHAINS
+        self.mimo = chain_is_mimo(chain)
         sfbc = chain in (C.CHAIN_SFBC, C.CHAIN_SFBC_CODED)
         # multi-antenna geometry (lte_capi.hip lte_plan_create): REs per OFDM symbol,
         # data SCs carrying data, channel estimates per frame

@@ -860,15 +860,20 @@ class OFDMSimulator:
         CN(0, 1) per frame; `beamforming` overrides {'num_tx': 4, 'num_rx': 1,
         'update_mode': 'adaptive'}.
 
-        early_stop=True (coded, mimo None or 'sfbc'): the turbo decoder stops each
+        mimo='spatial' with coded=True: the coded TM4 chain (LTE_CHAIN_SPATIAL_CODED,
+        include/lte_phy.h: config 2's coding around config 5's link with the soft
+        MMSE / ZF / MRC detector; n_bits defaults to 27760; detector 'SIC' raises
+        NotImplementedError: soft SIC is not built).
+
+        early_stop=True (coded, mimo None, 'sfbc' or 'spatial'): the turbo decoder stops each
         code block at the first iteration n* in 1..turbo_iters whose decisions
         pass the block's CRC-24 (turbo_iters if none does) and returns those
         decisions -- not always the ones turbo_iters iterations give.  The result
         then also holds 'turbo_iters_hist' (uint64 [S, turbo_iters + 1]: this
         rank's code blocks by n* per SNR point; all-reduce it like `counts`) and
         'turbo_iters_mean' [S]."""
-        if early_stop and not (coded and mimo in (None, 'sfbc')):
-            raise ValueError("early_stop needs a coded chain (coded=True with mimo=None or mimo='sfbc'): "
+        if early_stop and not (coded and mimo in (None, 'sfbc', 'spatial')):
+            raise ValueError("early_stop needs a coded chain (coded=True with mimo=None, 'sfbc' or 'spatial'): "
                              "nothing is decoded here")
         snrs = np.atleast_1d(np.asarray(snr_range, dtype=np.float64))
         S, T = len(snrs), int(num_trials)
@@ -884,19 +889,20 @@ class OFDMSimulator:
                 plan = self._sfbc_plan(int(np.ceil(nb / (res * cfg.bits_per_symbol))), nb, num_rx,
                                        max_frames=frames_per_call)
         elif mimo == 'spatial':
-            if coded:
-                raise NotImplementedError("config 5 is uncoded MMSE detection")
-            nb = int(n_bits or SLOT_SIZE * self.Nd * cfg.bits_per_symbol)
+            nb = int(n_bits or (27760 if coded else SLOT_SIZE * self.Nd * cfg.bits_per_symbol))
             ch = self.channels[0]
             ctype = 'rayleigh_mp' if ch.kind == C.CH_RAYLEIGH else 'awgn'
             from .tm4 import DETECTORS, LTECodebook
             sp = {'num_tx': 4, 'num_rx': 4, 'rank': 4, 'detector': 'MMSE', 'pmi': 0}
             sp.update(spatial or {})
+            if coded and sp['detector'].upper() == 'SIC':
+                raise NotImplementedError("the coded spatial chain has no soft SIC detector: MMSE, IRC, ZF or MRC")
             W = LTECodebook(sp['num_tx'], transmission_mode='TM4', rank=sp['rank']).get_precoder(sp['pmi'])
             plan = _spatial_plan(cfg, ctype, ch.profile, velocity_kmh, frequency_ghz,
-                                 int(np.ceil(nb / (self.Nd * cfg.bits_per_symbol))), nb, frames_per_call,
-                                 num_tx=sp['num_tx'], num_rx=sp['num_rx'], rank=sp['rank'],
-                                 detector=DETECTORS[sp['detector'].upper()], W=W, precision=self.precision)[0]
+                                 0 if coded else int(np.ceil(nb / (self.Nd * cfg.bits_per_symbol))), nb,
+                                 frames_per_call, num_tx=sp['num_tx'], num_rx=sp['num_rx'], rank=sp['rank'],
+                                 detector=DETECTORS[sp['detector'].upper()], W=W, precision=self.precision,
+                                 coded=coded, turbo_iters=turbo_iters, early_stop=early_stop)[0]
         elif mimo == 'beamforming':
             from .beamforming import bf_plan
             bfo = {'num_tx': 4, 'num_rx': 1, 'update_mode': 'adaptive'}
@@ -999,7 +1005,8 @@ def _harq_grid(sim, snr_range, num_trials, seed, n_bits, coded_bits, max_tx, rv_
 
 
 def _spatial_plan(config, channel_type, itu_profile, velocity_kmh, frequency_ghz, n_sym, n_bits, max_frames=1,
-                  num_tx=4, num_rx=4, rank=4, detector=C.DET_MMSE, W=None, precision=None):
+                  num_tx=4, num_rx=4, rank=4, detector=C.DET_MMSE, W=None, precision=None, coded=False,
+                  turbo_iters=8, early_stop=False):
     ch = {'awgn': C.CH_AWGN, 'rayleigh_mp': C.CH_RAYLEIGH}.get(channel_type)
     if ch is None:
         raise ValueError(f"Tipo de canal desconocido: {channel_type}")
@@ -1013,43 +1020,21 @@ def _spatial_plan(config, channel_type, itu_profile, velocity_kmh, frequency_ghz
     if W is None:
         W = np.eye(num_tx, dtype=complex)[:, :rank]
     Wt = tuple(complex(v) for v in np.asarray(W, dtype=complex).ravel())
+    # coded: LTE_CHAIN_SPATIAL_CODED (n_sym 0: it follows from the coded length)
+    kw = dict(chain=C.CHAIN_SPATIAL_CODED, turbo_iters=int(turbo_iters), early_stop=early_stop) if coded else \
+        dict(chain=C.CHAIN_SPATIAL)
     return get_plan(N=config.N, Nc=config.Nc, cp_len=config.cp_length, bps=config.bits_per_symbol, n_sym=n_sym,
-                    chain=C.CHAIN_SPATIAL, channel=ch, num_rx=num_rx, num_tx=num_tx, delays=tuple(delays),
+                    channel=ch, num_rx=num_rx, num_tx=num_tx, delays=tuple(delays),
                     gains=tuple(gains), fD=fD, fs=config.fs, n_bits=n_bits, max_frames=max_frames, rank=rank,
-                    detector=detector, precoder=Wt, precision=precision), gains, fD
+                    detector=detector, precoder=Wt, precision=precision, **kw), gains, fD
 
 
-def simulate_spatial_multiplexing(bits, num_tx=4, num_rx=2, rank='adaptive', detector_type='MMSE',
-                                  modulation='64-QAM', snr_db=15, config=None, channel_type='awgn',
-                                  itu_profile='Pedestrian_A', velocity_kmh=3, frequency_ghz=2.0,
-                                  enable_csi_feedback=True, coherence_time_symbols=None, enable_parallel=False,
-                                  codebook_type='TM4', *, precision: Optional[str] = None):
-    """simulate_spatial_multiplexing (core/ofdm_core.py:2489-2815): TM4 with
-    2 / 4 TX, 1-4 RX, rank 1-4 -- one GPU call.  Host: H_initial (:2573-2574,
-    drawn even at fixed rank) -> RankAdaptation.get_feedback on it for
-    rank='adaptive' with CSI (RI / PMI / W, core/rank_adaptation.py:212-265),
-    else the TM4 codebook's PMI 0 of the given rank (min(tx, rx) for
-    'adaptive' without CSI).  GPU: QAM -> layers (first ceil(Nd/rank) data
-    SCs, Q20) -> x = W layers -> CRS pilots per TX (cell tx % 4) -> IFFT/CP
-    -> transmit_spatial_multiplexing -> FFT -> CRS estimate per symbol ->
-    H_eff = H W -> MMSE / IRC / ZF / SIC / MRC with the nominal sigma^2 =
-    10^(-SNR/10) -> layer demap -> hard bits.  Global-RNG consumption as the
-    reference: H_initial -> TX pilot reseeds per symbol and TX -> channel draws
-    (core/channel.py:397-493: rayleigh_mp per link 16 phases per path for
-    filter() and 16 per path for impulse_response(); 'awgn' per link h ~
-    CN(0,1); then noise per RX) -> RX pilot reseeds."""
+def _sm_feedback(num_tx, num_rx, rank, detector_type, snr_db, enable_csi_feedback):
+    """simulate_spatial_multiplexing's host front (core/ofdm_core.py:2573-2590): the
+    H_initial draw (always), RankAdaptation.get_feedback on it for rank='adaptive'
+    with CSI, else the TM4 codebook's PMI 0 -> (rank, pmi, W, LTE_DET_*)."""
     from .tm4 import DETECTORS, LTECodebook, RankAdaptation
-    bits = np.asarray(bits)
-    if bits.size == 0:
-        raise ValueError("Bits array cannot be empty")
     det = DETECTORS.get(str(detector_type).upper())
-    if config is None:
-        config = LTEConfig(modulation=modulation)
-    n0 = len(bits)
-    grid = ResourceGrid(config.N, config.Nc)
-    Nd = len(grid._data)
-    bpo = Nd * config.bits_per_symbol
-    n_sym = int(np.ceil(n0 / bpo))
     H_initial = (np.random.randn(num_rx, num_tx) + 1j * np.random.randn(num_rx, num_tx)) / np.sqrt(2 * num_tx)
     if rank == 'adaptive' and enable_csi_feedback:
         fb = RankAdaptation(num_tx, num_rx, snr_db=snr_db).get_feedback(H_initial)
@@ -1064,11 +1049,15 @@ def simulate_spatial_multiplexing(bits, num_tx=4, num_rx=2, rank='adaptive', det
         raise ValueError(f"Detector '{detector_type}' no soportado")
     if det == C.DET_MRC and rank_used != 1:
         raise ValueError("MRC solo soporta num_layers=1 (rank-1)")
-    plan, gains, fD = _spatial_plan(config, channel_type, itu_profile, velocity_kmh, frequency_ghz, n_sym, n0,
-                                    num_tx=num_tx, num_rx=num_rx, rank=rank_used, detector=det, W=W,
-                                    precision=precision)
+    return rank_used, pmi_used, W, det
+
+
+def _sm_draws(plan, grid, num_tx, num_rx, ray):
+    """The global-RNG draws of one transmit_spatial_multiplexing frame of plan.L
+    samples, in the reference's order: TX pilot reseeds, per link the filter's
+    and the impulse response's 16 phases per path (rayleigh_mp) or h ~ CN(0,1)
+    (awgn), the noise per RX, RX pilot reseeds -> (phases, ir phases, link_h, z)."""
     L = plan.L
-    ray = channel_type == 'rayleigh_mp'
     step = num_tx if num_tx <= 4 else 4
     pidx = [grid._pilot[t % step::step] for t in range(num_tx)]
     for t in range(num_tx):
@@ -1093,10 +1082,13 @@ def simulate_spatial_multiplexing(bits, num_tx=4, num_rx=2, rank='adaptive', det
         z[r, 1] = np.random.normal(0, 1.0, L)
     for t in range(num_tx):
         _reseed_pilots(t % 4, len(pidx[t]))
-    out = plan.run([snr_db], bits=(bits & 1).astype(np.uint8)[None], phases=ph[None] if ray else None,
-                   noise=z[None], link_h=None if ray else lh[None], capture=('bits_rx', 'data_syms'))
-    brx = out['bits_rx'][0].astype(np.int64)
-    err = int(np.sum(bits != brx))
+    return ph, ir, lh, z
+
+
+def _sm_channel_matrix(ray, gains, fD, ir, lh):
+    """transmit_spatial_multiplexing's channel_matrix: the first impulse-response
+    tap per link (rayleigh_mp) or the link's h (awgn)."""
+    num_rx, num_tx = lh.shape[:2]
     Hm = np.zeros((num_rx, num_tx), dtype=complex)
     for r in range(num_rx):
         for t in range(num_tx):
@@ -1107,9 +1099,115 @@ def simulate_spatial_multiplexing(bits, num_tx=4, num_rx=2, rank='adaptive', det
                 Hm[r, t] = gains[0] * (h * np.sqrt(2 / 16))[0]
             else:
                 Hm[r, t] = lh[r, t, 0] + 1j * lh[r, t, 1]
+    return Hm
+
+
+def simulate_spatial_multiplexing(bits, num_tx=4, num_rx=2, rank='adaptive', detector_type='MMSE',
+                                  modulation='64-QAM', snr_db=15, config=None, channel_type='awgn',
+                                  itu_profile='Pedestrian_A', velocity_kmh=3, frequency_ghz=2.0,
+                                  enable_csi_feedback=True, coherence_time_symbols=None, enable_parallel=False,
+                                  codebook_type='TM4', *, precision: Optional[str] = None):
+    """simulate_spatial_multiplexing (core/ofdm_core.py:2489-2815): TM4 with
+    2 / 4 TX, 1-4 RX, rank 1-4 -- one GPU call.  Host: H_initial (:2573-2574,
+    drawn even at fixed rank) -> RankAdaptation.get_feedback on it for
+    rank='adaptive' with CSI (RI / PMI / W, core/rank_adaptation.py:212-265),
+    else the TM4 codebook's PMI 0 of the given rank (min(tx, rx) for
+    'adaptive' without CSI).  GPU: QAM -> layers (first ceil(Nd/rank) data
+    SCs, Q20) -> x = W layers -> CRS pilots per TX (cell tx % 4) -> IFFT/CP
+    -> transmit_spatial_multiplexing -> FFT -> CRS estimate per symbol ->
+    H_eff = H W -> MMSE / IRC / ZF / SIC / MRC with the nominal sigma^2 =
+    10^(-SNR/10) -> layer demap -> hard bits.  Global-RNG consumption as the
+    reference: H_initial -> TX pilot reseeds per symbol and TX -> channel draws
+    (core/channel.py:397-493: rayleigh_mp per link 16 phases per path for
+    filter() and 16 per path for impulse_response(); 'awgn' per link h ~
+    CN(0,1); then noise per RX) -> RX pilot reseeds."""
+    bits = np.asarray(bits)
+    if bits.size == 0:
+        raise ValueError("Bits array cannot be empty")
+    if config is None:
+        config = LTEConfig(modulation=modulation)
+    n0 = len(bits)
+    grid = ResourceGrid(config.N, config.Nc)
+    Nd = len(grid._data)
+    bpo = Nd * config.bits_per_symbol
+    n_sym = int(np.ceil(n0 / bpo))
+    rank_used, pmi_used, W, det = _sm_feedback(num_tx, num_rx, rank, detector_type, snr_db, enable_csi_feedback)
+    plan, gains, fD = _spatial_plan(config, channel_type, itu_profile, velocity_kmh, frequency_ghz, n_sym, n0,
+                                    num_tx=num_tx, num_rx=num_rx, rank=rank_used, detector=det, W=W,
+                                    precision=precision)
+    ray = channel_type == 'rayleigh_mp'
+    ph, ir, lh, z = _sm_draws(plan, grid, num_tx, num_rx, ray)
+    out = plan.run([snr_db], bits=(bits & 1).astype(np.uint8)[None], phases=ph[None] if ray else None,
+                   noise=z[None], link_h=None if ray else lh[None], capture=('bits_rx', 'data_syms'))
+    brx = out['bits_rx'][0].astype(np.int64)
+    err = int(np.sum(bits != brx))
+    Hm = _sm_channel_matrix(ray, gains, fD, ir, lh)
     return {'transmitted_bits': int(n0), 'received_bits': int(n0), 'bits_received_array': brx,
             'bit_errors': err, 'errors': err, 'ber': float(err / n0), 'snr_db': float(snr_db),
             'num_tx': num_tx, 'num_rx': num_rx, 'rank': int(rank_used), 'detector_type': detector_type,
             'mode': 'Spatial Multiplexing TM4', 'codebook_type': codebook_type, 'channel_matrix': Hm,
             'precoder_matrix': W, 'pmi_used': pmi_used, 'velocity_kmh': velocity_kmh,
             'modulation': modulation, 'symbols_rx': out['data_syms'][0].astype(np.complex128)}
+
+
+def simulate_spatial_multiplexing_coded(bits, num_tx=4, num_rx=2, rank='adaptive', detector_type='MMSE', snr_db=15,
+                                        config=None, channel_type='awgn', itu_profile='Pedestrian_A',
+                                        velocity_kmh=3, frequency_ghz=2.0, enable_csi_feedback=True, *,
+                                        precision: Optional[str] = None):
+    """TM4 spatial multiplexing with turbo coding (LTE_CHAIN_SPATIAL_CODED,
+    include/lte_phy.h; not in the reference, which has no coded spatial driver):
+    simulate_siso_coded's coding chain (CRC-24A, segmentation, turbo, rate
+    matching, QAM, T/F interleaver with cols = Nd) around
+    simulate_spatial_multiplexing's transmitter, link and per-symbol CRS
+    estimate, with the soft detector -- MMSE / IRC: unbiased z_l = s_l / mu_l,
+    nv_l = e_l / mu_l, e_l = s2 (A^-1)_ll, mu_l = max(1 - e_l, 1e-6); ZF: nv_l =
+    s2 min((A^-1)_ll, 1e6); MRC: nv = s2 min(1 / ||h||^2, 1e6); s2 = 10^(-SNR/10)
+    -- then max-log LLRs, de-interleave, dematch, 8 turbo iterations, CRC.
+    Rank / PMI selection and the global-RNG order are simulate_spatial_multiplexing's
+    (H_initial, TX pilot reseeds, channel draws, RX pilot reseeds).  One GPU call.
+    Returns simulate_siso_coded's coding keys (symbols_rx: z per coded symbol,
+    de-interleaved) plus rank, pmi_used, precoder_matrix, channel_matrix and
+    noise_var_mean (the mean nv over the coded symbols, formed on the host from
+    the captured estimates by the same rule)."""
+    bits = np.asarray(bits)
+    if bits.size == 0:
+        raise ValueError("Bits array cannot be empty")
+    if config is None:
+        config = LTEConfig()
+    n0 = len(bits)
+    grid = ResourceGrid(config.N, config.Nc)
+    rank_used, pmi_used, W, det = _sm_feedback(num_tx, num_rx, rank, detector_type, snr_db, enable_csi_feedback)
+    if det == C.DET_SIC:
+        raise NotImplementedError("the coded spatial chain has no soft SIC detector: MMSE, IRC, ZF or MRC")
+    plan, gains, fD = _spatial_plan(config, channel_type, itu_profile, velocity_kmh, frequency_ghz, 0, n0,
+                                    num_tx=num_tx, num_rx=num_rx, rank=rank_used, detector=det, W=W,
+                                    precision=precision, coded=True, turbo_iters=8)
+    ray = channel_type == 'rayleigh_mp'
+    ph, ir, lh, z = _sm_draws(plan, grid, num_tx, num_rx, ray)
+    out = plan.run([snr_db], bits=(bits & 1).astype(np.uint8)[None], phases=ph[None] if ray else None,
+                   noise=z[None], link_h=None if ray else lh[None], capture=('bits_rx', 'data_syms', 'H'))
+    dec = out['bits_rx'][0].astype(np.uint8)
+    err = int(np.sum(bits != dec))
+    bps, Nd = config.bits_per_symbol, plan.Nd
+    # the error variance per RE from the captured estimates H [rx][sym][tx][n_dsc], by the detector's rule
+    He = np.einsum('rstj,tc->sjrc', out['H'][0].astype(np.complex128), np.asarray(W, dtype=complex))
+    s2 = 10 ** (-snr_db / 10)
+    A = np.einsum('sjrc,sjrd->sjcd', He.conj(), He)
+    if det == C.DET_MRC:
+        nv = s2 * np.minimum(1.0 / np.real(A[..., 0, 0]), 1e6)[..., None]
+    elif det == C.DET_ZF:
+        nv = s2 * np.minimum(np.real(np.diagonal(np.linalg.inv(A), axis1=-2, axis2=-1)), 1e6)
+    else:
+        e = s2 * np.real(np.diagonal(np.linalg.inv(A + s2 * np.eye(rank_used)), axis1=-2, axis2=-1))
+        nv = e / np.maximum(1.0 - e, 1e-6)
+    nv = nv.reshape(plan.n_sym, -1)[:, :Nd].reshape(-1)                # RE R j + t of each symbol, cut at Nd
+    ncs = plan.coded_bits // bps
+    rows_rx = -(-ncs // Nd)
+    q = np.arange(ncs)
+    src = (q % Nd) * rows_rx + q // Nd                                 # T/F de-interleave, as simulate_siso_coded
+    return {'transmitted_bits': int(n0), 'received_bits': int(n0), 'bits_received_array': dec,
+            'bit_errors': err, 'ber': float(err / n0), 'crc_pass': bool(out['crc_ok'][0]), 'snr_db': float(snr_db),
+            'coded_bits_length': int(plan.coded_bits), 'symbols_rx': out['data_syms'][0].astype(np.complex128)[src],
+            'noise_var_mean': float(np.mean(nv[src])), 'num_tx': num_tx, 'num_rx': num_rx, 'rank': int(rank_used),
+            'detector_type': detector_type, 'pmi_used': pmi_used, 'precoder_matrix': W,
+            'channel_matrix': _sm_channel_matrix(ray, gains, fD, ir, lh)}

@@ -57,6 +57,11 @@ def configs(lte_phy, C):
             return _spatial_plan(cfg, chan, 'Pedestrian_A', 3, 2.0, 14, 14 * nd * 6, F)[0]
         return f
 
+    def c5cod(F):        # config 5's shape, coded: config 2's TB around the soft MMSE detector (LTE_CHAIN_SPATIAL_CODED)
+        from lte_phy.ofdm_core import _spatial_plan
+        return _spatial_plan(Cfg(bandwidth=20.0, modulation='64-QAM'), 'awgn', 'Pedestrian_A', 3, 2.0, 0, 27760, F,
+                             coded=True)[0]
+
     def tm4(num_tx, num_rx, rank, det, pmi=0):
         def f(F):
             from lte_phy.ofdm_core import _spatial_plan, ResourceGrid
@@ -95,6 +100,8 @@ def configs(lte_phy, C):
         'c4': ('config 4: SFBC 2x2 Alamouti + turbo, 20 MHz 64-QAM PedA (TB 27760)', c4),
         'c5': ('config 5: spatial 4x4 rank-4 MMSE, 20 MHz 64-QAM, flat CN(0,1) links', c5('awgn')),
         'c5r': ('config 5: spatial 4x4 rank-4 MMSE, 20 MHz 64-QAM, PedA 3 km/h links', c5('rayleigh_mp')),
+        'c5cod': ('config 5 + turbo: spatial 4x4 rank-4 soft MMSE + turbo, 20 MHz 64-QAM, flat CN(0,1) links (TB 27760)',
+                  c5cod),
         'tm4_sic44': ('TM4 4x4 rank-4 SIC (PMI 1), 20 MHz 64-QAM, flat CN(0,1) links', tm4(4, 4, 4, 'SIC', 1)),
         'tm4_zf22': ('TM4 2x2 rank-2 ZF (PMI 1), 20 MHz 64-QAM, flat CN(0,1) links', tm4(2, 2, 2, 'ZF', 1)),
         'tm4_mrc41': ('TM4 4x1 rank-1 MRC (PMI 3), 20 MHz 64-QAM, flat CN(0,1) links', tm4(4, 1, 1, 'MRC', 3)),
