@@ -105,6 +105,44 @@ enum {
    *     (lte_run_path: dematch=llr). */
   LTE_CHAIN_SPATIAL_CODED = 8
 };
+enum {   /* (continued again: the same value space) */
+  /* Coded SC-FDM (DFT-spread OFDM) with a soft frequency-domain equaliser: this
+   * library's composition (the reference's coded driver has no precoder and its
+   * SC-FDM receiver is uncoded ZF), LTE_CHAIN_CODED's coding chain around the
+   * DFT precoder and LTE_CHAIN_SIMO_CODED's link and estimator.  A SISO-family
+   * chain (num_tx 1, num_rx 1..8, stages as the SISO chains; num_tx > 1:
+   * LTE_EINVAL "bad chain", num_rx > 8: LTE_EUNSUP).  desc.detector selects the
+   * equaliser, LTE_DET_MMSE (0) or LTE_DET_ZF (another: LTE_EINVAL); desc.sc_fdm
+   * is not consulted (LTE_CHAIN_CODED keeps ignoring it).
+   *   TX: LTE_CHAIN_CODED's coding bit for bit -- CRC-24A, segmentation, turbo
+   *     encoding, rate matching at rv 0 with E = 3K + 12, QAM, the T/F interleaver
+   *     with cols = Nd (padding symbols are zeros), n_sym from the coded length
+   *     (desc.n_sym = 0).  Each OFDM symbol's Nd interleaved QAM symbols, zeros
+   *     included, go through the M = Nd unitary DFT exp(-j 2 pi k n / M) / sqrt(M)
+   *     (lte_dft_host64's) and then onto the data subcarriers; CRS pilots unchanged.
+   *   Link, FFT, estimate: LTE_CHAIN_SIMO_CODED's -- one channel per RX, the same
+   *     injected draws and Philox streams, the LS estimate on the first symbol of
+   *     every 14-symbol group.
+   *   Soft equaliser, per OFDM symbol over its Nd data subcarriers k, s2 = 1 /
+   *     10^(SNR/10), D_k = sum_r |H_r,k|^2 and num_k = sum_r conj(H_r,k) Y_r,k as
+   *     LTE_CHAIN_SIMO forms them, on awgn and rayleigh alike:
+   *       MMSE  w_k = num_k / (D_k + s2), e = (1/Nd) sum_k s2 / (D_k + s2),
+   *             mu = max(1 - e, 1e-6), z = IDFT_Nd(w) / mu (unbiased), nv = e / mu
+   *       ZF    w_k = num_k / (D_k + 1e-10), z = IDFT_Nd(w),
+   *             nv = s2 (1/Nd) sum_k 1 / clip(D_k, 1e-6, 1e6)
+   *     nv is one value for the Nd symbols of the OFDM symbol.  The sum over k is
+   *     accumulated in float64 in both plan precisions, in a fixed order (the same
+   *     inputs give the same bits on every run); the rest in the plan's precision.
+   *   Then max-log LLRs of (z, nv) in RE order, T/F de-interleave, dematch,
+   *     turbo_iters iterations, desegmentation, CRC-24A.  counts, frame_errors,
+   *     frame_crc_ok, cap_bits_rx, cap_noise_power and cap_H as
+   *     LTE_CHAIN_SIMO_CODED; cap_data_syms holds z, cap_llr the LLRs, cap_tx_syms
+   *     the QAM symbols before the precoder.  lte_plan_set_early_stop applies;
+   *     HARQ does not (lte_plan_create_harq: LTE_EUNSUP).  Always k_ofdm_tx /
+   *     k_ofdm_tx_ch and k_rx_chest + k_rx_data with LLRs (lte_run_path:
+   *     dematch=llr). */
+  LTE_CHAIN_SCFDM_CODED = 9
+};
 /* MIMODetector.detector_type (core/mimo_detector.py:116-133); IRC == MMSE */
 enum { LTE_DET_MMSE = 0, LTE_DET_ZF = 1, LTE_DET_SIC = 2, LTE_DET_MRC = 3 };
 enum { LTE_CH_AWGN = 0, LTE_CH_RAYLEIGH = 1 }; /* core/channel.py:10-245 */
@@ -154,14 +192,15 @@ typedef struct {
                             * multi-antenna chains use one link per (rx, tx).   */
   /* spatial chain only (LTE_CHAIN_SPATIAL): */
   int32_t rank;            /* layers, 1..min(num_tx, num_rx, 4); 0 -> num_tx with W = I */
-  int32_t detector;        /* LTE_DET_*                                          */
+  int32_t detector;        /* LTE_DET_* (LTE_CHAIN_SCFDM_CODED: its equaliser, MMSE / ZF) */
   double precoder[32];     /* W [num_tx][rank] (LTECodebook.get_precoder, core/codebook_lte.py:
                             * 317-330): entry (t, c) at [(t*4 + c)*2] re, [+1] im */
   /* SC-FDM (enable_sc_fdm, core/dft_precoding.py): the uncoded SISO / SIMO
    * transmitters DFT-precode each symbol's Nd QAM symbols (core/modulator.py:
    * 232-236); the uncoded SISO receiver applies the IDFT after ZF
    * (core/lte_receiver.py:318-333).  As in the reference, the SIMO receiver
-   * does not de-precode and the coded chain ignores the flag. */
+   * does not de-precode and the coded chain ignores the flag.  (Coded SC-FDM is
+   * a chain of its own, LTE_CHAIN_SCFDM_CODED, which does not read the flag.) */
   int32_t sc_fdm;
   /* beamforming chain: 0 = update_mode 'static' (the CSI-feedback codebook
    * vector), 1 = 'adaptive' (MRT, AdaptiveBeamforming) */

@@ -424,7 +424,8 @@ static int plan_tables(lte_plan* p) {
       upload(p->tabs.inv_gap, p->gh.inv_gap) || upload(p->tabs.pilots, pil) || upload(p->tabs.kinfo, make_kinfo(p->gh)) ||
       upload(p->tabs.tw, make_twiddles(d.N)) || upload(p->tabs.constel, make_constellation(d.bps)))
     return fail(LTE_ENOMEM, "table upload failed");
-  if (d.sc_fdm) {   // SC-FDM DFT of size M = Nd (DFTPrecodifier, core/dft_precoding.py:20-118)
+  const bool scf = d.sc_fdm || d.chain == LTE_CHAIN_SCFDM_CODED;   // (that chain precodes whatever the flag says)
+  if (scf) {   // SC-FDM DFT of size M = Nd (DFTPrecodifier, core/dft_precoding.py:20-118)
     std::vector<float2> ch, bh;
     make_bluestein(d.N, p->Nd, ch, bh);
     if (upload(p->tabs.chirp, ch) || upload(p->tabs.bhat, bh)) return fail(LTE_ENOMEM, "table upload failed");
@@ -437,7 +438,7 @@ static int plan_tables(lte_plan* p) {
     if (upload(p->tabs.pilots64, pil64) || upload(p->tabs.inv_gap64, ig64) ||
         upload(p->tabs.tw64, make_twiddles64(d.N)))
       return fail(LTE_ENOMEM, "table upload failed");
-    if (d.sc_fdm) {
+    if (scf) {
       std::vector<double2> ch, bh;
       make_bluestein64(d.N, p->Nd, ch, bh);
       if (upload(p->tabs.chirp64, ch) || upload(p->tabs.bhat64, bh)) return fail(LTE_ENOMEM, "table upload failed");
@@ -753,7 +754,15 @@ static int plan_mimo_tables(lte_plan* p) {
 
 // The chains that run the coding chain (encoder, dematch, turbo decoder, CRC),
 // and those of them that run_siso serves.
-static bool siso_coded(int chain) { return chain == LTE_CHAIN_CODED || chain == LTE_CHAIN_SIMO_CODED; }
+static bool siso_coded(int chain) {
+  return chain == LTE_CHAIN_CODED || chain == LTE_CHAIN_SIMO_CODED || chain == LTE_CHAIN_SCFDM_CODED;
+}
+// The transmitter DFT-precodes each symbol: the uncoded SISO / SIMO chains under
+// sc_fdm, LTE_CHAIN_SCFDM_CODED always; LTE_CHAIN_CODED never (simulate_siso_coded
+// builds its grids without the precoder, core/ofdm_core.py:1062-1099).
+static int tx_precodes(const lte_plan_desc& d) {
+  return d.chain == LTE_CHAIN_SCFDM_CODED || (d.sc_fdm && !siso_coded(d.chain)) ? 1 : 0;
+}
 static bool chain_is_coded(int chain) {
   return siso_coded(chain) || chain == LTE_CHAIN_SFBC_CODED || chain == LTE_CHAIN_SPATIAL_CODED;
 }
@@ -915,7 +924,14 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
   if (d.N < 128 || d.N > 2048 || (d.N & (d.N - 1))) return fail(LTE_EUNSUP, "N must be a power of two in [128, 2048]");
   if (d.Nc <= 0 || d.Nc >= d.N || d.cp_len < 0 || d.cp_len > d.N) return fail(LTE_EINVAL, "bad Nc / cp_len");
   if (d.bps != 2 && d.bps != 4 && d.bps != 6) return fail(LTE_EINVAL, "Unsupported modulation");
-  if (d.chain < 0 || d.chain > LTE_CHAIN_SPATIAL_CODED) return fail(LTE_EINVAL, "bad chain");
+  if (d.chain < 0 || d.chain > LTE_CHAIN_SCFDM_CODED) return fail(LTE_EINVAL, "bad chain");
+  if (d.chain == LTE_CHAIN_SCFDM_CODED) {   // a one-TX chain with its own equaliser choice and RX range
+    if (d.num_tx > 1) return fail(LTE_EINVAL, "bad chain");
+    if (d.detector != LTE_DET_MMSE && d.detector != LTE_DET_ZF)
+      return fail(LTE_EINVAL, "detector " + std::to_string(d.detector) +
+                                  " is no SC-FDM equaliser: LTE_DET_MMSE or LTE_DET_ZF");
+    if (d.num_rx < 1 || d.num_rx > 8) return fail(LTE_EUNSUP, "coded SC-FDM: 1 to 8 RX antennas");
+  }
   // the converse of "num_tx > 1 needs a multi-antenna chain" below, for the chain added last (the
   // older multi-antenna chains keep the refusals they had for such a descriptor)
   if (d.chain == LTE_CHAIN_SPATIAL_CODED && d.num_tx < 2)
@@ -924,11 +940,13 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
   if (d.num_rx < 1 || d.num_rx > 16) return fail(LTE_EINVAL, "num_rx must be >= 1");
   const bool bf = d.chain == LTE_CHAIN_BEAMFORMING;
   // LTE_CHAIN_SIMO_CODED is a SISO-family chain (one TX, run_siso) numbered after the multi-antenna ones
-  // (LTE_CHAIN_SPATIAL_CODED, numbered after it, is a multi-antenna chain again)
-  const bool mimo = d.chain >= LTE_CHAIN_SFBC && !bf && d.chain != LTE_CHAIN_SIMO_CODED;
+  // (LTE_CHAIN_SPATIAL_CODED, numbered after it, is a multi-antenna chain again; LTE_CHAIN_SCFDM_CODED is not)
+  const bool mimo = d.chain >= LTE_CHAIN_SFBC && !bf && d.chain != LTE_CHAIN_SIMO_CODED &&
+                    d.chain != LTE_CHAIN_SCFDM_CODED;
   const int num_tx = d.num_tx > 0 ? d.num_tx : 1;
   if (!mimo && !bf && num_tx != 1) return fail(LTE_EINVAL, "num_tx > 1 needs a multi-antenna chain");
-  if (!mimo && !bf && d.chain != LTE_CHAIN_SIMO && d.chain != LTE_CHAIN_SIMO_CODED && d.num_rx != 1)
+  if (!mimo && !bf && d.chain != LTE_CHAIN_SIMO && d.chain != LTE_CHAIN_SIMO_CODED &&
+      d.chain != LTE_CHAIN_SCFDM_CODED && d.num_rx != 1)
     return fail(LTE_EINVAL, "SISO chains need num_rx == 1");
   if (bf && num_tx != 2 && num_tx != 4 && num_tx != 8)
     return fail(LTE_EINVAL, "num_tx=" + std::to_string(num_tx) + " no soportado en TM6");
@@ -1287,7 +1305,9 @@ static bool tx_per_frame(const lte_plan* p) {
 // [max_frames][n_re] nv: 3 R per RE).
 static bool demap_in_dematch(const lte_plan* p, const lte_run_args* a) {
   const lte_plan_desc& d = p->d;
-  return siso_coded(d.chain) && !p->mimo && !p->bf && (d.bps == 4 || d.bps == 6) && !a->cap_llr;
+  // (not LTE_CHAIN_SCFDM_CODED: its nv is one value per OFDM symbol, the hand-off's per (group, subcarrier))
+  return siso_coded(d.chain) && d.chain != LTE_CHAIN_SCFDM_CODED && !p->mimo && !p->bf && (d.bps == 4 || d.bps == 6) &&
+         !a->cap_llr;
 }
 
 // Fused SISO receiver (k_rx_frame): one RX, coded or uncoded, no SC-FDM.
@@ -1341,7 +1361,8 @@ static SisoPath select_siso(const lte_plan* p, const lte_run_args* a, const Knob
   const Grid& g = p->grid;
   const bool coded = siso_coded(d.chain), tv = d.fD != 0.0;
   const bool cap_H = a->cap_H != nullptr, cap_ps = a->cap_pilot_stats != nullptr;
-  const int stages = a->stages ? a->stages : LTE_STAGE_ALL, rx = d.num_rx, scf = (d.sc_fdm && !coded) ? 1 : 0;
+  const int stages = a->stages ? a->stages : LTE_STAGE_ALL, rx = d.num_rx, scf = tx_precodes(d);
+  const int scf_el = coded && scf ? (p->f64 ? 16 : 8) : 0;   // coded SC-FDM: tx_stage_supported's second buffer
   const bool do_tx = stages & LTE_STAGE_TX, do_ch = stages & LTE_STAGE_CHANNEL, do_rx = stages & LTE_STAGE_RX;
   SisoPath s{};
   // TX + static-tap channel in one kernel (the received stream is written once)
@@ -1367,14 +1388,14 @@ static SisoPath select_siso(const lte_plan* p, const lte_run_args* a, const Knob
     s.tx = TX_NONE;
   else if (!fuse)
     s.tx = TX_SYM;
-  else if (coded && k.tx_frame && tx_per_frame(p))
+  else if (coded && !scf && k.tx_frame && tx_per_frame(p))   // (k_ofdm_txf has no precoder)
     s.tx = k.tx_wave && !p->txf_map.p && txf_w_supported(g, p->f64, d.n_paths, maxd, rx, tv) ? TX_FRAME_W : TX_FRAME;
   else
     s.tx = k.simo_tx_wave && tx_simo_w_supported(g, p->f64, coded, scf, d.n_paths, maxd, rx, tv, s.xhand) ? TX_SIMO_W
                                                                                                           : TX_SYM_CH;
   s.tx_stage = s.tx == TX_FRAME ? TXF_STAGE != 0
                : s.tx == TX_FRAME_W ? k.txw_stage
-               : (s.tx == TX_SYM || s.tx == TX_SYM_CH) && k.tx_stage && tx_stage_supported(g, coded, p->enc_words);
+               : (s.tx == TX_SYM || s.tx == TX_SYM_CH) && k.tx_stage && tx_stage_supported(g, coded, p->enc_words, scf_el);
   // k_ofdm_tx_simo_w built per frame (TXSW_FRAME) forms each symbol's head power itself
   s.ch_fix = s.fused() && !(s.tx == TX_SIMO_W && TXSW_FRAME);
   return s;
@@ -1852,7 +1873,7 @@ static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const Sis
                               cap_tx_syms, ch));
     } else if (path.tx == TX_SYM_CH) {
       LCHK(launch_ofdm_tx_ch<R>(s, p->grid, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, tx_map, B,
-                                cap_tx_syms, ch, (d.sc_fdm && !coded) ? 1 : 0, path.tx_stage ? 1 : 0));
+                                cap_tx_syms, ch, tx_precodes(d), path.tx_stage ? 1 : 0));
     } else if constexpr (std::is_same_v<R, double>) {   // the wave-private transmitters (lte_wave.hip)
       if (path.tx == TX_FRAME_W)
         LCHK(launch_ofdm_txf_w(s, p->grid, p->enc.p, p->enc_words, tx_map, B, cap_tx_syms, ch,
@@ -1932,10 +1953,8 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
       if (e != LTE_OK) return e;
     } else {
       Timer t(p, KN_OFDM_TX);
-      // SC-FDM precodes the uncoded SISO / SIMO transmitters only: simulate_siso_coded
-      // builds its own grids without the precoder (core/ofdm_core.py:1062-1099)
       LCHK(launch_ofdm_tx<R>(s, g, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, tx_map, c.x.p, B, cts,
-                             (d.sc_fdm && !coded) ? 1 : 0, path.tx_stage ? 1 : 0));
+                             tx_precodes(d), path.tx_stage ? 1 : 0));
     }
   } else {
     const R* in = static_cast<const R*>(a->in_signal);
@@ -2010,7 +2029,8 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
                            coded ? nullptr : cap_bits_dev,
                            // the IDFT runs in receive_and_decode only (core/lte_receiver.py:318-333): the SIMO
                            // MRC receiver (core/ofdm_core.py:1340-1534) never de-precodes
-                           (d.sc_fdm && d.chain == LTE_CHAIN_UNCODED) ? 1 : 0, zn ? zn_nv<R>(p) : nullptr));
+                           (d.sc_fdm && d.chain == LTE_CHAIN_UNCODED) ? 1 : 0, zn ? zn_nv<R>(p) : nullptr,
+                           d.detector == LTE_DET_ZF ? 1 : 0));
   }
   if (coded && do_rx) {
     // HARQ: round 0 stores zeros in the rows its map does not cover (an earlier

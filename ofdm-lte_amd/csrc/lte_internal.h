@@ -77,8 +77,9 @@ int launch_encode(hipStream_t s, const uint32_t* pw, int PW, int KWmax, uint32_t
 template <class R>
 int launch_ofdm_tx(hipStream_t s, const Grid& g, int coded, const uint32_t* pw, int PW, const uint32_t* enc,
                    int enc_words, const int32_t* tx_map, cx<R>* x, int B, cx<R>* cap_syms, int sc_fdm, int stage);
-// stage: the coded stream staged in LDS per slot (k_ofdm_tx, with or without the channel)
-bool tx_stage_supported(const Grid& g, int coded, int enc_words);
+// stage: the coded stream staged in LDS per slot (k_ofdm_tx, with or without the channel);
+// scf_el: sizeof(cx<R>) for the coded SC-FDM transmitter (a second symbol buffer), else 0
+bool tx_stage_supported(const Grid& g, int coded, int enc_words, int scf_el = 0);
 template <class R>
 int launch_fading(hipStream_t s, int B, int num_rx, int n_paths, const R* gains_dev, const uint64_t* fid,
                   uint64_t seed, const R* inj_ph, int64_t inj_stride, R* phases, cx<R>* coef);
@@ -165,13 +166,16 @@ template <class R>
 int launch_rx_chest(hipStream_t s, const Grid& g, int B, int num_rx, const cx<R>* y, int64_t y_rx_stride,
                     int64_t y_frame_stride, const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z,
                     int64_t inj_stride, cx<R>* H, R* pstats);
-// coded: nv_out set -> llr takes z (cx<R> per RE), nv_out sigma^2_eff
+// coded: nv_out set -> llr takes z (cx<R> per RE), nv_out sigma^2_eff.
+// LTE_CHAIN_SCFDM_CODED: always de-precodes (sc_fdm is not read), LLRs only; eq_zf: its ZF rule (0: MMSE).
 template <class R>
 int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B, int num_rx, const cx<R>* y,
                    int64_t y_rx_stride, int64_t y_frame_stride, const cx<R>* H, const R* npow, const R* snr_lin,
                    const uint64_t* fid, uint64_t seed, const R* inj_z, int64_t inj_stride, const uint32_t* pw, int PW,
                    int n_bits, uint32_t* frame_err, R* llr, cx<R>* cap_syms, uint8_t* cap_bits, int sc_fdm = 0,
-                   R* nv_out = nullptr);
+                   R* nv_out = nullptr, int eq_zf = 0);
+// k_rx_data's CHAIN argument for LTE_CHAIN_SCFDM_CODED with the ZF rule (the chain value plus this bit)
+constexpr int RX_EQ_ZF = 0x100;
 // Fused SISO receiver (estimation + data path, one slot per frame): coded or
 // uncoded, one RX, no SC-FDM.  nv_out set: llr takes z per RE and nv_out
 // sigma^2_eff per (frame, group, data subcarrier); H / pstats: optional captures.

@@ -270,8 +270,9 @@ __device__ __forceinline__ void tx_channel(cx<R>* buf, const Grid& g, const TxCh
 // tx_map (rate_match_turbo + T/F interleaver, rate_matching.py:193-297,
 // ofdm_core.py:1040-1099), ResourceMapper.map_symbols (resource_mapper.py:
 // 181-223), ifft*sqrt(N) + CP (modulator.py:242-248).
-// SCF (SC-FDM, uncoded chains): the Nd QAM symbols of the OFDM symbol are
-// DFT-precoded (M = Nd, core/modulator.py:232-236) in a second LDS buffer first.
+// SCF (SC-FDM: the uncoded chains with sc_fdm, and LTE_CHAIN_SCFDM_CODED): the Nd
+// QAM symbols of the OFDM symbol are DFT-precoded (M = Nd, core/modulator.py:
+// 232-236) in a second LDS buffer first; the staged coded stream follows both.
 // CH: the channel applied in place (tx_channel: 1 static taps, 2 time-varying);
 // NC: compile-time N (fft_lds).
 template <class R, int CODED, int BPS, bool SCF = false, int CH = 0, int NC = 0, int NP = 0>
@@ -294,7 +295,7 @@ __global__ __launch_bounds__(WG) void k_ofdm_tx(Grid g, const uint32_t* __restri
   // instead of issuing scattered global loads
   const uint32_t* fe = enc + (size_t)b * enc_words;
   if (CODED && stage_enc) {
-    uint32_t* es = reinterpret_cast<uint32_t*>(sm + spw * N) + slot * enc_words;
+    uint32_t* es = reinterpret_cast<uint32_t*>(sm + (SCF ? 2 : 1) * spw * N) + slot * enc_words;
     if (active)
       for (int i = tid; i < enc_words; i += T) es[i] = fe[i];
     fe = es;
@@ -336,7 +337,8 @@ __global__ __launch_bounds__(WG) void k_ofdm_tx(Grid g, const uint32_t* __restri
         idx = (idx << 1) | (int)bit;
       }
       const V sym = zero ? mkc((R)0, (R)0) : qam_point<BPS, R>(idx);
-      buf[kpos[q]] = sym;
+      if constexpr (SCF) pre[j] = sym;   // (the padding zeros are precoded like any symbol)
+      else buf[kpos[q]] = sym;
       if (cap_syms) cap_syms[(size_t)b * g.n_sym * g.Nd + (size_t)l * g.Nd + j] = sym;
     }
   }
@@ -372,12 +374,15 @@ __global__ __launch_bounds__(WG) void k_ofdm_tx(Grid g, const uint32_t* __restri
 
 // LDS bytes of the coded stream staged per slot (0: not staged; Knobs::tx_stage
 // off gathers the coded bits through L1 / L2 instead).
-static size_t tx_enc_shm(int coded, int spw, int enc_words, int stage) {
+// scf_el (coded SC-FDM: bytes per complex element, else 0): the two symbol
+// buffers of a block (2 * 2048 elements) and the stream stay within the 64 KB a
+// launch gets without an attribute, so float64 (64 KB of buffers) never stages.
+static size_t tx_enc_shm(int coded, int spw, int enc_words, int stage, int scf_el = 0) {
   const size_t e = (size_t)spw * enc_words * sizeof(uint32_t);
-  return coded && stage && e <= 32768 ? e : 0;
+  return coded && stage && e <= 32768 && (size_t)scf_el * 2 * 2048 + e <= 65536 ? e : 0;
 }
-bool tx_stage_supported(const Grid& g, int coded, int enc_words) {
-  return tx_enc_shm(coded, WG / (g.N >> 3), enc_words, 1) > 0;
+bool tx_stage_supported(const Grid& g, int coded, int enc_words, int scf_el) {
+  return tx_enc_shm(coded, WG / (g.N >> 3), enc_words, 1, scf_el) > 0;
 }
 
 template <class R>
@@ -386,17 +391,18 @@ int launch_ofdm_tx(hipStream_t s, const Grid& g, int coded, const uint32_t* pw, 
   const int spw = WG / (g.N >> 3);
   const int64_t total = (int64_t)B * g.n_sym;
   if (total > 0x7FFFFFFF - spw || (g.bps != 2 && g.bps != 4 && g.bps != 6)) return (int)hipErrorInvalidValue;
-  if (stage && !tx_stage_supported(g, coded, enc_words)) return (int)hipErrorInvalidValue;
-  if (sc_fdm && (coded || !GridT<R>::chirp(g) || !GridT<R>::bhat(g) || 2 * g.Nd > g.N))
-    return (int)hipErrorInvalidValue;
+  // sc_fdm: the chain's precode decision (the uncoded chains' flag, LTE_CHAIN_SCFDM_CODED; never LTE_CHAIN_CODED)
+  const int scf_el = coded && sc_fdm ? (int)sizeof(cx<R>) : 0;
+  if (stage && !tx_stage_supported(g, coded, enc_words, scf_el)) return (int)hipErrorInvalidValue;
+  if (sc_fdm && (!GridT<R>::chirp(g) || !GridT<R>::bhat(g) || 2 * g.Nd > g.N)) return (int)hipErrorInvalidValue;
   const int blocks = (int)((total + spw - 1) / spw);
-  const size_t enc_shm = tx_enc_shm(coded, spw, enc_words, stage);
+  const size_t enc_shm = tx_enc_shm(coded, spw, enc_words, stage, scf_el);
   const int stage_enc = enc_shm > 0;
   const size_t shm = (sc_fdm ? 2 : 1) * spw * g.N * sizeof(cx<R>) + enc_shm;
   return launch_status(with_bps(g.bps, [&](auto Q) {
     with_bool(coded, [&](auto C) {
       with_bool(sc_fdm, [&](auto S) {
-        constexpr bool SCF = S() && !C();   // SC-FDM is the uncoded chains' (checked above)
+        constexpr bool SCF = S();
         hipLaunchKernelGGL((k_ofdm_tx<R, C(), Q(), SCF>), dim3(blocks), dim3(WG), shm, s, g, pw, PW, enc, enc_words,
                            tx_map, x, B, cap_syms, stage_enc, TxChannelT<R>{});
       });
@@ -415,14 +421,14 @@ int launch_ofdm_tx_ch(hipStream_t s, const Grid& g, int coded, const uint32_t* p
                       int sc_fdm, int stage) {
   const int spw = WG / (g.N >> 3);
   const int64_t total = (int64_t)B * g.n_sym;
-  if (sc_fdm && (coded || !GridT<R>::chirp(g) || !GridT<R>::bhat(g) || 2 * g.Nd > g.N))
-    return (int)hipErrorInvalidValue;
+  const int scf_el = coded && sc_fdm ? (int)sizeof(cx<R>) : 0;   // (sc_fdm: as launch_ofdm_tx)
+  if (sc_fdm && (!GridT<R>::chirp(g) || !GridT<R>::bhat(g) || 2 * g.Nd > g.N)) return (int)hipErrorInvalidValue;
   if (!txch_supported(g, ch.n_paths, ch.max_delay) || total > 0x7FFFFFFF - spw ||
       (g.bps != 2 && g.bps != 4 && g.bps != 6))
     return (int)hipErrorInvalidValue;
-  if (stage && !tx_stage_supported(g, coded, enc_words)) return (int)hipErrorInvalidValue;
+  if (stage && !tx_stage_supported(g, coded, enc_words, scf_el)) return (int)hipErrorInvalidValue;
   const int blocks = (int)((total + spw - 1) / spw);
-  const size_t enc_shm = tx_enc_shm(coded, spw, enc_words, stage);
+  const size_t enc_shm = tx_enc_shm(coded, spw, enc_words, stage, scf_el);
   const int stage_enc = enc_shm > 0;
   const size_t shm = (sc_fdm ? 2 : 1) * (size_t)spw * g.N * sizeof(cx<R>) + enc_shm;
   return launch_status(with_bps(g.bps, [&](auto Q) {
@@ -431,7 +437,7 @@ int launch_ofdm_tx_ch(hipStream_t s, const Grid& g, int coded, const uint32_t* p
         with_bool(ch.tcoef != nullptr, [&](auto TV) {
           with_n<2048, 1024>(g.N, [&](auto N) {
             with_int_or<0, 4, 6>(ch.n_paths, [&](auto P) {
-              constexpr bool SCF = S() && !C();   // SC-FDM is the uncoded chains' (checked above)
+              constexpr bool SCF = S();
               constexpr int CH = TV() ? 2 : 1;    // tx_channel: static / time-varying taps
               // compile-time N: 2048 (20 MHz), and 1024 (10 MHz, config 3) for the
               // uncoded OFDM transmitters with static taps
@@ -1207,6 +1213,25 @@ __device__ __forceinline__ re_t<V> abs2_ref(V h) {
 // (modulator.py:28-59, Q9): bits = [I-level bits | Q-level bits], MSB first.
 // (store_llrs, the LLR output of every receiver: lte_dev.h)
 
+// Sum of v over the T = 16 .. 256 threads of a slot (consecutive lanes, T a
+// power of two), returned to each of them: a butterfly over the slot's lanes of
+// a wave, adjacent pairs first (every lane adds the same two values at each
+// step, so all hold the same bits), then the slot's T / 64 waves in order
+// through red[wave of the block].  A fixed order, no atomics.  Every thread of
+// the block calls it (T > 64 has a barrier); one call per red.
+__device__ __forceinline__ double slot_sum(double v, int T, double* red) {
+  const int W = T < 64 ? T : 64;
+  for (int o = 1; o < W; o <<= 1) v += __shfl_xor(v, o);
+  if (T > 64) {
+    const int wave = threadIdx.x >> 6, wps = T >> 6, w0 = wave / wps * wps;
+    if ((threadIdx.x & 63) == 0) red[wave] = v;
+    __syncthreads();
+    v = red[w0];
+    for (int w = 1; w < wps; ++w) v += red[w0 + w];
+  }
+  return v;
+}
+
 // ---------------------------------------------------------------------------
 // Data path: one slot per (frame, OFDM symbol).  Per RX: CP-remove + noise +
 // FFT/sqrt(N) (lte_receiver.py:444-491); then
@@ -1218,6 +1243,12 @@ __device__ __forceinline__ re_t<V> abs2_ref(V h) {
 // Templated on chain and bits/symbol so every per-RE array stays in VGPRs.
 //  SCF (SC-FDM, UNCODED): the ZF outputs of the symbol's Nd data REs go
 //       through the M = Nd IDFT (core/lte_receiver.py:318-333) before slicing.
+//  SCFDM_CODED (SCF set; CHAIN + RX_EQ_ZF: the ZF rule): the MRC sums, then per
+//       OFDM symbol the mean over its data subcarriers of s2 / (D + s2) (ZF: of
+//       1 / clip(D)) -- slot_sum, the only reduction over a slot here -- the
+//       weights num / (D + s2) (ZF: + 1e-10), their IDFT, the bias 1 / mu and one
+//       nv for the symbol's LLRs (include/lte_phy.h).  One double of LDS per
+//       wave follows the symbol buffers.
 template <class R, int CHAIN, int BPS, bool SCF = false, int NC = 0>
 __global__ __launch_bounds__(WG) void k_rx_data(Grid g, int rayleigh, int B, int num_rx,
                                                 const cx<R>* __restrict__ y, int64_t y_rx_stride,
@@ -1243,8 +1274,10 @@ __global__ __launch_bounds__(WG) void k_rx_data(Grid g, int rayleigh, int B, int
   constexpr R QS = (R)qam_norm<BPS>();
   constexpr int QM = 4;  // data REs per thread (Nd < N/2 for every LTE profile)
   // SIMO_CODED: the MRC sums of SIMO, then CODED's soft output with sigma^2 / D
-  constexpr bool MRC = CHAIN == LTE_CHAIN_SIMO || CHAIN == LTE_CHAIN_SIMO_CODED;
-  constexpr bool SOFT = CHAIN == LTE_CHAIN_CODED || CHAIN == LTE_CHAIN_SIMO_CODED;
+  constexpr bool FDE = (CHAIN & ~RX_EQ_ZF) == LTE_CHAIN_SCFDM_CODED, FDE_ZF = FDE && (CHAIN & RX_EQ_ZF) != 0;
+  static_assert(!FDE || SCF, "LTE_CHAIN_SCFDM_CODED de-precodes");
+  constexpr bool MRC = CHAIN == LTE_CHAIN_SIMO || CHAIN == LTE_CHAIN_SIMO_CODED || FDE;
+  constexpr bool SOFT = CHAIN == LTE_CHAIN_CODED || CHAIN == LTE_CHAIN_SIMO_CODED || FDE;
   constexpr int NRX = MRC ? 8 : 1;
   V num[QM];
   R den[QM];
@@ -1279,6 +1312,25 @@ __global__ __launch_bounds__(WG) void k_rx_data(Grid g, int rayleigh, int B, int
     }
     if constexpr (NRX > 1) __syncthreads();
   }
+  R fde_mu = (R)1, fde_nv = (R)0;   // FDE: the OFDM symbol's bias and noise variance
+  if constexpr (FDE) {
+    const R s2 = active ? (R)1 / snr_lin[b] : (R)1;
+    double part = 0.0;   // this thread's terms in q order; inactive slots carry zeros through the barrier
+#pragma unroll
+    for (int q = 0; q < QM; ++q)
+      if (active && tid + q * T < g.Nd)
+        part += (double)(FDE_ZF ? (R)1 / fmin(fmax(den[q], (R)1e-6), (R)1e6) : s2 / (den[q] + s2));
+    const R mean = (R)(slot_sum(part, T, reinterpret_cast<double*>(sm + spw * N)) / (double)g.Nd);
+    if constexpr (FDE_ZF) {
+      fde_nv = s2 * mean;
+    } else {
+      fde_mu = fmax((R)1 - mean, (R)1e-6);
+      fde_nv = mean / fde_mu;
+    }
+    const R reg = FDE_ZF ? (R)1e-10 : s2;
+#pragma unroll
+    for (int q = 0; q < QM; ++q) num[q] = mkc(num[q].x / (den[q] + reg), num[q].y / (den[q] + reg));
+  }
   if constexpr (SCF) {   // IDFT(z) = conj(DFT(conj(z))) over the Nd data REs, in the (consumed) FFT buffer
     __syncthreads();
     if (active) {
@@ -1307,7 +1359,12 @@ __global__ __launch_bounds__(WG) void k_rx_data(Grid g, int rayleigh, int B, int
     if (!active || j >= g.Nd) continue;
     const int re = l * g.Nd + j;
     V z = num[q];
-    if constexpr (MRC) {
+    if constexpr (FDE) {
+      z = mkc(z.x / fde_mu, z.y / fde_mu);
+      if (cap_syms) cap_syms[fre + re] = z;
+      store_llrs<R, BPS>(llr + (fre + re) * BPS, z, fde_nv);
+      continue;
+    } else if constexpr (MRC) {
       const R r = (R)1 / (den[q] + (R)1e-10);
       z = mkc(z.x * r, z.y * r);
     }
@@ -1986,8 +2043,24 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
                    int64_t y_rx_stride, int64_t y_frame_stride, const cx<R>* H, const R* npow, const R* snr_lin,
                    const uint64_t* fid, uint64_t seed, const R* inj_z, int64_t inj_stride, const uint32_t* pw, int PW,
                    int n_bits, uint32_t* frame_err, R* llr, cx<R>* cap_syms, uint8_t* cap_bits, int sc_fdm,
-                   R* nv_out) {
+                   R* nv_out, int eq_zf) {
   if (g.bps != 2 && g.bps != 4 && g.bps != 6) return (int)hipErrorInvalidValue;
+  if (chain == LTE_CHAIN_SCFDM_CODED) {   // one nv per OFDM symbol: LLRs only, no (z, nv) hand-off
+    if (nv_out || !llr || !GridT<R>::chirp(g) || !GridT<R>::bhat(g) || 2 * g.Nd > g.N || num_rx < 1 || num_rx > 8)
+      return (int)hipErrorInvalidValue;
+    const int spw = WG / (g.N >> 3);
+    const int64_t total = (int64_t)B * g.n_sym;
+    if (total > 0x7FFFFFFF - spw) return (int)hipErrorInvalidValue;
+    const size_t shm = spw * g.N * sizeof(cx<R>) + (WG / 64) * sizeof(double);   // + slot_sum's red
+    return launch_status(with_bps(g.bps, [&](auto Q) {
+      with_bool(eq_zf, [&](auto Z) {
+        constexpr int CH = LTE_CHAIN_SCFDM_CODED + (Z() ? RX_EQ_ZF : 0);
+        hipLaunchKernelGGL((k_rx_data<R, CH, Q(), true>), dim3((int)((total + spw - 1) / spw)), dim3(WG), shm, s, g,
+                           rayleigh, B, num_rx, y, y_rx_stride, y_frame_stride, H, npow, snr_lin, fid, seed, inj_z,
+                           inj_stride, pw, PW, n_bits, frame_err, llr, cap_syms, cap_bits, (R*)nullptr);
+      });
+    }));
+  }
   if (nv_out && chain != LTE_CHAIN_CODED && chain != LTE_CHAIN_SIMO_CODED) return (int)hipErrorInvalidValue;
   if (sc_fdm && (chain != LTE_CHAIN_UNCODED || !GridT<R>::chirp(g) || !GridT<R>::bhat(g)))
     return (int)hipErrorInvalidValue;
@@ -2034,7 +2107,7 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
                                   const uint64_t*, uint64_t, const R*, int64_t, cx<R>*, R*);                        \
   template int launch_rx_data<R>(hipStream_t, const Grid&, int, int, int, int, const cx<R>*, int64_t, int64_t,       \
                                  const cx<R>*, const R*, const R*, const uint64_t*, uint64_t, const R*, int64_t,    \
-                                 const uint32_t*, int, int, uint32_t*, R*, cx<R>*, uint8_t*, int, R*);              \
+                                 const uint32_t*, int, int, uint32_t*, R*, cx<R>*, uint8_t*, int, R*, int);         \
   template int launch_rx_frame_simo<R>(hipStream_t, const Grid&, int, int, const cx<R>*, int64_t, int64_t, const R*,  \
                                        const uint64_t*, uint64_t, const R*, int64_t, const uint32_t*, int, int,       \
                                        uint32_t*, cx<R>*, uint8_t*, cx<R>*, R*, int, const TxChannelT<R>*,           \

@@ -19,6 +19,7 @@ LTE_OK, LTE_EINVAL, LTE_EHIP, LTE_ENOMEM, LTE_ENODEV, LTE_EUNSUP = 0, -1, -2, -3
 CHAIN_UNCODED, CHAIN_CODED, CHAIN_SIMO, CHAIN_SFBC, CHAIN_SFBC_CODED, CHAIN_SPATIAL, CHAIN_BEAMFORMING = 0, 1, 2, 3, 4, 5, 6
 CHAIN_SIMO_CODED = 7   # 1 x num_rx MRC with turbo coding: a SISO-family chain numbered after the multi-antenna ones
 CHAIN_SPATIAL_CODED = 8   # TM4 spatial multiplexing with the soft MMSE / ZF / MRC detector and turbo coding
+CHAIN_SCFDM_CODED = 9   # coded SC-FDM: DFT precoder, soft MMSE / ZF frequency-domain equaliser, turbo coding (SISO family)
 CH_AWGN, CH_RAYLEIGH = 0, 1
 DET_MMSE, DET_ZF, DET_SIC, DET_MRC = 0, 1, 2, 3
 STAGE_TX, STAGE_CHANNEL, STAGE_RX, STAGE_ALL = 1, 2, 4, 7

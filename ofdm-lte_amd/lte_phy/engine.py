@@ -23,11 +23,13 @@ MIMO_CHAINS = (C.CHAIN_SFBC, C.CHAIN_SFBC_CODED, C.CHAIN_SPATIAL)
 # its own: tests/test_simo_coded_host.py holds the two above to the chains that
 # existed with the coded SIMO chain.
 CODED_MIMO_CHAINS = (C.CHAIN_SPATIAL_CODED,)
+# The coded SC-FDM chain: coded, SISO family (one TX), likewise in a tuple of its own.
+CODED_SCFDM_CHAINS = (C.CHAIN_SCFDM_CODED,)
 
 
 def chain_is_coded(chain):
     """Plan.coded: the chain runs the coding chain (encoder, dematch, turbo, CRC)."""
-    return chain in CODED_CHAINS or chain in CODED_MIMO_CHAINS
+    return chain in CODED_CHAINS or chain in CODED_MIMO_CHAINS or chain in CODED_SCFDM_CHAINS
 
 
 def chain_is_mimo(chain):

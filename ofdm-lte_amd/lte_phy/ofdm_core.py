@@ -505,10 +505,11 @@ class OFDMSimulator:
     def Nd(self):
         return len(self.grid._data)
 
-    def _plan(self, chain, n_sym, n_bits, num_rx=1, max_frames=1, iters=8, early_stop=False, harq=None):
+    def _plan(self, chain, n_sym, n_bits, num_rx=1, max_frames=1, iters=8, early_stop=False, harq=None, detector=0):
         """SC-FDM (enable_sc_fdm / mode 'sc-fdm') reaches the uncoded SISO / SIMO
         transmitters and the SISO receiver; simulate_siso_coded ignores it, as
-        the reference does (lte_plan_desc.sc_fdm, include/lte_phy.h)."""
+        the reference does (lte_plan_desc.sc_fdm, include/lte_phy.h).  The coded
+        SC-FDM chain precodes whatever the flag says; `detector` is its equaliser."""
         cfg, ch = self.config, self.channels[0]
         sc = int(self.tx.modulator.enable_sc_fdm and chain in (C.CHAIN_UNCODED, C.CHAIN_SIMO))
         # enable_equalization reaches simulate_siso's receiver only (the coded and SIMO
@@ -518,7 +519,7 @@ class OFDMSimulator:
                         chain=chain, channel=ch.kind, num_rx=num_rx, delays=tuple(ch.delays),
                         gains=tuple(ch.gains), fD=ch.fD, fs=cfg.fs, n_bits=n_bits, turbo_iters=iters,
                         max_frames=max_frames, sc_fdm=sc, no_equalization=noeq, precision=self.precision,
-                        early_stop=early_stop, harq=harq)
+                        early_stop=early_stop, harq=harq, detector=detector)
 
     def _ref_draws(self, L, num_rx=1):
         """Exactly the global-RNG consumption of one reference simulate_* call:
@@ -708,6 +709,76 @@ class OFDMSimulator:
         self.last_results = res
         return res
 
+    # -------------------------------------------------------------- SC-FDM + turbo
+    @staticmethod
+    def _scfdm_equalizer(equalizer):
+        eq = str(equalizer).lower()
+        if eq not in ('mmse', 'zf'):
+            raise ValueError(f"equalizer must be 'mmse' or 'zf', not {equalizer!r}")
+        return eq, (C.DET_MMSE if eq == 'mmse' else C.DET_ZF)
+
+    def simulate_scfdm_coded(self, bits: np.ndarray, snr_db: float = 10.0, num_rx: int = 1,
+                             equalizer: str = 'mmse') -> Dict:
+        """Turbo-coded SC-FDM (DFT-spread OFDM) with a soft frequency-domain
+        equaliser (LTE_CHAIN_SCFDM_CODED, include/lte_phy.h; not in the reference,
+        whose coded driver has no precoder): simulate_siso_coded's coding chain,
+        each OFDM symbol's Nd QAM symbols through the M = Nd DFT, one channel per
+        RX as simulate_simo, and per OFDM symbol over D_k = sum|H_i,k|^2, s2 = 1 / SNR
+          'mmse': w = sum(conj(H_i) Y_i) / (D + s2), e = mean s2 / (D + s2),
+                  mu = max(1 - e, 1e-6), z = IDFT(w) / mu, nv = e / mu
+          'zf':   w = sum(conj(H_i) Y_i) / (D + 1e-10), z = IDFT(w),
+                  nv = s2 mean 1 / clip(D, 1e-6, 1e6)
+        with one nv for the symbol's LLRs.  The simulator's enable_sc_fdm flag is
+        not consulted.  One GPU call; the global RNG is consumed as simulate_simo
+        consumes it.  Returns simulate_simo_coded's keys (papr_db: of the
+        DFT-spread stream; noise_var_mean: the mean of nv) plus 'equalizer'."""
+        bits = self._bits_in(bits)
+        if num_rx < 1:
+            raise ValueError("num_rx must be >= 1")
+        eq, det = self._scfdm_equalizer(equalizer)
+        n0 = len(bits)
+        plan = self._plan(C.CHAIN_SCFDM_CODED, 0, n0, num_rx=num_rx, iters=8, detector=det)
+        ph, z = self._ref_draws(plan.L, num_rx)
+        r = plan.run([snr_db], bits=(bits & 1).astype(np.uint8)[None], phases=ph[None] if ph.size else None,
+                     noise=z[None], capture=('signal_tx', 'signal_rx', 'data_syms', 'bits_rx', 'tx_syms', 'H'))
+        bps, Nd = self.config.bits_per_symbol, self.Nd
+        coded = plan.coded_bits
+        dec = r['bits_rx'][0].astype(np.uint8)
+        err = int(np.sum(bits != dec))
+        sig_tx = r['signal_tx'][0].astype(np.complex128)
+        pa = papr(sig_tx)
+        # T/F de-interleave of the captured TX / RX symbols, as simulate_siso_coded
+        ncs_tx = -(-coded // bps)
+        rows = -(-ncs_tx // Nd)
+        q = np.arange(ncs_tx)
+        qam = r['tx_syms'][0].astype(np.complex128)[(q % Nd) * rows + q // Nd]
+        ncs = coded // bps
+        rows_rx = -(-ncs // Nd)
+        q = np.arange(ncs)
+        src = (q % Nd) * rows_rx + q // Nd
+        Hs = r['H'][0].astype(np.complex128)                           # [num_rx][n_grp][N]
+        Dg = np.zeros((plan.n_grp, Nd))
+        for a in range(num_rx):                                        # RX order, as the receiver sums
+            Dg += np.abs(Hs[a][:, self.grid._data]) ** 2
+        s2 = 1.0 / (10 ** (snr_db / 10))
+        if eq == 'mmse':
+            e = np.mean(s2 / (Dg + s2), axis=1)
+            nvg = e / np.maximum(1.0 - e, 1e-6)
+        else:
+            nvg = s2 * np.mean(1.0 / np.clip(Dg, 1e-6, 1e6), axis=1)
+        grp = np.arange(plan.n_sym) // SLOT_SIZE
+        res = {'transmitted_bits': int(n0), 'received_bits': int(n0), 'bits_received_array': dec,
+               'bit_errors': err, 'ber': float(err / n0), 'crc_pass': bool(r['crc_ok'][0]),
+               'snr_db': float(snr_db), 'papr_db': float(pa['papr_db']), 'papr_linear': float(pa['papr_linear']),
+               'coded_bits_length': int(coded), 'signal_tx': sig_tx,
+               'signal_rx_list': [r['signal_rx'][0, i].astype(np.complex128) for i in range(num_rx)],
+               'symbols_tx': qam, 'symbols_rx': r['data_syms'][0].astype(np.complex128)[src],
+               'channel_gain': np.concatenate([Dg[g] for g in grp])[src],
+               'noise_var_mean': float(np.mean(np.repeat(nvg[grp], Nd)[src])), 'num_rx': num_rx,
+               'combining_method': 'mrc', 'equalizer': eq}
+        self.last_results = res
+        return res
+
     # -------------------------------------------------------------- SFBC (config 4)
     def _sfbc_plan(self, n_sym, n_bits, num_rx, coded=False, max_frames=1, iters=8, early_stop=False):
         cfg, ch = self.config, self.channels[0]
@@ -876,7 +947,7 @@ class OFDMSimulator:
             raise ValueError("early_stop needs a coded chain (coded=True with mimo=None, 'sfbc' or 'spatial'): "
                              "nothing is decoded here")
         snrs = np.atleast_1d(np.asarray(snr_range, dtype=np.float64))
-        S, T = len(snrs), int(num_trials)
+        T = int(num_trials)
         cfg = self.config
         if mimo == 'sfbc':
             res = self.Nd & ~1
@@ -922,26 +993,7 @@ class OFDMSimulator:
             n_sym = int(np.ceil(nb / (self.Nd * cfg.bits_per_symbol)))
             chain = C.CHAIN_SIMO if num_rx > 1 else C.CHAIN_UNCODED
             plan = self._plan(chain, n_sym, nb, num_rx=num_rx, max_frames=frames_per_call)
-        ids = np.array([s * T + t for s in range(S) for t in trial_shard(T, rank, world_size)], dtype=np.uint64)
-        counts = np.zeros((S, 4), dtype=np.uint64)
-        hist = np.zeros((S, int(turbo_iters) + 1), dtype=np.uint64) if early_stop else None
-        for i in range(0, len(ids), frames_per_call):
-            chunk = ids[i:i + frames_per_call]
-            si = (chunk // T).astype(np.int32)
-            r = plan.run(snrs[si], snr_index=si, n_snr=S, seed=seed, frame_ids=chunk)
-            counts += r['counts']
-            if early_stop:
-                used = r['turbo_iters_used']
-                np.add.at(hist, (np.repeat(si, used.shape[1]), used.ravel()), 1)
-        with np.errstate(divide='ignore', invalid='ignore'):
-            ber = counts[:, 0] / np.maximum(counts[:, 1], 1)
-            bler = counts[:, 2] / np.maximum(counts[:, 3], 1)
-        out = {'snr_db': snrs, 'counts': counts, 'ber': ber, 'bler': bler, 'bit_errors': counts[:, 0],
-               'bits': counts[:, 1], 'block_errors': counts[:, 2], 'blocks': counts[:, 3], 'plan': plan}
-        if early_stop:
-            out['turbo_iters_hist'] = hist
-            out['turbo_iters_mean'] = (hist * np.arange(hist.shape[1])).sum(axis=1) / np.maximum(hist.sum(axis=1), 1)
-        return out
+        return _run_plan_grid(plan, snrs, T, seed, frames_per_call, rank, world_size, turbo_iters, early_stop)
 
     def run_harq_grid(self, snr_range, num_trials, seed=0, n_bits=None, coded_bits=None, max_tx=4,
                       rv_seq=(0, 2, 3, 1), frames_per_call=4096, rank=0, world_size=1, turbo_iters=8, **other):
@@ -961,6 +1013,45 @@ class OFDMSimulator:
         run_grid keywords coded=False, num_rx > 1 or mimo= raise ValueError."""
         return _harq_grid(self, snr_range, num_trials, seed, n_bits, coded_bits, max_tx, rv_seq, frames_per_call,
                           rank, world_size, turbo_iters, other)
+
+    def run_scfdm_grid(self, snr_range, num_trials, seed=0, num_rx=1, equalizer='mmse', n_bits=None,
+                       frames_per_call=4096, rank=0, world_size=1, turbo_iters=8, early_stop=False):
+        """BER / BLER grid of the coded SC-FDM chain on the device
+        (LTE_CHAIN_SCFDM_CODED; simulate_scfdm_coded's chain, equalizer 'mmse' or
+        'zf', 1..8 RX; n_bits defaults to 27760).  Frame ids, Philox streams,
+        sharding, the counts layout and early_stop as run_grid(coded=True): the
+        caller all-reduces `counts` (and 'turbo_iters_hist')."""
+        det = self._scfdm_equalizer(equalizer)[1]
+        snrs = np.atleast_1d(np.asarray(snr_range, dtype=np.float64))
+        plan = self._plan(C.CHAIN_SCFDM_CODED, 0, int(n_bits or 27760), num_rx=num_rx, max_frames=frames_per_call,
+                          iters=turbo_iters, early_stop=early_stop, detector=det)
+        return _run_plan_grid(plan, snrs, int(num_trials), seed, frames_per_call, rank, world_size, turbo_iters,
+                              early_stop)
+
+
+def _run_plan_grid(plan, snrs, T, seed, frames_per_call, rank, world_size, turbo_iters, early_stop):
+    """The (SNR, trial) frames of this rank through a plan: run_grid's result dict."""
+    S = len(snrs)
+    ids = np.array([s * T + t for s in range(S) for t in trial_shard(T, rank, world_size)], dtype=np.uint64)
+    counts = np.zeros((S, 4), dtype=np.uint64)
+    hist = np.zeros((S, int(turbo_iters) + 1), dtype=np.uint64) if early_stop else None
+    for i in range(0, len(ids), frames_per_call):
+        chunk = ids[i:i + frames_per_call]
+        si = (chunk // T).astype(np.int32)
+        r = plan.run(snrs[si], snr_index=si, n_snr=S, seed=seed, frame_ids=chunk)
+        counts += r['counts']
+        if early_stop:
+            used = r['turbo_iters_used']
+            np.add.at(hist, (np.repeat(si, used.shape[1]), used.ravel()), 1)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        ber = counts[:, 0] / np.maximum(counts[:, 1], 1)
+        bler = counts[:, 2] / np.maximum(counts[:, 3], 1)
+    out = {'snr_db': snrs, 'counts': counts, 'ber': ber, 'bler': bler, 'bit_errors': counts[:, 0],
+           'bits': counts[:, 1], 'block_errors': counts[:, 2], 'blocks': counts[:, 3], 'plan': plan}
+    if early_stop:
+        out['turbo_iters_hist'] = hist
+        out['turbo_iters_mean'] = (hist * np.arange(hist.shape[1])).sum(axis=1) / np.maximum(hist.sum(axis=1), 1)
+    return out
 
 
 def _harq_grid(sim, snr_range, num_trials, seed, n_bits, coded_bits, max_tx, rv_seq, frames_per_call, rank,

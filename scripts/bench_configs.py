@@ -41,7 +41,11 @@ def configs(lte_phy, C):
             return s._plan(C.CHAIN_SIMO_CODED, 0, 27760, num_rx=num_rx, max_frames=F)
         return f
 
-    def c3cod(F):        # config 3's numerology and link, coded: TB 9000 = 14 OFDM symbols
+    def c2scf(F):        # config 2's numerology and coding, DFT-spread with the soft MMSE equaliser (LTE_CHAIN_SCFDM_CODED)
+        s = O(Cfg(bandwidth=20.0, modulation='64-QAM'), channel_type='rayleigh_mp', itu_profile='Pedestrian_A')
+        return s._plan(C.CHAIN_SCFDM_CODED, 0, 27760, num_rx=1, max_frames=F, detector=C.DET_MMSE)
+
+    def c3cod(F):       # config 3's numerology and link, coded: TB 9000 = 14 OFDM symbols
         s = O(Cfg(bandwidth=10.0, modulation='16-QAM'), channel_type='rayleigh_mp', itu_profile='Vehicular_A')
         return s._plan(C.CHAIN_SIMO_CODED, 0, 9000, num_rx=4, max_frames=F)
 
@@ -95,6 +99,7 @@ def configs(lte_phy, C):
         'c2': ('config 2: SISO 20 MHz 64-QAM PedA + turbo (TB 27760)', c2),
         'c2mrc2': ('config 2 + MRC: SIMO 1x2 MRC + turbo, 20 MHz 64-QAM PedA (TB 27760)', c2mrc(2)),
         'c2mrc4': ('config 2 + MRC: SIMO 1x4 MRC + turbo, 20 MHz 64-QAM PedA (TB 27760)', c2mrc(4)),
+        'c2scf': ('config 2 as SC-FDM: SISO 20 MHz 64-QAM PedA, DFT-spread + soft MMSE-FDE + turbo (TB 27760)', c2scf),
         'c3': ('config 3: SIMO 1x4 MRC 10 MHz 16-QAM VehA, 14 symbols uncoded', c3),
         'c3cod': ('config 3 + turbo: SIMO 1x4 MRC + turbo, 10 MHz 16-QAM VehA (TB 9000)', c3cod),
         'c4': ('config 4: SFBC 2x2 Alamouti + turbo, 20 MHz 64-QAM PedA (TB 27760)', c4),
