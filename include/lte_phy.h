@@ -295,6 +295,11 @@ int lte_plan_create(const lte_plan_desc *desc, lte_plan **out);
 int lte_plan_destroy(lte_plan *plan);
 /* Geometry derived by the plan: [L, n_sym, Nd, Np, n_grp, n_cb, coded_bits, n_re_bits] */
 int lte_plan_info(const lte_plan *plan, int64_t *info8);
+/* What kind of chain an LTE_CHAIN_* value is (no device needed; an addition to ABI 3): fills the first n of
+ * [family (0 SISO family, 1 multi-antenna, 2 beamforming), coded (1: encoder, dematch, turbo decoder, CRC),
+ * mode (-1 none, 0 SFBC, 1 spatial multiplexing), precode (0 never DFT-precodes, 1 follows desc.sc_fdm, 2 always)]
+ * and returns the number of fields, 4.  An unassigned value: LTE_EINVAL "bad chain". */
+int lte_chain_info(int chain, int32_t *info, int n);
 /* Arithmetic type the plan runs in: LTE_PREC_F32 or LTE_PREC_F64. */
 int lte_plan_precision(const lte_plan *plan);
 /* Run the full chain (TX -> channel -> RX (-> turbo)) for one batch of frames. */

@@ -424,7 +424,7 @@ static int plan_tables(lte_plan* p) {
       upload(p->tabs.inv_gap, p->gh.inv_gap) || upload(p->tabs.pilots, pil) || upload(p->tabs.kinfo, make_kinfo(p->gh)) ||
       upload(p->tabs.tw, make_twiddles(d.N)) || upload(p->tabs.constel, make_constellation(d.bps)))
     return fail(LTE_ENOMEM, "table upload failed");
-  const bool scf = d.sc_fdm || d.chain == LTE_CHAIN_SCFDM_CODED;   // (that chain precodes whatever the flag says)
+  const bool scf = d.sc_fdm || p->ct->precode == PRECODE_ALWAYS;   // (the tables follow the flag on every chain)
   if (scf) {   // SC-FDM DFT of size M = Nd (DFTPrecodifier, core/dft_precoding.py:20-118)
     std::vector<float2> ch, bh;
     make_bluestein(d.N, p->Nd, ch, bh);
@@ -752,31 +752,32 @@ static int plan_mimo_tables(lte_plan* p) {
 
 }  // extern "C"
 
-// The chains that run the coding chain (encoder, dematch, turbo decoder, CRC),
-// and those of them that run_siso serves.
-static bool siso_coded(int chain) {
-  return chain == LTE_CHAIN_CODED || chain == LTE_CHAIN_SIMO_CODED || chain == LTE_CHAIN_SCFDM_CODED;
+// A coded plan's decoder rows: per code block the zeroed input rows and the window checkpoints; the rows' addresses.
+template <class R>
+static bool alloc_decoder_rows(lte_plan* p, ChainBufs<R>& c) {
+  const int G = (int)(((size_t)p->d.max_frames + 63) / 64);
+  bool bad = false;
+  c.blk.resize(p->C);
+  c.ckpt.resize(p->C);
+  std::vector<R*> bp(p->C);
+  for (int r = 0; r < p->C; ++r) {
+    const int K = p->cbs[r].K;
+    bad |= c.blk[r].alloc((size_t)turbo_galloc(G) * turbo_rows(K) * 64) != 0;
+    bad |= c.ckpt[r].alloc((size_t)turbo_galloc(G) * turbo_nwin(K) * turbo_ck_rows(sizeof(R) == 8) * 64) != 0;
+    if (!bad && hipMemset(c.blk[r].p, 0, c.blk[r].n * sizeof(R)) != hipSuccess) bad = true;
+    bp[r] = c.blk[r].p;
+  }
+  if (!bad) bad |= upload(c.blk_ptrs, bp) != 0;
+  return !bad;
 }
-// The transmitter DFT-precodes each symbol: the uncoded SISO / SIMO chains under
-// sc_fdm, LTE_CHAIN_SCFDM_CODED always; LTE_CHAIN_CODED never (simulate_siso_coded
-// builds its grids without the precoder, core/ofdm_core.py:1062-1099).
-static int tx_precodes(const lte_plan_desc& d) {
-  return d.chain == LTE_CHAIN_SCFDM_CODED || (d.sc_fdm && !siso_coded(d.chain)) ? 1 : 0;
-}
-static bool chain_is_coded(int chain) {
-  return siso_coded(chain) || chain == LTE_CHAIN_SFBC_CODED || chain == LTE_CHAIN_SPATIAL_CODED;
-}
-// the TM4 chains (run_mimo, MIMO_SPATIAL): hard and soft detection
-static bool chain_is_spatial(int chain) { return chain == LTE_CHAIN_SPATIAL || chain == LTE_CHAIN_SPATIAL_CODED; }
 
 // Device workspace of the SISO / SIMO chains in precision R.  The TX signal x
 // is allocated on first use (the fused TX + channel path never writes it).
 template <class R>
-static bool alloc_siso(lte_plan* p, bool coded) {
+static bool alloc_siso(lte_plan* p) {
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
   const size_t B = (size_t)d.max_frames;
-  const int G = (int)((B + 63) / 64);
   const int rx = d.num_rx;
   const bool ray = d.channel == LTE_CH_RAYLEIGH;
   bool bad = false;
@@ -792,33 +793,22 @@ static bool alloc_siso(lte_plan* p, bool coded) {
   bad |= c.pstats.alloc(B * rx * p->n_grp * 2) != 0;
   bad |= c.npow.alloc(B * rx) != 0;
   bad |= c.snr_lin.alloc(B) != 0;
-  if (coded) {
+  if (p->ct->coded) {
     // the fused demap path keeps (z, nv) = 3 R per RE here; the LLR path
     // (captures, QPSK) grows it to bps R per RE on first use
     const size_t n_re = p->n_re_bits / d.bps;
     bad |= c.llr.alloc(B * (d.bps >= 4 ? 3 * n_re : (size_t)p->n_re_bits)) != 0;
-    c.blk.resize(p->C);
-    c.ckpt.resize(p->C);
-    std::vector<R*> bp(p->C);
-    for (int r = 0; r < p->C; ++r) {
-      const int K = p->cbs[r].K;
-      bad |= c.blk[r].alloc((size_t)turbo_galloc(G) * turbo_rows(K) * 64) != 0;
-      bad |= c.ckpt[r].alloc((size_t)turbo_galloc(G) * turbo_nwin(K) * turbo_ck_rows(sizeof(R) == 8) * 64) != 0;
-      if (!bad && hipMemset(c.blk[r].p, 0, c.blk[r].n * sizeof(R)) != hipSuccess) bad = true;
-      bp[r] = c.blk[r].p;
-    }
-    if (!bad) bad |= upload(c.blk_ptrs, bp) != 0;
+    bad = bad || !alloc_decoder_rows<R>(p, c);
   }
   return !bad;
 }
 
 // Device workspace of the multi-antenna chains in precision R.
 template <class R>
-static bool alloc_mimo(lte_plan* p, bool coded) {
+static bool alloc_mimo(lte_plan* p) {
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
   const size_t B = (size_t)d.max_frames;
-  const int G = (int)((B + 63) / 64);
   const bool ray = d.channel == LTE_CH_RAYLEIGH;
   const MimoGrid& m = p->mg;
   const size_t links = (size_t)m.num_rx * m.num_tx;
@@ -828,7 +818,7 @@ static bool alloc_mimo(lte_plan* p, bool coded) {
   bad |= c.y.alloc(B * m.num_rx * p->L) != 0;
   bad |= c.coef.alloc(B * links * (ray ? d.n_paths : 1) * m.n_cs * (p->f64 ? mimo_ncf<double>() : mimo_ncf<float>())) != 0;
   if (ray && m.exact_jakes) bad |= c.phases.alloc(B * links * d.n_paths * 16) != 0;
-  if (ray && !chain_is_spatial(d.chain)) {
+  if (ray && m.mode == MIMO_SFBC) {
     bad |= c.link_part.alloc(B * links * p->nblk) != 0;
     bad |= c.link_sigma.alloc(B * links) != 0;
   }
@@ -846,19 +836,9 @@ static bool alloc_mimo(lte_plan* p, bool coded) {
   bad |= c.pow_part.alloc(B * m.num_rx * p->nblk) != 0;
   bad |= c.npow.alloc(B * m.num_rx) != 0;
   bad |= c.snr_lin.alloc(B) != 0;
-  if (coded) {
+  if (p->ct->coded) {
     bad |= c.llr.alloc(B * p->n_re_bits) != 0;
-    c.blk.resize(p->C);
-    c.ckpt.resize(p->C);
-    std::vector<R*> bp(p->C);
-    for (int r = 0; r < p->C; ++r) {
-      const int K = p->cbs[r].K;
-      bad |= c.blk[r].alloc((size_t)turbo_galloc(G) * turbo_rows(K) * 64) != 0;
-      bad |= c.ckpt[r].alloc((size_t)turbo_galloc(G) * turbo_nwin(K) * turbo_ck_rows(sizeof(R) == 8) * 64) != 0;
-      if (!bad && hipMemset(c.blk[r].p, 0, c.blk[r].n * sizeof(R)) != hipSuccess) bad = true;
-      bp[r] = c.blk[r].p;
-    }
-    if (!bad) bad |= upload(c.blk_ptrs, bp) != 0;
+    bad = bad || !alloc_decoder_rows<R>(p, c);
   }
   return !bad;
 }
@@ -869,11 +849,11 @@ static int plan_alloc(lte_plan* p) {
   const lte_plan_desc& d = p->d;
   const size_t B = (size_t)d.max_frames;
   const int G = (int)((B + 63) / 64);
-  const bool coded = chain_is_coded(d.chain);
+  const bool coded = p->ct->coded;
   bool bad = false;
   bad |= p->pw.alloc(B * p->PW) != 0;
   if (p->mimo) {
-    bad |= !(p->f64 ? alloc_mimo<double>(p, coded) : alloc_mimo<float>(p, coded));
+    bad |= !(p->f64 ? alloc_mimo<double>(p) : alloc_mimo<float>(p));
   } else if (p->bf) {   // per frame: the BfFrameT state and the noise scale (in snr_lin)
     if (p->f64) {
       bad |= p->bf_fr64.alloc(B) != 0;
@@ -883,7 +863,7 @@ static int plan_alloc(lte_plan* p) {
       bad |= p->c32.snr_lin.alloc(B) != 0;
     }
   } else {
-    bad |= !(p->f64 ? alloc_siso<double>(p, coded) : alloc_siso<float>(p, coded));
+    bad |= !(p->f64 ? alloc_siso<double>(p) : alloc_siso<float>(p));
   }
   bad |= p->snr_idx.alloc(B) != 0;
   if (p->mimo) bad |= p->nvar.alloc(B) != 0;
@@ -909,13 +889,14 @@ static int plan_alloc(lte_plan* p) {
   return LTE_OK;
 }
 
+static_assert(chain_traits(LTE_CHAIN_BEAMFORMING).rx_max == LTE_BF_MAX_RX, "BfFrameT holds the table's RX ceiling");
 // lte_plan_create (harq null) / lte_plan_create_harq
 static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte_plan** out) {
   if (!desc || !out) return fail(LTE_EINVAL, "null argument");
   const lte_plan_desc& d = *desc;
+  const ChainTraits& ct = chain_traits(d.chain);
   if (harq) {
-    if (d.chain != LTE_CHAIN_CODED)
-      return fail(LTE_EUNSUP, "HARQ runs on the coded SISO chain (LTE_CHAIN_CODED) only");
+    if (!ct.harq) return fail(LTE_EUNSUP, "HARQ runs on the coded SISO chain (LTE_CHAIN_CODED) only");
     if (harq->max_tx < 1 || harq->max_tx > 8) return fail(LTE_EINVAL, "HARQ: max_tx must be in 1..8");
     for (int t = 0; t < harq->max_tx; ++t)
       if (harq->rv_seq[t] < 0 || harq->rv_seq[t] > 3) return fail(LTE_EINVAL, "HARQ: rv_seq entries must be in 0..3");
@@ -924,48 +905,42 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
   if (d.N < 128 || d.N > 2048 || (d.N & (d.N - 1))) return fail(LTE_EUNSUP, "N must be a power of two in [128, 2048]");
   if (d.Nc <= 0 || d.Nc >= d.N || d.cp_len < 0 || d.cp_len > d.N) return fail(LTE_EINVAL, "bad Nc / cp_len");
   if (d.bps != 2 && d.bps != 4 && d.bps != 6) return fail(LTE_EINVAL, "Unsupported modulation");
-  if (d.chain < 0 || d.chain > LTE_CHAIN_SCFDM_CODED) return fail(LTE_EINVAL, "bad chain");
-  if (d.chain == LTE_CHAIN_SCFDM_CODED) {   // a one-TX chain with its own equaliser choice and RX range
+  if (!chain_valid(d.chain)) return fail(LTE_EINVAL, "bad chain");
+  if (ct.fde) {   // coded SC-FDM answers for its antennas and its equaliser choice before the common checks
     if (d.num_tx > 1) return fail(LTE_EINVAL, "bad chain");
     if (d.detector != LTE_DET_MMSE && d.detector != LTE_DET_ZF)
       return fail(LTE_EINVAL, "detector " + std::to_string(d.detector) +
                                   " is no SC-FDM equaliser: LTE_DET_MMSE or LTE_DET_ZF");
-    if (d.num_rx < 1 || d.num_rx > 8) return fail(LTE_EUNSUP, "coded SC-FDM: 1 to 8 RX antennas");
+    if (d.num_rx < 1 || d.num_rx > ct.rx_max) return fail(LTE_EUNSUP, "coded SC-FDM: 1 to 8 RX antennas");
   }
-  // the converse of "num_tx > 1 needs a multi-antenna chain" below, for the chain added last (the
-  // older multi-antenna chains keep the refusals they had for such a descriptor)
+  // one TX on the coded spatial chain is refused by name (the other multi-antenna chains: by their antenna checks below)
   if (d.chain == LTE_CHAIN_SPATIAL_CODED && d.num_tx < 2)
     return fail(LTE_EINVAL, "bad chain for num_tx < 2: LTE_CHAIN_SPATIAL_CODED is a multi-antenna chain (2 or 4 TX)");
   if (d.channel != LTE_CH_AWGN && d.channel != LTE_CH_RAYLEIGH) return fail(LTE_EINVAL, "Tipo de canal desconocido");
   if (d.num_rx < 1 || d.num_rx > 16) return fail(LTE_EINVAL, "num_rx must be >= 1");
-  const bool bf = d.chain == LTE_CHAIN_BEAMFORMING;
-  // LTE_CHAIN_SIMO_CODED is a SISO-family chain (one TX, run_siso) numbered after the multi-antenna ones
-  // (LTE_CHAIN_SPATIAL_CODED, numbered after it, is a multi-antenna chain again; LTE_CHAIN_SCFDM_CODED is not)
-  const bool mimo = d.chain >= LTE_CHAIN_SFBC && !bf && d.chain != LTE_CHAIN_SIMO_CODED &&
-                    d.chain != LTE_CHAIN_SCFDM_CODED;
+  const bool mimo = ct.family == CHAIN_MIMO, bf = ct.family == CHAIN_BF;
+  const bool sfbc = ct.mode == MIMO_SFBC, spatial = ct.mode == MIMO_SPATIAL;
   const int num_tx = d.num_tx > 0 ? d.num_tx : 1;
-  if (!mimo && !bf && num_tx != 1) return fail(LTE_EINVAL, "num_tx > 1 needs a multi-antenna chain");
-  if (!mimo && !bf && d.chain != LTE_CHAIN_SIMO && d.chain != LTE_CHAIN_SIMO_CODED &&
-      d.chain != LTE_CHAIN_SCFDM_CODED && d.num_rx != 1)
-    return fail(LTE_EINVAL, "SISO chains need num_rx == 1");
-  if (bf && num_tx != 2 && num_tx != 4 && num_tx != 8)
-    return fail(LTE_EINVAL, "num_tx=" + std::to_string(num_tx) + " no soportado en TM6");
-  if (bf && d.num_rx > LTE_BF_MAX_RX) return fail(LTE_EUNSUP, "beamforming: at most 8 RX antennas");
-  if ((d.chain == LTE_CHAIN_SFBC || d.chain == LTE_CHAIN_SFBC_CODED) && num_tx != 2)
-    return fail(LTE_EINVAL, "Alamouti SFBC requires exactly 2 TX antennas");
-  if ((d.chain == LTE_CHAIN_SFBC || d.chain == LTE_CHAIN_SFBC_CODED) && d.num_rx > 8)
-    return fail(LTE_EUNSUP, "SFBC: at most 8 RX antennas");
-  const int rank = chain_is_spatial(d.chain) ? (d.rank > 0 ? d.rank : num_tx) : 0;
-  if (chain_is_spatial(d.chain)) {
+  const int rank = spatial ? (d.rank > 0 ? d.rank : num_tx) : 0;
+  if (spatial) {   // (the reference's refusals first, then this path's antenna ranges)
     if (d.num_rx < rank)
       return fail(LTE_EINVAL, "num_rx (" + std::to_string(d.num_rx) + ") debe ser >= num_layers (" +
                                   std::to_string(rank) + ")");
     if (d.detector < LTE_DET_MMSE || d.detector > LTE_DET_MRC) return fail(LTE_EINVAL, "Detector no soportado");
     if (d.detector == LTE_DET_MRC && rank != 1) return fail(LTE_EINVAL, "MRC solo soporta num_layers=1 (rank-1)");
-    if ((num_tx != 2 && num_tx != 4) || d.num_rx > 4 || rank < 1 || rank > num_tx)
+    if (!tx_allowed(ct, num_tx) || d.num_rx > ct.rx_max || rank < 1 || rank > num_tx)
       return fail(LTE_EUNSUP, "spatial multiplexing on the GPU path: 2 or 4 TX, 1-4 RX, rank <= num_tx");
-    if (d.chain == LTE_CHAIN_SPATIAL_CODED && d.detector == LTE_DET_SIC)
+    if (ct.coded && d.detector == LTE_DET_SIC)
       return fail(LTE_EUNSUP, "the coded spatial chain has no soft SIC: MMSE, ZF or MRC");
+  } else {   // the chain's num_tx set, then its num_rx ceiling, in its family's words
+    if (!tx_allowed(ct, num_tx))
+      return fail(LTE_EINVAL, bf     ? "num_tx=" + std::to_string(num_tx) + " no soportado en TM6"
+                              : sfbc ? "Alamouti SFBC requires exactly 2 TX antennas"
+                                     : "num_tx > 1 needs a multi-antenna chain");
+    if (d.num_rx > ct.rx_max)
+      return bf     ? fail(LTE_EUNSUP, "beamforming: at most 8 RX antennas")
+             : sfbc ? fail(LTE_EUNSUP, "SFBC: at most 8 RX antennas")
+                    : fail(LTE_EINVAL, "SISO chains need num_rx == 1");
   }
   if (d.channel == LTE_CH_RAYLEIGH && (d.n_paths < 1 || d.n_paths > LTE_MAX_PATHS))
     return fail(LTE_EINVAL, "bad n_paths");
@@ -979,19 +954,20 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
   lte_plan* const p = own.get();
   p->d = d;
   p->d.num_tx = num_tx;
+  p->ct = &ct;
   p->mimo = mimo;
+  p->bf = bf;
   p->f64 = d.precision != LTE_PREC_F32;
   if (harq) {
     p->harq = true;
     p->hq = *harq;
   }
-  const bool coded = chain_is_coded(d.chain);
+  const bool coded = ct.coded;
   if (coded && d.turbo_iters < 0) return fail(LTE_EINVAL, "bad turbo_iters");
   int rc = plan_tables(p);
   if (rc) return rc;
   // Nd < N/2 is assumed by k_rx_data (4 data REs per thread)
   if (p->Nd * 2 >= d.N) return fail(LTE_EUNSUP, "Nd >= N/2 not supported");
-  const bool sfbc = d.chain == LTE_CHAIN_SFBC || d.chain == LTE_CHAIN_SFBC_CODED;
   // REs per OFDM symbol: SFBC drops an odd last data SC (core/sfbc_alamouti.py:196-200, Q18)
   p->res = sfbc ? (p->Nd & ~1) : p->Nd;
   if (coded) {
@@ -1007,7 +983,6 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
   p->L = bf ? p->n_sym * p->Nd : p->n_sym * (d.N + d.cp_len);   // beamforming: REs per antenna
   p->n_grp = (p->n_sym + 13) / 14;
   p->nblk = bf ? (p->L + 255) / 256 : std::max((p->L + 255) / 256, mimo_channel_nblk(p->L, d.N + d.cp_len));
-  p->bf = bf;
   if (bf) {   // rank-1 codebook (TM6 == TM4 rank 1), core/codebook_lte.py:58-96
     std::vector<double> cb;
     const double r2 = 1.0 / std::sqrt(2.0);
@@ -1031,7 +1006,7 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
   }
   if (mimo) {
     MimoGrid& m = p->mg;
-    m.mode = sfbc ? MIMO_SFBC : MIMO_SPATIAL;
+    m.mode = ct.mode;
     m.num_tx = num_tx;
     m.num_rx = d.num_rx;
     m.res = p->res;
@@ -1131,6 +1106,15 @@ int lte_plan_info(const lte_plan* p, int64_t* info) {
   return LTE_OK;
 }
 
+int lte_chain_info(int chain, int32_t* info, int n) {
+  if (!info) return fail(LTE_EINVAL, "null argument");
+  if (!chain_valid(chain)) return fail(LTE_EINVAL, "bad chain");
+  const ChainTraits& ct = chain_traits(chain);
+  const int32_t v[4] = {ct.family, ct.coded ? 1 : 0, ct.mode, ct.precode};
+  for (int i = 0; i < 4 && i < n; ++i) info[i] = v[i];
+  return 4;
+}
+
 int lte_plan_precision(const lte_plan* p) {
   if (!p) return fail(LTE_EINVAL, "null plan");
   return p->f64 ? LTE_PREC_F64 : LTE_PREC_F32;
@@ -1139,7 +1123,7 @@ int lte_plan_precision(const lte_plan* p) {
 int lte_plan_set_early_stop(lte_plan* p, int on) {
   if (!p) return fail(LTE_EINVAL, "null plan");
   if (p->harq) return fail(LTE_EUNSUP, "CRC early termination is not combined with HARQ");
-  if (!chain_is_coded(p->d.chain))
+  if (!p->ct->coded)
     return fail(LTE_EINVAL, "early stop applies to the coded chains only (nothing is decoded in this plan)");
   if (on && p->es_used.empty()) {
     std::vector<DBuf<uint32_t>> u(p->C);
@@ -1305,19 +1289,18 @@ static bool tx_per_frame(const lte_plan* p) {
 // [max_frames][n_re] nv: 3 R per RE).
 static bool demap_in_dematch(const lte_plan* p, const lte_run_args* a) {
   const lte_plan_desc& d = p->d;
-  // (not LTE_CHAIN_SCFDM_CODED: its nv is one value per OFDM symbol, the hand-off's per (group, subcarrier))
-  return siso_coded(d.chain) && d.chain != LTE_CHAIN_SCFDM_CODED && !p->mimo && !p->bf && (d.bps == 4 || d.bps == 6) &&
-         !a->cap_llr;
+  // (not coded SC-FDM: its nv is one value per OFDM symbol, the hand-off's per (group, subcarrier))
+  return p->ct->zn && (d.bps == 4 || d.bps == 6) && !a->cap_llr;
 }
 
 // Fused SISO receiver (k_rx_frame): one RX, coded or uncoded, no SC-FDM.
 static bool rx_fusable(const lte_plan* p) {
   const lte_plan_desc& d = p->d;
-  return rx_frame_supported(p->grid, d.chain, d.num_rx, (d.sc_fdm && d.chain == LTE_CHAIN_UNCODED) ? 1 : 0);
+  return rx_frame_supported(p->grid, d.chain, d.num_rx, precode_on(p->ct->deprecode, d.sc_fdm));
 }
 // Fused SIMO MRC receiver (k_rx_frame_simo*), uncoded or with the coded chain's soft output.
 static bool rx_simo_fusable(const lte_plan* p) {
-  return (p->d.chain == LTE_CHAIN_SIMO || p->d.chain == LTE_CHAIN_SIMO_CODED) && rx_frame_simo_supported(p->grid, p->d.num_rx);
+  return p->ct->mrc && !p->ct->fde && rx_frame_simo_supported(p->grid, p->d.num_rx);
 }
 
 // the kernel families, as lte_run_path prints them
@@ -1359,9 +1342,9 @@ struct MimoPath {
 static SisoPath select_siso(const lte_plan* p, const lte_run_args* a, const Knobs& k) {
   const lte_plan_desc& d = p->d;
   const Grid& g = p->grid;
-  const bool coded = siso_coded(d.chain), tv = d.fD != 0.0;
+  const bool coded = p->ct->coded, tv = d.fD != 0.0;
   const bool cap_H = a->cap_H != nullptr, cap_ps = a->cap_pilot_stats != nullptr;
-  const int stages = a->stages ? a->stages : LTE_STAGE_ALL, rx = d.num_rx, scf = tx_precodes(d);
+  const int stages = a->stages ? a->stages : LTE_STAGE_ALL, rx = d.num_rx, scf = precode_on(p->ct->precode, d.sc_fdm);
   const int scf_el = coded && scf ? (p->f64 ? 16 : 8) : 0;   // coded SC-FDM: tx_stage_supported's second buffer
   const bool do_tx = stages & LTE_STAGE_TX, do_ch = stages & LTE_STAGE_CHANNEL, do_rx = stages & LTE_STAGE_RX;
   SisoPath s{};
@@ -1406,7 +1389,7 @@ static MimoPath select_mimo(const lte_plan* p, const lte_run_args* a, const Knob
   const lte_plan_desc& d = p->d;
   const Grid& g = p->grid;
   const MimoGrid& m = p->mg;
-  const bool coded = chain_is_coded(d.chain), ray = d.channel == LTE_CH_RAYLEIGH, sfbc = m.mode == MIMO_SFBC;
+  const bool coded = p->ct->coded, ray = d.channel == LTE_CH_RAYLEIGH, sfbc = m.mode == MIMO_SFBC;
   const bool link_noise = sfbc && ray;  // transmit_mimo's per-link 100 dB ChannelSimulator (core/ofdm_core.py:490-503)
   const bool inj_lz = a->link_noise && link_noise, inj_z = a->noise != nullptr;
   const int maxd = ray ? *std::max_element(d.delays, d.delays + d.n_paths) : 0;
@@ -1439,7 +1422,7 @@ static MimoPath select_mimo(const lte_plan* p, const lte_run_args* a, const Knob
   // coded SFBC 16/64-QAM without an LLR capture: the detector hands over the
   // combined symbols and each RE pair's sigma^2_eff, k_dematch_zn demaps (as
   // the SISO chain does; LTE_DEMAP_IN_DEMATCH=0 keeps the LLR round trip)
-  s.zn = coded && sfbc && (d.bps == 4 || d.bps == 6) && !a->cap_llr && (m.res & 1) == 0 && m.n_dsc <= m.res &&
+  s.zn = p->ct->zn && (d.bps == 4 || d.bps == 6) && !a->cap_llr && (m.res & 1) == 0 && m.n_dsc <= m.res &&
          k.demap_in_dematch;
   // config 4 (SFBC on Philox draws, zn handoff or uncoded, no capture of the
   // received grids / estimates / symbols): receiver + detector in one pass
@@ -1615,7 +1598,7 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, in
   const MimoGrid& m = p->mg;
   ChainBufs<R>& c = cbuf<R>(p);
   hipStream_t s = p->stream;
-  const bool coded = chain_is_coded(d.chain);   // SFBC or spatial + the coding chain
+  const bool coded = p->ct->coded;   // SFBC or spatial + the coding chain
   const bool ray = d.channel == LTE_CH_RAYLEIGH;
   const bool sfbc = m.mode == MIMO_SFBC;
   const bool link_noise = sfbc && ray;  // transmit_mimo's per-link 100 dB ChannelSimulator (core/ofdm_core.py:490-503)
@@ -1873,7 +1856,7 @@ static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const Sis
                               cap_tx_syms, ch));
     } else if (path.tx == TX_SYM_CH) {
       LCHK(launch_ofdm_tx_ch<R>(s, p->grid, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, tx_map, B,
-                                cap_tx_syms, ch, tx_precodes(d), path.tx_stage ? 1 : 0));
+                                cap_tx_syms, ch, precode_on(p->ct->precode, d.sc_fdm), path.tx_stage ? 1 : 0));
     } else if constexpr (std::is_same_v<R, double>) {   // the wave-private transmitters (lte_wave.hip)
       if (path.tx == TX_FRAME_W)
         LCHK(launch_ofdm_txf_w(s, p->grid, p->enc.p, p->enc_words, tx_map, B, cap_tx_syms, ch,
@@ -1900,7 +1883,7 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
   const Grid& g = p->grid;
-  const bool coded = siso_coded(d.chain), ray_cfg = d.channel == LTE_CH_RAYLEIGH;
+  const bool coded = p->ct->coded, ray_cfg = d.channel == LTE_CH_RAYLEIGH;
   const int rx = d.num_rx;
   hipStream_t s = p->stream;
   const int stages = a->stages ? a->stages : LTE_STAGE_ALL;
@@ -1954,7 +1937,7 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
     } else {
       Timer t(p, KN_OFDM_TX);
       LCHK(launch_ofdm_tx<R>(s, g, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, tx_map, c.x.p, B, cts,
-                             tx_precodes(d), path.tx_stage ? 1 : 0));
+                             precode_on(p->ct->precode, d.sc_fdm), path.tx_stage ? 1 : 0));
     }
   } else {
     const R* in = static_cast<const R*>(a->in_signal);
@@ -2029,7 +2012,7 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
                            coded ? nullptr : cap_bits_dev,
                            // the IDFT runs in receive_and_decode only (core/lte_receiver.py:318-333): the SIMO
                            // MRC receiver (core/ofdm_core.py:1340-1534) never de-precodes
-                           (d.sc_fdm && d.chain == LTE_CHAIN_UNCODED) ? 1 : 0, zn ? zn_nv<R>(p) : nullptr,
+                           precode_on(p->ct->deprecode, d.sc_fdm), zn ? zn_nv<R>(p) : nullptr,
                            d.detector == LTE_DET_ZF ? 1 : 0));
   }
   if (coded && do_rx) {
@@ -2128,7 +2111,7 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
   const int stages = a->stages ? a->stages : LTE_STAGE_ALL;
   if (!(stages & LTE_STAGE_TX) && !a->in_signal) return fail(LTE_EINVAL, "in_signal required when the TX stage is skipped");
   p->evuse.clear();
-  if (logmap_on() && chain_is_coded(d.chain) && !p->f64)
+  if (logmap_on() && p->ct->coded && !p->f64)
     return fail(LTE_EUNSUP, "exact log-MAP decoding runs in float64 plans only");
   if (logmap_on() && p->early_stop)
     return fail(LTE_EUNSUP, "CRC early termination runs the max-log decoders only (set_decoder_mode(True))");
@@ -2166,7 +2149,7 @@ int lte_run_path(const lte_plan* p, const lte_run_args* a, char* buf, int len) {
     const SisoPath s = select_siso(p, a, knobs);
     n = std::snprintf(buf, len, "tx=%s tx_stage=%d ch_fix=%d rx=%s xhand=%d dematch=%s", SISO_TX_NAME[s.tx], s.tx_stage,
                       s.ch_fix, SISO_RX_NAME[s.rx], s.xhand,
-                      !siso_coded(p->d.chain) || s.rx == RX_NONE ? "none" : s.zn ? "zn" : "llr");
+                      !p->ct->coded || s.rx == RX_NONE ? "none" : s.zn ? "zn" : "llr");
   } else {
     const MimoPath s = p->f64 ? select_mimo<double>(p, a, knobs) : select_mimo<float>(p, a, knobs);
     char ch[48];   // the channel pass: fused into the TX, k_channel_mimo, or k_channel_tay with its form
@@ -2176,7 +2159,7 @@ int lte_run_path(const lte_plan* p, const lte_run_args* a, char* buf, int len) {
       std::snprintf(ch, sizeof ch, "%s", s.ch_sep ? "k_channel_mimo" : "fused");
     n = std::snprintf(buf, len, "tx=%s lp_fuse=%d ch=%s link_merge=%d rx=%s h_pilots=%d det_stage=%d dematch=%s",
                       MIMO_TX_NAME[s.tx], s.lp_fuse, ch, s.sfbc_merge, MIMO_RX_NAME[s.rx], s.h_pilots, s.det_stage,
-                      !chain_is_coded(p->d.chain) ? "none" : s.zn ? "zn" : "llr");
+                      !p->ct->coded ? "none" : s.zn ? "zn" : "llr");
   }
   // the decoder family is named only when it is not the default one
   if (p->early_stop && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " turbo=es");

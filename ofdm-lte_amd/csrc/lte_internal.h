@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/lte_phy.h"
+#include "lte_chain.h"
 #include "lte_common.h"
 #include "lte_knobs.h"
 #include "lte_dispatch.h"
@@ -301,8 +302,7 @@ int launch_rsc(hipStream_t s, int64_t n, const uint8_t* u, int term, uint8_t* sy
 
 // ---------------------------------------------------------------- multi-antenna chains
 // SFBC 2xN (configs 4 / simulate_miso / simulate_mimo) and TM4 spatial
-// multiplexing (config 5 and its generalisation).  lte_mimo.hip.
-enum { MIMO_SFBC = 0, MIMO_SPATIAL = 1 };
+// multiplexing (config 5 and its generalisation).  lte_mimo.hip.  (MIMO_SFBC / MIMO_SPATIAL: lte_chain.h)
 // terms per fading coefficient set: h(c + d) = sum_k c_k d^k, d in samples from
 // the set's centre (f32: degree 2; f64: degree 5, remainder under float64 rounding)
 template <class R> constexpr int mimo_ncf() { return sizeof(R) == 8 ? 6 : 3; }

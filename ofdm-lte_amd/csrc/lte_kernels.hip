@@ -1274,10 +1274,10 @@ __global__ __launch_bounds__(WG) void k_rx_data(Grid g, int rayleigh, int B, int
   constexpr R QS = (R)qam_norm<BPS>();
   constexpr int QM = 4;  // data REs per thread (Nd < N/2 for every LTE profile)
   // SIMO_CODED: the MRC sums of SIMO, then CODED's soft output with sigma^2 / D
-  constexpr bool FDE = (CHAIN & ~RX_EQ_ZF) == LTE_CHAIN_SCFDM_CODED, FDE_ZF = FDE && (CHAIN & RX_EQ_ZF) != 0;
-  static_assert(!FDE || SCF, "LTE_CHAIN_SCFDM_CODED de-precodes");
-  constexpr bool MRC = CHAIN == LTE_CHAIN_SIMO || CHAIN == LTE_CHAIN_SIMO_CODED || FDE;
-  constexpr bool SOFT = CHAIN == LTE_CHAIN_CODED || CHAIN == LTE_CHAIN_SIMO_CODED || FDE;
+  constexpr ChainTraits CT = chain_traits(CHAIN & ~RX_EQ_ZF);
+  constexpr bool FDE = CT.fde, FDE_ZF = FDE && (CHAIN & RX_EQ_ZF) != 0;
+  static_assert(SCF || CT.deprecode != PRECODE_ALWAYS, "this chain de-precodes");
+  constexpr bool MRC = CT.mrc, SOFT = CT.coded;
   constexpr int NRX = MRC ? 8 : 1;
   V num[QM];
   R den[QM];
@@ -1562,10 +1562,10 @@ __global__ __launch_bounds__(WG, RXF_WAVES) void k_rx_frame(Grid g, int rayleigh
         const V Y = cscale(buf[kpos[q]], sc);
         const V z = (CHAIN == LTE_CHAIN_UNCODED && g.no_eq) ? Y : zc[q].apply(Y);
         if (cap_syms) cap_syms[fre + re] = z;
-        if constexpr (CHAIN == LTE_CHAIN_CODED && ZN) {
+        if constexpr (chain_traits(CHAIN).coded && ZN) {
           // demap in k_dematch_zn: the equalised symbol (sigma^2_eff per subcarrier in nvo)
           reinterpret_cast<V*>(llr)[fre + re] = z;
-        } else if constexpr (CHAIN == LTE_CHAIN_CODED) {
+        } else if constexpr (chain_traits(CHAIN).coded) {
           store_llrs<R, BPS>(llr + (fre + re) * BPS, z, nvq[q]);
         } else {
           const int idx = hard_index(z, BPS, QS);
@@ -1581,11 +1581,12 @@ __global__ __launch_bounds__(WG, RXF_WAVES) void k_rx_frame(Grid g, int rayleigh
     }
     __syncthreads();   // every read of buf done before the next symbol lands in it
   }
-  if constexpr (CHAIN != LTE_CHAIN_CODED) frame_err_add(frame_err, b, errs);
+  if constexpr (!chain_traits(CHAIN).coded) frame_err_add(frame_err, b, errs);
 }
 
 bool rx_frame_supported(const Grid& g, int chain, int num_rx, int sc_fdm) {
-  return num_rx == 1 && !sc_fdm && (chain == LTE_CHAIN_CODED || chain == LTE_CHAIN_UNCODED) &&
+  const ChainTraits& ct = chain_traits(chain);   // the one-RX chains of the SISO family
+  return num_rx == 1 && !sc_fdm && ct.family == CHAIN_SISO && !ct.mrc &&
          (g.bps == 2 || g.bps == 4 || g.bps == 6) && 2 * g.Nd < g.N;
 }
 
@@ -1594,7 +1595,7 @@ int launch_rx_frame(hipStream_t s, const Grid& g, int chain, int rayleigh, int B
                     int64_t y_frame_stride, const R* npow, const R* snr_lin, const uint64_t* fid, uint64_t seed,
                     const R* inj_z, int64_t inj_stride, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
                     R* llr, cx<R>* cap_syms, uint8_t* cap_bits, R* nv_out, cx<R>* H, R* pstats) {
-  if (!rx_frame_supported(g, chain, 1, 0) || (nv_out && chain != LTE_CHAIN_CODED)) return (int)hipErrorInvalidValue;
+  if (!rx_frame_supported(g, chain, 1, 0) || (nv_out && !chain_traits(chain).zn)) return (int)hipErrorInvalidValue;
   const int spw = WG / (g.N >> 3);
   const int blocks = (B + spw - 1) / spw;
   const size_t shm = (size_t)spw * (g.N + g.Np) * sizeof(cx<R>);
@@ -1602,7 +1603,7 @@ int launch_rx_frame(hipStream_t s, const Grid& g, int chain, int rayleigh, int B
     with_bps(g.bps, [&](auto Q) {
       with_n<2048>(g.N, [&](auto NC) {   // 2048: the headline chain
         with_bool(nv_out != nullptr, [&](auto NV) {
-          constexpr bool ZN = CH() == LTE_CHAIN_CODED && NV();   // the (z, nv) hand-off is the coded chain's
+          constexpr bool ZN = chain_traits(CH()).zn && NV();   // the (z, nv) hand-off is the coded chain's
           hipLaunchKernelGGL((k_rx_frame<R, CH(), Q(), NC(), ZN>), dim3(blocks), dim3(WG), shm, s, g, rayleigh, B, y,
                              y_frame_stride, npow, snr_lin, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,
                              llr, cap_syms, cap_bits, nv_out, H, pstats);
@@ -2045,7 +2046,8 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
                    int n_bits, uint32_t* frame_err, R* llr, cx<R>* cap_syms, uint8_t* cap_bits, int sc_fdm,
                    R* nv_out, int eq_zf) {
   if (g.bps != 2 && g.bps != 4 && g.bps != 6) return (int)hipErrorInvalidValue;
-  if (chain == LTE_CHAIN_SCFDM_CODED) {   // one nv per OFDM symbol: LLRs only, no (z, nv) hand-off
+  const ChainTraits& ct = chain_traits(chain);
+  if (ct.fde) {   // one nv per OFDM symbol: LLRs only, no (z, nv) hand-off
     if (nv_out || !llr || !GridT<R>::chirp(g) || !GridT<R>::bhat(g) || 2 * g.Nd > g.N || num_rx < 1 || num_rx > 8)
       return (int)hipErrorInvalidValue;
     const int spw = WG / (g.N >> 3);
@@ -2061,10 +2063,10 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
       });
     }));
   }
-  if (nv_out && chain != LTE_CHAIN_CODED && chain != LTE_CHAIN_SIMO_CODED) return (int)hipErrorInvalidValue;
-  if (sc_fdm && (chain != LTE_CHAIN_UNCODED || !GridT<R>::chirp(g) || !GridT<R>::bhat(g)))
+  if (nv_out && !ct.zn) return (int)hipErrorInvalidValue;
+  if (sc_fdm && (ct.deprecode != PRECODE_FLAG || !GridT<R>::chirp(g) || !GridT<R>::bhat(g)))
     return (int)hipErrorInvalidValue;
-  if ((chain == LTE_CHAIN_SIMO || chain == LTE_CHAIN_SIMO_CODED) && num_rx > 8) return (int)hipErrorInvalidValue;
+  if (ct.mrc && num_rx > 8) return (int)hipErrorInvalidValue;
   const int spw = WG / (g.N >> 3);
   const int64_t total = (int64_t)B * g.n_sym;
   if (total > 0x7FFFFFFF - spw) return (int)hipErrorInvalidValue;
@@ -2075,7 +2077,7 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
     with_int_or<LTE_CHAIN_UNCODED, LTE_CHAIN_CODED, LTE_CHAIN_SIMO, LTE_CHAIN_SIMO_CODED>(chain, [&](auto CH) {
       with_bool(sc_fdm, [&](auto S) {
         with_n<2048>(g.N, [&](auto N) {
-          constexpr bool SCF = S() && CH() == LTE_CHAIN_UNCODED;   // SC-FDM is the uncoded chain's
+          constexpr bool SCF = S() && chain_traits(CH()).deprecode == PRECODE_FLAG;   // SC-FDM is the uncoded chain's
           constexpr int NC = CH() == LTE_CHAIN_CODED ? N() : 0;    // compile-time N: the headline chain
           hipLaunchKernelGGL((k_rx_data<R, CH(), Q(), SCF, NC>), dim3(blocks), dim3(WG), shm, s, g, rayleigh, B,
                              num_rx, y, y_rx_stride, y_frame_stride, H, npow, snr_lin, fid, seed, inj_z, inj_stride,

@@ -184,10 +184,10 @@ struct Plan {
   std::vector<uint32_t> hq_skip_h;   // hq_skip after the last round
   DBuf<int32_t> hq_zmap;             // decoder input rows (r << 24 | row) rv_seq[0]'s map leaves unwritten
   int hq_nz = 0;
-  // multi-antenna chains (lte_mimo.hip)
-  bool mimo = false;
+  // the chain's row of lte_chain.h (plan_create); mimo / bf: its family is run_mimo's / run_bf's
+  const ChainTraits* ct = nullptr;
+  bool mimo = false, bf = false;
   // beamforming chain (lte_bf.hip)
-  bool bf = false;
   int bf_ncb = 0;
   DBuf<double> bf_cb;
   DBuf<BfFrameT<float>> bf_fr;

@@ -286,8 +286,9 @@ void k_rx_frame_w(Grid g, int rayleigh, int B, const double2* __restrict__ y, in
 }
 
 bool rx_frame_w_supported(const Grid& g, int chain, int f64) {
-  return f64 && g.N == 2048 && chain == LTE_CHAIN_CODED && g.kinfo && g.pilots64 && g.cp % 2 == 0 && g.Np >= 1 &&
-         32 * g.Np <= wfft::LDS_DOUBLES * 8;
+  const ChainTraits& ct = chain_traits(chain);   // the one-RX SISO chain with the (z, nv) hand-off
+  return f64 && g.N == 2048 && ct.family == CHAIN_SISO && ct.zn && !ct.mrc && g.kinfo && g.pilots64 && g.cp % 2 == 0 &&
+         g.Np >= 1 && 32 * g.Np <= wfft::LDS_DOUBLES * 8;
 }
 
 // ---------------------------------------------------------------------------
@@ -627,8 +628,9 @@ void k_rx_frame_simo_w(Grid g, int B, int num_rx, int yrow, const double2* __res
 }
 
 bool rx_simo_w_supported(const Grid& g, int chain, int num_rx, int f64, bool H, bool pstats, bool xin) {
-  // uncoded only: LTE_CHAIN_SIMO_CODED's soft output is k_rx_frame_simo*'s
-  return chain == LTE_CHAIN_SIMO && f64 && g.N == 1024 && g.kinfo && g.pilots64 && g.cp % 2 == 0 && num_rx >= 1 &&
+  // the uncoded MRC chain only: the coded one's soft output is k_rx_frame_simo*'s
+  const ChainTraits& ct = chain_traits(chain);
+  return ct.mrc && !ct.coded && f64 && g.N == 1024 && g.kinfo && g.pilots64 && g.cp % 2 == 0 && num_rx >= 1 &&
          num_rx <= SIMOW_WAVES &&
          num_rx <= RXS_MAXRX && !H && !pstats && !xin && g.Nd <= 2 * 64 * SIMOW_WAVES && g.Np >= 1 &&
          (g.bps == 2 || g.bps == 4 || g.bps == 6);

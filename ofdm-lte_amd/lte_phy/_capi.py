@@ -6,7 +6,9 @@ visible, calls raise loudly.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
+import functools
 import os
 import threading
 
@@ -17,10 +19,13 @@ LIB_PATH = os.environ.get('LTE_HIP_LIB', os.path.join(_HERE, 'liblte_hip.so'))
 
 LTE_OK, LTE_EINVAL, LTE_EHIP, LTE_ENOMEM, LTE_ENODEV, LTE_EUNSUP = 0, -1, -2, -3, -4, -5
 CHAIN_UNCODED, CHAIN_CODED, CHAIN_SIMO, CHAIN_SFBC, CHAIN_SFBC_CODED, CHAIN_SPATIAL, CHAIN_BEAMFORMING = 0, 1, 2, 3, 4, 5, 6
-CHAIN_SIMO_CODED = 7   # 1 x num_rx MRC with turbo coding: a SISO-family chain numbered after the multi-antenna ones
+CHAIN_SIMO_CODED = 7   # 1 x num_rx MRC with turbo coding (SISO family)
 CHAIN_SPATIAL_CODED = 8   # TM4 spatial multiplexing with the soft MMSE / ZF / MRC detector and turbo coding
 CHAIN_SCFDM_CODED = 9   # coded SC-FDM: DFT precoder, soft MMSE / ZF frequency-domain equaliser, turbo coding (SISO family)
 CH_AWGN, CH_RAYLEIGH = 0, 1
+FAMILY_SISO, FAMILY_MIMO, FAMILY_BF = 0, 1, 2
+MODE_NONE, MODE_SFBC, MODE_SPATIAL = -1, 0, 1   # (chain_info's fields; the chains' traits: csrc/lte_chain.h)
+PRECODE_NEVER, PRECODE_FLAG, PRECODE_ALWAYS = 0, 1, 2
 DET_MMSE, DET_ZF, DET_SIC, DET_MRC = 0, 1, 2, 3
 STAGE_TX, STAGE_CHANNEL, STAGE_RX, STAGE_ALL = 1, 2, 4, 7
 MAX_PATHS = 16
@@ -74,6 +79,7 @@ _SIGS = {
     'lte_plan_create': (ctypes.c_int, [P(PlanDesc), P(ctypes.c_void_p)]),
     'lte_plan_destroy': (ctypes.c_int, [ctypes.c_void_p]),
     'lte_plan_info': (ctypes.c_int, [ctypes.c_void_p, P(c_i64)]),
+    'lte_chain_info': (ctypes.c_int, [ctypes.c_int, P(c_i32), ctypes.c_int]),
     'lte_plan_precision': (ctypes.c_int, [ctypes.c_void_p]),
     'lte_run': (ctypes.c_int, [ctypes.c_void_p, P(RunArgs)]),
     'lte_run_path': (ctypes.c_int, [ctypes.c_void_p, P(RunArgs), ctypes.c_char_p, ctypes.c_int]),
@@ -145,6 +151,8 @@ _SIGS = {
                                                P(c_f64), P(c_f64), P(c_f64)]),
 }
 
+ChainInfo = collections.namedtuple('ChainInfo', 'family coded mode precode')
+
 _lib = None
 _lock = threading.Lock()
 _device_ready = {}
@@ -192,6 +200,14 @@ def check(rc):
     if rc == LTE_EUNSUP:
         raise NotImplementedError(msg)
     raise RuntimeError(f"liblte_hip: {lib.lte_strerror(rc).decode()}: {msg}")
+
+
+@functools.lru_cache(maxsize=None)
+def chain_info(chain):
+    """(family, coded, mode, precode) of a chain value (lte_chain_info); no device needed."""
+    info = (c_i32 * 4)()
+    check(load().lte_chain_info(int(chain), info, 4))
+    return ChainInfo(*info)
 
 
 def device_init(device=None):

@@ -15,26 +15,14 @@ import numpy as np
 from . import _capi as C
 
 
-# Plan.coded / Plan.mimo by chain, as lte_plan_create classifies them: the coded
-# SIMO chain decodes but is a SISO-family chain (one TX, the SISO capture shapes)
-CODED_CHAINS = (C.CHAIN_CODED, C.CHAIN_SFBC_CODED, C.CHAIN_SIMO_CODED)
-MIMO_CHAINS = (C.CHAIN_SFBC, C.CHAIN_SFBC_CODED, C.CHAIN_SPATIAL)
-# The coded TM4 chain is both coded and multi-antenna.  It stands in a tuple of
-# its own: tests/test_simo_coded_host.py holds the two above to the chains that
-# existed with the coded SIMO chain.
-CODED_MIMO_CHAINS = (C.CHAIN_SPATIAL_CODED,)
-# The coded SC-FDM chain: coded, SISO family (one TX), likewise in a tuple of its own.
-CODED_SCFDM_CHAINS = (C.CHAIN_SCFDM_CODED,)
-
-
 def chain_is_coded(chain):
     """Plan.coded: the chain runs the coding chain (encoder, dematch, turbo, CRC)."""
-    return chain in CODED_CHAINS or chain in CODED_MIMO_CHAINS or chain in CODED_SCFDM_CHAINS
+    return bool(C.chain_info(chain).coded)
 
 
 def chain_is_mimo(chain):
     """Plan.mimo: a multi-antenna chain (run_mimo, the multi-antenna capture shapes)."""
-    return chain in MIMO_CHAINS or chain in CODED_MIMO_CHAINS
+    return C.chain_info(chain).family == C.FAMILY_MIMO
 
 
 class RunResult(dict):
@@ -108,9 +96,9 @@ class Plan:
         self.chain = chain
         self.num_tx = int(num_tx)
         self.coded = chain_is_coded(chain)
-        self.bf = chain == C.CHAIN_BEAMFORMING
+        self.bf = C.chain_info(chain).family == C.FAMILY_BF
         self.mimo = chain_is_mimo(chain)
-        sfbc = chain in (C.CHAIN_SFBC, C.CHAIN_SFBC_CODED)
+        sfbc = C.chain_info(chain).mode == C.MODE_SFBC
         # multi-antenna geometry (lte_capi.hip lte_plan_create): REs per OFDM symbol,
         # data SCs carrying data, channel estimates per frame
         self.res = (self.Nd & ~1) if sfbc else self.Nd

@@ -34,6 +34,12 @@ from .demodulator import OFDMDemodulator  # noqa: E402
 from .channel import AWGNChannel, FadingChannel, RayleighMultiPathChannel  # noqa: E402
 
 
+def _tf_deinterleave(n, Nd):
+    """Where coded QAM symbol q of n sits among the REs (T/F interleaver, core/ofdm_core.py:1040-1060, 1174-1207)."""
+    q = np.arange(n)
+    return (q % Nd) * -(-n // Nd) + q // Nd
+
+
 def _check_mode(mode, enable_sc_fdm):
     """OFDMModulator mode rule (core/modulator.py:128-131): enable_sc_fdm or
     mode 'sc-fdm' -> LTE mapping + DFT precoding.  Returns the SC-FDM flag."""
@@ -511,7 +517,7 @@ class OFDMSimulator:
         the reference does (lte_plan_desc.sc_fdm, include/lte_phy.h).  The coded
         SC-FDM chain precodes whatever the flag says; `detector` is its equaliser."""
         cfg, ch = self.config, self.channels[0]
-        sc = int(self.tx.modulator.enable_sc_fdm and chain in (C.CHAIN_UNCODED, C.CHAIN_SIMO))
+        sc = int(self.tx.modulator.enable_sc_fdm and C.chain_info(chain).precode == C.PRECODE_FLAG)
         # enable_equalization reaches simulate_siso's receiver only (the coded and SIMO
         # drivers build their own LTEReceivers, core/ofdm_core.py:1117-1122, 1369-1373)
         noeq = int(not self.enable_equalization and chain == C.CHAIN_UNCODED)
@@ -537,6 +543,29 @@ class OFDMSimulator:
         if bits.size == 0:
             raise ValueError("Bits array cannot be empty")
         return bits
+
+    def _run_coded(self, plan, bits, snr_db, num_rx=1, capture=()):
+        """The coded SISO-family drivers' shared part: the reference's draws and the one GPU call.  Returns (run
+        result, the leading result keys, the TX QAM symbols de-interleaved, the RX T/F de-interleave index)."""
+        ph, z = self._ref_draws(plan.L, num_rx)
+        r = plan.run([snr_db], bits=(bits & 1).astype(np.uint8)[None], phases=ph[None] if ph.size else None,
+                     noise=z[None], capture=('signal_tx', 'signal_rx', 'data_syms', 'bits_rx', 'tx_syms', 'H') + capture)
+        n0, bps, coded = len(bits), self.config.bits_per_symbol, plan.coded_bits
+        dec = r['bits_rx'][0].astype(np.uint8)
+        err = int(np.sum(bits != dec))
+        sig_tx = r['signal_tx'][0].astype(np.complex128)
+        pa = papr(sig_tx)
+        qam = r['tx_syms'][0].astype(np.complex128)[_tf_deinterleave(-(-coded // bps), self.Nd)]
+        head = {'transmitted_bits': int(n0), 'received_bits': int(n0), 'bits_received_array': dec,
+                'bit_errors': err, 'ber': float(err / n0), 'crc_pass': bool(r['crc_ok'][0]),
+                'snr_db': float(snr_db), 'papr_db': float(pa['papr_db']), 'papr_linear': float(pa['papr_linear']),
+                'coded_bits_length': int(coded), 'signal_tx': sig_tx}
+        return r, head, qam, _tf_deinterleave(coded // bps, self.Nd)
+
+    def _mrc_gain(self, r, num_rx):
+        """D = sum_r |H_r|^2 [n_grp][Nd] on the data subcarriers, from the captured H, in the combiner's RX order."""
+        Hs = r['H'][0].astype(np.complex128)
+        return sum(np.abs(Hs[a][:, self.grid._data]) ** 2 for a in range(num_rx))
 
     # -------------------------------------------------------------- SISO
     def simulate_siso(self, bits: np.ndarray, snr_db: float = 10.0) -> Dict:
@@ -582,26 +611,7 @@ class OFDMSimulator:
         bits = self._bits_in(bits)
         n0 = len(bits)
         plan = self._plan(C.CHAIN_CODED, 0, n0, iters=8)
-        ph, z = self._ref_draws(plan.L)
-        r = plan.run([snr_db], bits=(bits & 1).astype(np.uint8)[None], phases=ph[None] if ph.size else None,
-                     noise=z[None], capture=('signal_tx', 'signal_rx', 'data_syms', 'bits_rx', 'tx_syms',
-                                             'H', 'pilot_stats'))
-        cfg = self.config
-        bps, Nd = cfg.bits_per_symbol, self.Nd
-        coded = plan.coded_bits
-        dec = r['bits_rx'][0].astype(np.uint8)
-        err = int(np.sum(bits != dec))
-        sig_tx = r['signal_tx'][0].astype(np.complex128)
-        pa = papr(sig_tx)
-        # T/F de-interleave of the captured TX / RX REs (core/ofdm_core.py:1040-1060, 1174-1207)
-        ncs_tx = -(-coded // bps)
-        rows = -(-ncs_tx // Nd)
-        q = np.arange(ncs_tx)
-        qam = r['tx_syms'][0].astype(np.complex128)[(q % Nd) * rows + q // Nd]
-        ncs = coded // bps
-        rows_rx = -(-ncs // Nd)
-        q = np.arange(ncs)
-        src = (q % Nd) * rows_rx + q // Nd
+        r, res, qam, src = self._run_coded(plan, bits, snr_db, capture=('pilot_stats',))
         sy = r['data_syms'][0].astype(np.complex128)
         Hs = r['H'][0, 0].astype(np.complex128)                        # [n_grp][N]
         Hd = np.concatenate([Hs[l // SLOT_SIZE][self.grid._data] for l in range(plan.n_sym)])
@@ -613,12 +623,8 @@ class OFDMSimulator:
             nv = np.maximum(s2 / np.clip(np.abs(hd) ** 2, 1e-6, 1e6), s2 / 4.0)
         st = r['pilot_stats'][0, 0].astype(np.float64)
         ch_snr = float(np.mean(10 * np.log10(st[:, 0] / (st[:, 1] + 1e-10) + 1e-10)))
-        res = {'transmitted_bits': int(n0), 'received_bits': int(n0), 'bits_received_array': dec,
-               'bit_errors': err, 'ber': float(err / n0), 'crc_pass': bool(r['crc_ok'][0]),
-               'snr_db': float(snr_db), 'papr_db': float(pa['papr_db']), 'papr_linear': float(pa['papr_linear']),
-               'coded_bits_length': int(coded), 'signal_tx': sig_tx,
-               'signal_rx': r['signal_rx'][0, 0].astype(np.complex128), 'symbols_tx': qam, 'symbols_rx': sd,
-               'H_estimate': hd, 'channel_snr_db': ch_snr, 'noise_var_mean': float(np.mean(nv))}
+        res.update({'signal_rx': r['signal_rx'][0, 0].astype(np.complex128), 'symbols_tx': qam, 'symbols_rx': sd,
+                    'H_estimate': hd, 'channel_snr_db': ch_snr, 'noise_var_mean': float(np.mean(nv))})
         self.last_results = res
         return res
 
@@ -673,39 +679,15 @@ class OFDMSimulator:
             raise ValueError("num_rx must be >= 1")
         n0 = len(bits)
         plan = self._plan(C.CHAIN_SIMO_CODED, 0, n0, num_rx=num_rx, iters=8)
-        ph, z = self._ref_draws(plan.L, num_rx)
-        r = plan.run([snr_db], bits=(bits & 1).astype(np.uint8)[None], phases=ph[None] if ph.size else None,
-                     noise=z[None], capture=('signal_tx', 'signal_rx', 'data_syms', 'bits_rx', 'tx_syms', 'H'))
-        bps, Nd = self.config.bits_per_symbol, self.Nd
-        coded = plan.coded_bits
-        dec = r['bits_rx'][0].astype(np.uint8)
-        err = int(np.sum(bits != dec))
-        sig_tx = r['signal_tx'][0].astype(np.complex128)
-        pa = papr(sig_tx)
-        # T/F de-interleave of the captured TX / RX REs, as simulate_siso_coded
-        ncs_tx = -(-coded // bps)
-        rows = -(-ncs_tx // Nd)
-        q = np.arange(ncs_tx)
-        qam = r['tx_syms'][0].astype(np.complex128)[(q % Nd) * rows + q // Nd]
-        ncs = coded // bps
-        rows_rx = -(-ncs // Nd)
-        q = np.arange(ncs)
-        src = (q % Nd) * rows_rx + q // Nd
-        Hs = r['H'][0].astype(np.complex128)                           # [num_rx][n_grp][N]
-        Dg = np.zeros((plan.n_grp, Nd))
-        for a in range(num_rx):                                        # RX order, as the combiner sums
-            Dg += np.abs(Hs[a][:, self.grid._data]) ** 2
+        r, res, qam, src = self._run_coded(plan, bits, snr_db, num_rx)
+        Dg = self._mrc_gain(r, num_rx)
         gain = np.concatenate([Dg[l // SLOT_SIZE] for l in range(plan.n_sym)])[src]
         s2 = 1.0 / (10 ** (snr_db / 10))
         nv = np.maximum(s2 / np.clip(gain, 1e-6, 1e6), s2 / 4.0)
-        res = {'transmitted_bits': int(n0), 'received_bits': int(n0), 'bits_received_array': dec,
-               'bit_errors': err, 'ber': float(err / n0), 'crc_pass': bool(r['crc_ok'][0]),
-               'snr_db': float(snr_db), 'papr_db': float(pa['papr_db']), 'papr_linear': float(pa['papr_linear']),
-               'coded_bits_length': int(coded), 'signal_tx': sig_tx,
-               'signal_rx_list': [r['signal_rx'][0, i].astype(np.complex128) for i in range(num_rx)],
-               'symbols_tx': qam, 'symbols_rx': r['data_syms'][0].astype(np.complex128)[src],
-               'channel_gain': gain, 'noise_var_mean': float(np.mean(nv)), 'num_rx': num_rx,
-               'combining_method': 'mrc'}
+        res.update({'signal_rx_list': [r['signal_rx'][0, i].astype(np.complex128) for i in range(num_rx)],
+                    'symbols_tx': qam, 'symbols_rx': r['data_syms'][0].astype(np.complex128)[src],
+                    'channel_gain': gain, 'noise_var_mean': float(np.mean(nv)), 'num_rx': num_rx,
+                    'combining_method': 'mrc'})
         self.last_results = res
         return res
 
@@ -738,28 +720,8 @@ class OFDMSimulator:
         eq, det = self._scfdm_equalizer(equalizer)
         n0 = len(bits)
         plan = self._plan(C.CHAIN_SCFDM_CODED, 0, n0, num_rx=num_rx, iters=8, detector=det)
-        ph, z = self._ref_draws(plan.L, num_rx)
-        r = plan.run([snr_db], bits=(bits & 1).astype(np.uint8)[None], phases=ph[None] if ph.size else None,
-                     noise=z[None], capture=('signal_tx', 'signal_rx', 'data_syms', 'bits_rx', 'tx_syms', 'H'))
-        bps, Nd = self.config.bits_per_symbol, self.Nd
-        coded = plan.coded_bits
-        dec = r['bits_rx'][0].astype(np.uint8)
-        err = int(np.sum(bits != dec))
-        sig_tx = r['signal_tx'][0].astype(np.complex128)
-        pa = papr(sig_tx)
-        # T/F de-interleave of the captured TX / RX symbols, as simulate_siso_coded
-        ncs_tx = -(-coded // bps)
-        rows = -(-ncs_tx // Nd)
-        q = np.arange(ncs_tx)
-        qam = r['tx_syms'][0].astype(np.complex128)[(q % Nd) * rows + q // Nd]
-        ncs = coded // bps
-        rows_rx = -(-ncs // Nd)
-        q = np.arange(ncs)
-        src = (q % Nd) * rows_rx + q // Nd
-        Hs = r['H'][0].astype(np.complex128)                           # [num_rx][n_grp][N]
-        Dg = np.zeros((plan.n_grp, Nd))
-        for a in range(num_rx):                                        # RX order, as the receiver sums
-            Dg += np.abs(Hs[a][:, self.grid._data]) ** 2
+        r, res, qam, src = self._run_coded(plan, bits, snr_db, num_rx)
+        Nd, Dg = self.Nd, self._mrc_gain(r, num_rx)
         s2 = 1.0 / (10 ** (snr_db / 10))
         if eq == 'mmse':
             e = np.mean(s2 / (Dg + s2), axis=1)
@@ -767,15 +729,11 @@ class OFDMSimulator:
         else:
             nvg = s2 * np.mean(1.0 / np.clip(Dg, 1e-6, 1e6), axis=1)
         grp = np.arange(plan.n_sym) // SLOT_SIZE
-        res = {'transmitted_bits': int(n0), 'received_bits': int(n0), 'bits_received_array': dec,
-               'bit_errors': err, 'ber': float(err / n0), 'crc_pass': bool(r['crc_ok'][0]),
-               'snr_db': float(snr_db), 'papr_db': float(pa['papr_db']), 'papr_linear': float(pa['papr_linear']),
-               'coded_bits_length': int(coded), 'signal_tx': sig_tx,
-               'signal_rx_list': [r['signal_rx'][0, i].astype(np.complex128) for i in range(num_rx)],
-               'symbols_tx': qam, 'symbols_rx': r['data_syms'][0].astype(np.complex128)[src],
-               'channel_gain': np.concatenate([Dg[g] for g in grp])[src],
-               'noise_var_mean': float(np.mean(np.repeat(nvg[grp], Nd)[src])), 'num_rx': num_rx,
-               'combining_method': 'mrc', 'equalizer': eq}
+        res.update({'signal_rx_list': [r['signal_rx'][0, i].astype(np.complex128) for i in range(num_rx)],
+                    'symbols_tx': qam, 'symbols_rx': r['data_syms'][0].astype(np.complex128)[src],
+                    'channel_gain': np.concatenate([Dg[g] for g in grp])[src],
+                    'noise_var_mean': float(np.mean(np.repeat(nvg[grp], Nd)[src])), 'num_rx': num_rx,
+                    'combining_method': 'mrc', 'equalizer': eq})
         self.last_results = res
         return res
 
@@ -1292,10 +1250,7 @@ def simulate_spatial_multiplexing_coded(bits, num_tx=4, num_rx=2, rank='adaptive
         e = s2 * np.real(np.diagonal(np.linalg.inv(A + s2 * np.eye(rank_used)), axis1=-2, axis2=-1))
         nv = e / np.maximum(1.0 - e, 1e-6)
     nv = nv.reshape(plan.n_sym, -1)[:, :Nd].reshape(-1)                # RE R j + t of each symbol, cut at Nd
-    ncs = plan.coded_bits // bps
-    rows_rx = -(-ncs // Nd)
-    q = np.arange(ncs)
-    src = (q % Nd) * rows_rx + q // Nd                                 # T/F de-interleave, as simulate_siso_coded
+    src = _tf_deinterleave(plan.coded_bits // bps, Nd)                 # as simulate_siso_coded
     return {'transmitted_bits': int(n0), 'received_bits': int(n0), 'bits_received_array': dec,
             'bit_errors': err, 'ber': float(err / n0), 'crc_pass': bool(out['crc_ok'][0]), 'snr_db': float(snr_db),
             'coded_bits_length': int(plan.coded_bits), 'symbols_rx': out['data_syms'][0].astype(np.complex128)[src],

@@ -33,11 +33,7 @@ def test_header_and_binding_name_the_chain(C):
     assert re.search(r'^#define LTE_ABI_VERSION 3$', text, re.M)      # an additive value: no new version
     assert C.CHAIN_SCFDM_CODED == 9 and C.load().lte_version() == 3 and C.ABI_VERSION == 3
     from lte_phy import engine
-    assert engine.CODED_SCFDM_CHAINS == (C.CHAIN_SCFDM_CODED,)
     assert engine.chain_is_coded(9) and not engine.chain_is_mimo(9)  # Plan.coded, Plan.mimo: one TX, SISO captures
-    assert set(engine.CODED_CHAINS) == {C.CHAIN_CODED, C.CHAIN_SFBC_CODED, C.CHAIN_SIMO_CODED}
-    assert set(engine.MIMO_CHAINS) == {C.CHAIN_SFBC, C.CHAIN_SFBC_CODED, C.CHAIN_SPATIAL}
-    assert engine.CODED_MIMO_CHAINS == (C.CHAIN_SPATIAL_CODED,)
     assert engine.chain_is_coded(C.CHAIN_CODED) and not engine.chain_is_coded(C.CHAIN_UNCODED)
 
 

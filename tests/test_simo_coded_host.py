@@ -59,11 +59,11 @@ def test_plan_create_knows_the_chain_without_a_device(C):
 
 
 def test_plan_classifies_the_chain_as_coded_siso_family(C):
+    """(Every chain's classification, the other chains' included: tests/test_chain_traits_host.py.)"""
     from lte_phy import engine
-    assert C.CHAIN_SIMO_CODED in engine.CODED_CHAINS            # Plan.coded
-    assert C.CHAIN_SIMO_CODED not in engine.MIMO_CHAINS         # Plan.mimo: one TX, the SISO capture shapes
-    assert set(engine.CODED_CHAINS) == {C.CHAIN_CODED, C.CHAIN_SFBC_CODED, C.CHAIN_SIMO_CODED}
-    assert set(engine.MIMO_CHAINS) == {C.CHAIN_SFBC, C.CHAIN_SFBC_CODED, C.CHAIN_SPATIAL}
+    assert engine.chain_is_coded(C.CHAIN_SIMO_CODED)            # Plan.coded
+    assert not engine.chain_is_mimo(C.CHAIN_SIMO_CODED)         # Plan.mimo: one TX, the SISO capture shapes
+    assert C.chain_info(C.CHAIN_SIMO_CODED).family == C.FAMILY_SISO
 
 
 def test_simulate_simo_coded_signature_and_refusal():

@@ -31,7 +31,6 @@ def test_header_and_binding_name_the_chain(C):
     assert re.search(r'^#define LTE_ABI_VERSION 3$', text, re.M)      # an additive value: no new version
     assert C.CHAIN_SPATIAL_CODED == 8 and C.load().lte_version() == 3
     from lte_phy import engine
-    assert engine.CODED_MIMO_CHAINS == (C.CHAIN_SPATIAL_CODED,)
     assert engine.chain_is_coded(C.CHAIN_SPATIAL_CODED) and engine.chain_is_mimo(C.CHAIN_SPATIAL_CODED)   # Plan.coded, .mimo
     assert engine.chain_is_coded(C.CHAIN_SIMO_CODED) and not engine.chain_is_mimo(C.CHAIN_SIMO_CODED)
     assert engine.chain_is_mimo(C.CHAIN_SPATIAL) and not engine.chain_is_coded(C.CHAIN_SPATIAL)
