@@ -323,6 +323,27 @@ int lte_run_path(const lte_plan *plan, const lte_run_args *args, char *buf, int 
  * holds.  lte_run_path appends " turbo=es" for such a plan. */
 int lte_plan_set_early_stop(lte_plan *plan, int on);
 int lte_plan_early_stop(const lte_plan *plan);   /* 1 / 0 */
+/* Re-packing of the undecided blocks (ABI 3, additions; opt-in, needs early
+ * stop on).  With a boundary `after`, 1 <= after < turbo_iters, the decode runs
+ * as above up to and including the CRC check of D(after); the blocks still
+ * undecided then are copied, in ascending (frame, code block slot) order per
+ * slot, into dense 64-block groups of a second, smaller set of decoder arrays
+ * (max(1, ceil(G / 4)) groups per slot, G = ceil(max_frames / 64)), only those
+ * groups run the remaining iterations, and their decisions and n* go back to
+ * the blocks' own places.  A slot whose undecided blocks do not fit, or are all
+ * of its blocks, continues in place; one with none runs nothing more.  Every
+ * output of lte_run is bit for bit that of the same plan without re-packing.
+ * after = 0 switches it off (nothing is freed); lte_plan_set_early_stop(plan,
+ * 0) clears it too.  LTE_EINVAL: NULL plan, early stop off, after outside
+ * 0..turbo_iters-1.  lte_run_path appends " repack=<after>" after " turbo=es". */
+int lte_plan_set_early_stop_repack(lte_plan *plan, int after);
+int lte_plan_early_stop_repack(const lte_plan *plan);   /* after, or 0 */
+/* info [n] of the last lte_run: after, n_cb, then per code block slot the
+ * blocks undecided at the boundary, the 64-block groups that ran the remaining
+ * iterations, and 0 / 1 / 2 = nothing left / packed / continued in place
+ * (zeros before the first run); entries past n are dropped.  Returns the full
+ * length 2 + 3 n_cb.  LTE_EINVAL when re-packing is off. */
+int lte_plan_repack_info(const lte_plan *plan, int64_t *info, int n);
 /* n* of the plan's last lte_run, [n_frames][n_cb] bytes (n = n_frames * n_cb);
  * LTE_EINVAL when early stop is off, nothing has run since it was set, or n
  * is not that run's size. */
@@ -453,6 +474,15 @@ int lte_turbo_decode_es_host64(int K, int iters, int64_t ncb, const double *llr 
                                uint8_t *bits, uint8_t *iters_used);
 int lte_turbo_decode_es_host(int K, int iters, int64_t ncb, const float *llr /*[ncb][3K+12]*/, uint32_t crc_poly,
                              uint8_t *bits, uint8_t *iters_used);
+/* The two entries above with re-packing at the boundary `after`
+ * (lte_plan_set_early_stop_repack; 1 <= after < iters, LTE_EINVAL otherwise):
+ * the same bits and iters_used; info [3] = blocks undecided at the boundary,
+ * groups that ran the remaining iterations, 0 / 1 / 2 as lte_plan_repack_info.
+ * The packed arrays hold max(1, ceil(ceil(ncb / 64) / 4)) groups. */
+int lte_turbo_decode_es_repack_host64(int K, int iters, int64_t ncb, const double *llr /*[ncb][3K+12]*/,
+                                      uint32_t crc_poly, int after, uint8_t *bits, uint8_t *iters_used, int64_t *info);
+int lte_turbo_decode_es_repack_host(int K, int iters, int64_t ncb, const float *llr /*[ncb][3K+12]*/,
+                                    uint32_t crc_poly, int after, uint8_t *bits, uint8_t *iters_used, int64_t *info);
 /* float64 single BCJR pass of any length n, a-posteriori output for every step:
  * LogMAPDecoder.decode (turbo_decoder.py:181-278) with return_extrinsic=False.
  * n = 0 is valid (nothing written), like the reference's zero-step recursion. */

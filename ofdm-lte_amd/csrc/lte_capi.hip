@@ -355,8 +355,34 @@ int plan_launch_turbo(lte_plan* p, hipStream_t s, const std::vector<TurboJob>& j
   std::vector<int> nv(p->C, B);
   for (int r = 0; r < p->C; ++r) used[r] = p->es_used[r].p;
   p->es_frames = B;
-  return launch_turbo_jobs_es(s, jobs.data(), used.data(), nv.data(), p->C, p->d.turbo_iters, f64,
-                              p->C == 1 ? CRC24A_POLY : CRC24B_POLY);
+  const uint32_t poly = p->C == 1 ? CRC24A_POLY : CRC24B_POLY;
+  if (!p->repack_after)
+    return launch_turbo_jobs_es(s, jobs.data(), used.data(), nv.data(), p->C, p->d.turbo_iters, f64, poly);
+  // re-packing: the undecided blocks continue in the plan's packed arrays
+  std::vector<TurboPack> pk(p->C);
+  const int cap = turbo_pack_cap((p->d.max_frames + 63) / 64);
+  for (int r = 0; r < p->C; ++r) {
+    void* pb = f64 ? (void*)p->c64.pk_blk[r].p : (void*)p->c32.pk_blk[r].p;
+    void* pc = f64 ? (void*)p->c64.pk_ckpt[r].p : (void*)p->c32.pk_ckpt[r].p;
+    pk[r] = TurboPack{pb, pc, p->pk_decb[r].p, p->pk_used[r].p, p->pk_idx[r].p, cap};
+  }
+  p->rp_last.assign((size_t)3 * p->C, 0);
+  return launch_turbo_jobs_es_repack(s, jobs.data(), used.data(), nv.data(), p->C, p->d.turbo_iters, f64, poly,
+                                     p->repack_after, pk.data(), p->rp_cnt.p, p->rp_last.data());
+}
+
+// the packed rows / checkpoints of re-packing, cap groups per CB slot (true: out of memory)
+template <class R>
+bool alloc_packed(lte_plan* p, ChainBufs<R>& c, int cap) {
+  bool bad = false;
+  c.pk_blk.resize(p->C);
+  c.pk_ckpt.resize(p->C);
+  for (int r = 0; r < p->C; ++r) {
+    const int K = p->cbs[r].K;
+    bad |= c.pk_blk[r].alloc((size_t)turbo_galloc(cap) * turbo_rows(K) * 64) != 0;
+    bad |= c.pk_ckpt[r].alloc((size_t)turbo_galloc(cap) * turbo_nwin(K) * turbo_ck_rows(sizeof(R) == 8) * 64) != 0;
+  }
+  return bad;
 }
 
 void collect_timing(lte_plan* p) {
@@ -1136,7 +1162,52 @@ int lte_plan_set_early_stop(lte_plan* p, int on) {
   if (on && p->d.turbo_iters > 255) return fail(LTE_EUNSUP, "early stop reports iterations as bytes: turbo_iters <= 255");
   p->early_stop = on != 0;
   p->es_frames = 0;
+  if (!on) p->repack_after = 0;
   return LTE_OK;
+}
+
+int lte_plan_set_early_stop_repack(lte_plan* p, int after) {
+  if (!p) return fail(LTE_EINVAL, "null plan");
+  if (!p->early_stop) return fail(LTE_EINVAL, "re-packing needs early stop (lte_plan_set_early_stop) on this plan");
+  if (after < 0 || after >= p->d.turbo_iters)
+    return fail(LTE_EINVAL, "re-packing boundary must be in 1..turbo_iters-1 (0 switches it off): after = " +
+                                std::to_string(after) + ", turbo_iters = " + std::to_string(p->d.turbo_iters));
+  if (after && p->pk_decb.empty()) {
+    const int cap = turbo_pack_cap((p->d.max_frames + 63) / 64);
+    std::vector<DBuf<uint32_t>> b(p->C), u(p->C), x(p->C);
+    bool bad = p->f64 ? alloc_packed(p, p->c64, cap) : alloc_packed(p, p->c32, cap);
+    for (int r = 0; r < p->C; ++r) {
+      bad |= b[r].alloc((size_t)cap * turbo_kw(p->cbs[r].K) * 64) != 0;
+      bad |= u[r].alloc((size_t)cap * 64) != 0;
+      bad |= x[r].alloc((size_t)cap * 64) != 0;
+    }
+    bad |= p->rp_cnt.alloc(p->C) != 0;
+    if (bad) {
+      p->c64.pk_blk.clear(); p->c64.pk_ckpt.clear();
+      p->c32.pk_blk.clear(); p->c32.pk_ckpt.clear();
+      return fail(LTE_ENOMEM, "re-packing arrays");
+    }
+    p->pk_decb.swap(b);
+    p->pk_used.swap(u);
+    p->pk_idx.swap(x);
+  }
+  p->repack_after = after;
+  p->rp_last.assign((size_t)3 * p->C, 0);
+  return LTE_OK;
+}
+
+int lte_plan_early_stop_repack(const lte_plan* p) {
+  if (!p) return fail(LTE_EINVAL, "null plan");
+  return p->repack_after;
+}
+
+int lte_plan_repack_info(const lte_plan* p, int64_t* info, int n) {
+  if (!p || !info) return fail(LTE_EINVAL, "null argument");
+  if (!p->repack_after) return fail(LTE_EINVAL, "re-packing is off for this plan");
+  std::vector<int64_t> v = {p->repack_after, p->C};
+  for (int i = 0; i < 3 * p->C; ++i) v.push_back(i < (int)p->rp_last.size() ? p->rp_last[i] : 0);
+  for (int i = 0; i < n && i < (int)v.size(); ++i) info[i] = v[i];
+  return (int)v.size();
 }
 
 int lte_plan_early_stop(const lte_plan* p) {
@@ -2163,6 +2234,8 @@ int lte_run_path(const lte_plan* p, const lte_run_args* a, char* buf, int len) {
   }
   // the decoder family is named only when it is not the default one
   if (p->early_stop && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " turbo=es");
+  if (p->early_stop && p->repack_after && n >= 0 && n < len)
+    n += std::snprintf(buf + n, len - n, " repack=%d", p->repack_after);
   if (p->harq && n >= 0 && n < len)
     n += std::snprintf(buf + n, len - n, " harq=t%d,rv%d,skip=%d", p->hq_round, p->hq.rv_seq[p->hq_round],
                        select_siso(p, a, knobs).hq_skip ? 1 : 0);

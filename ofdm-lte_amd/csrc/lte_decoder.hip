@@ -623,8 +623,19 @@ struct TurboEs {
   uint32_t poly;                    // CRC-24 generator without x^24
 };
 
-template <class T, int CH>
-__device__ __forceinline__ void turbo_body_es(const TurboJobs& jobs, const TurboEs& es, int iters, uint32_t* crc_t) {
+// WIN (the re-packing kernels k_turbo*_esw): the decode runs in
+// two windows split at the boundary win.after, 1 <= after < iters.  The first
+// window (resume = 0) runs as above up to and including the check of D(after);
+// a lane still undecided there stores TURBO_UNDECIDED as its iteration count,
+// so "done" is in memory: a lane is done iff its count is another value.  The
+// second window (resume = 1) reads that back, starts with the decoder-2 pass
+// of it = after and goes on as above.  A block's state at the boundary is its
+// rows (LE as decoder 1 left it); the checkpoints are scratch.  (TurboWin:
+// lte_internal.h)
+
+template <class T, int CH, bool WIN = false>
+__device__ __forceinline__ void turbo_body_es(const TurboJobs& jobs, const TurboEs& es, int iters, uint32_t* crc_t,
+                                              TurboWin win = {}) {
   crc24_slice4_fill(crc_t, es.poly);
   __syncthreads();   // the only barrier (one wave)
   const int wg = blockIdx.x;
@@ -642,28 +653,46 @@ __device__ __forceinline__ void turbo_body_es(const TurboJobs& jobs, const Turbo
   const RowPtr<uint32_t> words{make_rsrc(bo, (uint32_t)(kw * RS * 4)), 0, lane * 4};
   const RowPtr<uint32_t> used{make_rsrc(es.used[r] + (size_t)g * RS, (uint32_t)(RS * 4)), 0, lane * 4};
   bool done = g * RS + lane >= es.nv[r];
+  int it = 0;
+  bool resumed = false;   // the second window enters at its decoder-2 pass
+  if constexpr (WIN) {
+    if (win.resume) {
+      done = done || used.ld(0) != TURBO_UNDECIDED;
+      it = win.after;
+      resumed = true;
+    }
+  }
   if (__builtin_amdgcn_ballot_w64(!done) == 0) return;
-  for (int it = 0;; ++it) {
-    // the decoder-1 pass of iteration it + 1 = the final pass after `it`
-    // iterations: from it = 1 on (and at it = iters, where the decode ends)
-    // its decisions are D(it)
-    const bool last = it == iters;
-    half_pass<T, TM_DEC1, false, CH, true>(base, ck, slot, lane, K, jb.f1, jb.f2, it == 0, bo,
-                                           !done && (it > 0 || last));
-    if (last) {
-      if (!done) used.st(0, (uint32_t)it);
-      return;
-    }
-    if (it > 0) {
-      uint32_t c = 0;
-#pragma unroll 4
-      for (int w = 0; w < kw; ++w) c = crc24_slice4(crc_t, c, words.ld(w));
-      if (!done && c == 0) {
-        used.st(0, (uint32_t)it);
-        done = true;
+  for (;; ++it) {
+    if (!(WIN && resumed)) {
+      // the decoder-1 pass of iteration it + 1 = the final pass after `it`
+      // iterations: from it = 1 on (and at it = iters, where the decode ends)
+      // its decisions are D(it)
+      const bool last = it == iters;
+      half_pass<T, TM_DEC1, false, CH, true>(base, ck, slot, lane, K, jb.f1, jb.f2, it == 0, bo,
+                                             !done && (it > 0 || last));
+      if (last) {
+        if (!done) used.st(0, (uint32_t)it);
+        return;
       }
-      if (__builtin_amdgcn_ballot_w64(!done) == 0) return;
+      if (it > 0) {
+        uint32_t c = 0;
+#pragma unroll 4
+        for (int w = 0; w < kw; ++w) c = crc24_slice4(crc_t, c, words.ld(w));
+        if (!done && c == 0) {
+          used.st(0, (uint32_t)it);
+          done = true;
+        }
+        if (__builtin_amdgcn_ballot_w64(!done) == 0) return;
+        if constexpr (WIN) {
+          if (!win.resume && it == win.after) {
+            if (!done) used.st(0, TURBO_UNDECIDED);
+            return;
+          }
+        }
+      }
     }
+    resumed = false;
     half_pass<T, TM_DEC2, false, CH>(base, ck, slot, lane, K, jb.f1, jb.f2, false);
   }
 }
@@ -688,6 +717,117 @@ __global__ __launch_bounds__(64, LTE_TURBO64_ONE_WAVE ? 1 : 2) void k_turbo64_es
   asm volatile("" ::: "a31");
 #endif
   turbo_body_es<double, CH>(jobs, es, iters, crc_t);
+}
+
+// The windowed early-stop decoders of re-packing: the bodies and register caps
+// of k_turbo_es / k_turbo64_es, one more kernel argument (as k_turbo64_skip is
+// to k_turbo64).
+template <int CH>
+__global__ __launch_bounds__(64, LTE_TURBO32_WAVES == 3 ? 2 : 1) void k_turbo_esw(TurboJobs jobs, TurboEs es,
+                                                                                    int iters, TurboWin win) {
+  __shared__ uint32_t crc_t[1024];
+#if LTE_TURBO32_WAVES == 2
+  asm volatile("" ::: "a47");
+#elif LTE_TURBO32_WAVES == 1
+  asm volatile("" ::: "a127");
+#endif
+  turbo_body_es<float, CH, true>(jobs, es, iters, crc_t, win);
+}
+
+template <int CH>
+__global__ __launch_bounds__(64, LTE_TURBO64_ONE_WAVE ? 1 : 2) void k_turbo64_esw(TurboJobs jobs, TurboEs es,
+                                                                                    int iters, TurboWin win) {
+  __shared__ uint32_t crc_t[1024];
+#if LTE_TURBO64_ONE_WAVE
+  asm volatile("" ::: "a31");
+#endif
+  turbo_body_es<double, CH, true>(jobs, es, iters, crc_t, win);
+}
+
+// ---------------------------------------------------------------------------
+// Re-packing of the blocks still undecided at the boundary.
+//
+// k_repack_index, one 1024-thread block per code-block slot: the slot's
+// undecided blocks (valid lanes whose count is TURBO_UNDECIDED) in ascending
+// (group, lane) order.  Wave w owns a contiguous run of groups; it counts its
+// run (ballot + popcount per group), the 16 run totals are prefix-summed, and
+// a second walk over the run gives every undecided lane its rank -- prefix
+// sums, no atomics, so the order does not depend on arrival.  idx[rank] =
+// group * 64 + lane for rank < cap (the packed arrays' lanes); *count takes
+// the total whether it fits or not.
+constexpr int RPK_WAVES = 16;
+__global__ __launch_bounds__(64 * RPK_WAVES) void k_repack_index(const uint32_t* __restrict__ used, int nv, int G,
+                                                                 uint32_t* __restrict__ idx, int cap,
+                                                                 uint32_t* __restrict__ count) {
+  __shared__ int tot[RPK_WAVES];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int per = (G + RPK_WAVES - 1) / RPK_WAVES;
+  const int g0 = min(G, w * per), g1 = min(G, g0 + per);
+  int n = 0;
+  for (int g = g0; g < g1; ++g) {
+    const bool u = g * RS + lane < nv && used[(size_t)g * RS + lane] == TURBO_UNDECIDED;
+    n += __builtin_popcountll(__builtin_amdgcn_ballot_w64(u));
+  }
+  if (lane == 0) tot[w] = n;
+  __syncthreads();
+  int base = 0, all = 0;
+  for (int i = 0; i < RPK_WAVES; ++i) {
+    if (i < w) base += tot[i];
+    all += tot[i];
+  }
+  if (threadIdx.x == 0) *count = (uint32_t)all;
+  for (int g = g0; g < g1; ++g) {
+    const bool u = g * RS + lane < nv && used[(size_t)g * RS + lane] == TURBO_UNDECIDED;
+    const uint64_t m = __builtin_amdgcn_ballot_w64(u);
+    const int rank = base + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+    if (u && rank < cap) idx[rank] = (uint32_t)(g * RS + lane);
+    base += __builtin_popcountll(m);
+  }
+}
+
+// k_repack_gather: block (j, y) fills packed group j's rows [y * RPK_ROWS,
+// (y + 1) * RPK_ROWS), four waves taking every fourth row.  Lane l of a row
+// reads element idx[j * 64 + l] of the same row of the source arrays (chunk
+// width sch) and the wave stores one whole row of the packed arrays (chunk
+// width dch); lanes past n store zeros, so the packed wave computes on defined
+// values.  A wave per destination group touches one 8-byte element per live
+// block and row, not the source group's whole 512-byte row for the one or two
+// stragglers it holds at the waterfall (the copy shape is argued in DESIGN.md
+// §5); the rows are spread over the grid because the destination groups alone
+// are a few dozen waves.  Block (j, 0) also marks the packed lanes undecided.
+constexpr int RPK_ROWS = 64;
+template <class T>
+__global__ __launch_bounds__(256) void k_repack_gather(const T* __restrict__ src, int sch, T* __restrict__ dst, int dch,
+                                                       int rows, const uint32_t* __restrict__ idx, int n,
+                                                       uint32_t* __restrict__ dused) {
+  const int j = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int d = j * RS + lane;
+  const bool on = d < n;
+  const uint32_t sidx = on ? idx[d] : 0u;
+  const int64_t sg = sidx >> 6;
+  const int sl = (int)(sidx & 63u);
+  if (blockIdx.y == 0 && w == 0) dused[d] = TURBO_UNDECIDED;
+  const int r1 = min(rows, ((int)blockIdx.y + 1) * RPK_ROWS);
+  for (int row = blockIdx.y * RPK_ROWS + w; row < r1; row += 4) {
+    const T v = on ? src[turbo_elem_ch(sch, rows, sg, row) + sl] : (T)0;
+    dst[turbo_elem_ch(dch, rows, j, row) + lane] = v;
+  }
+}
+
+// k_repack_scatter: the packed groups' decision words ([G'][kw][64]) and
+// iteration counts back to the blocks' own (group, lane); one thread per
+// packed block.
+__global__ __launch_bounds__(64) void k_repack_scatter(const uint32_t* __restrict__ pbits,
+                                                       const uint32_t* __restrict__ pused,
+                                                       const uint32_t* __restrict__ idx, int n, int kw,
+                                                       uint32_t* __restrict__ bits, uint32_t* __restrict__ used) {
+  const int j = blockIdx.x, lane = threadIdx.x;
+  const int d = j * RS + lane;
+  if (d >= n) return;
+  const uint32_t sidx = idx[d];
+  const size_t sg = sidx >> 6, sl = sidx & 63u;
+  for (int w = 0; w < kw; ++w) bits[(sg * kw + w) * RS + sl] = pbits[((size_t)j * kw + w) * RS + lane];
+  used[sg * RS + sl] = pused[d];
 }
 
 // decoder arithmetic of the f64 entry points and chains: max-log-MAP (the
@@ -738,9 +878,11 @@ int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int
 }
 
 // the early-stop decoders: used[i] / nv[i] per job (TurboEs), poly CRC24A_POLY / CRC24B_POLY
+// win set: one window of a re-packing decode (k_turbo*_esw)
 int launch_turbo_jobs_es(hipStream_t s, const TurboJob* jobs, uint32_t* const* used, const int* nv, int n, int iters,
-                         int f64, uint32_t poly) {
+                         int f64, uint32_t poly, const TurboWin* win) {
   if (g_logmap || iters < 0) return (int)hipErrorInvalidValue;   // max-log only (the callers refuse it first)
+  if (win && (win->after < 1 || win->after >= iters)) return (int)hipErrorInvalidValue;
   for (int o = 0; o < n; o += TURBO_MAX_JOBS) {
     TurboJobs J{};
     TurboEs E{};
@@ -759,15 +901,81 @@ int launch_turbo_jobs_es(hipStream_t s, const TurboJob* jobs, uint32_t* const* u
     for (int i = 1; i < J.n; ++i)
       if (J.j[i].ch != ch) return (int)hipErrorInvalidValue;
     const dim3 grid(waves), block(64);   // one wave per block (turbo_body_es)
-    const int e = launch_status(with_int<TURBO_CH, 1>(ch, [&](auto CH) {
-      with_bool(f64, [&](auto F64) {
-        if constexpr (F64()) hipLaunchKernelGGL(k_turbo64_es<CH()>, grid, block, 0, s, J, E, iters);
-        else hipLaunchKernelGGL(k_turbo_es<CH()>, grid, block, 0, s, J, E, iters);
-      });
+    auto with_form = [&](auto&& f) {
+      return with_int<TURBO_CH, 1>(ch, [&](auto CH) { with_bool(f64, [&](auto F64) { f(CH, F64); }); });
+    };
+    const int e = launch_status(win ? with_form([&](auto CH, auto F64) {
+      if constexpr (F64()) hipLaunchKernelGGL(k_turbo64_esw<CH()>, grid, block, 0, s, J, E, iters, *win);
+      else hipLaunchKernelGGL(k_turbo_esw<CH()>, grid, block, 0, s, J, E, iters, *win);
+    }) : with_form([&](auto CH, auto F64) {
+      if constexpr (F64()) hipLaunchKernelGGL(k_turbo64_es<CH()>, grid, block, 0, s, J, E, iters);
+      else hipLaunchKernelGGL(k_turbo_es<CH()>, grid, block, 0, s, J, E, iters);
     }));
     if (e) return e;
   }
   return 0;
+}
+
+// Early-stop decode with re-packing at the boundary `after`:
+// the first window on every job, the undecided blocks of each job indexed and
+// counted (one host read of n counts sizes what follows), then per job either
+// nothing, the gather into pk[i]'s arrays, or nothing to copy (in place); the
+// second window on the packed and the in-place jobs, one launch per chunk
+// width; the scatter of the packed jobs.  info: 3 per job (lte_internal.h).
+int launch_turbo_jobs_es_repack(hipStream_t s, const TurboJob* jobs, uint32_t* const* used, const int* nv, int n,
+                                int iters, int f64, uint32_t poly, int after, const TurboPack* pk, uint32_t* counts,
+                                int64_t* info) {
+  const TurboWin w0{after, 0}, w1{after, 1};
+  if (int e = launch_turbo_jobs_es(s, jobs, used, nv, n, iters, f64, poly, &w0)) return e;
+  for (int i = 0; i < n; ++i)
+    hipLaunchKernelGGL(k_repack_index, dim3(1), dim3(64 * RPK_WAVES), 0, s, used[i], nv[i], jobs[i].G, pk[i].idx,
+                       pk[i].cap * RS, counts + i);
+  if (int e = (int)hipGetLastError()) return e;
+  std::vector<uint32_t> cnt(n);
+  if (hipMemcpyAsync(cnt.data(), counts, n * sizeof(uint32_t), hipMemcpyDeviceToHost, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return (int)hipErrorUnknown;
+  // the second window's jobs, the packed arrays' chunk widths apart from the blocks' own
+  std::vector<TurboJob> rj[2];
+  std::vector<uint32_t*> ru[2];
+  std::vector<int> rn[2];
+  for (int i = 0; i < n; ++i) {
+    const int64_t u = cnt[i];
+    const bool pack = u > 0 && u <= (int64_t)pk[i].cap * RS && u < nv[i];
+    const int Gp = (int)((u + RS - 1) / RS);
+    info[3 * i] = u;
+    info[3 * i + 1] = u == 0 ? 0 : pack ? Gp : jobs[i].G;
+    info[3 * i + 2] = u == 0 ? TURBO_RP_NONE : pack ? TURBO_RP_PACKED : TURBO_RP_INPLACE;
+    if (u == 0) continue;
+    TurboJob j = jobs[i];
+    if (pack) {
+      const int64_t rows = turbo_rows(j.K);
+      const dim3 grid(Gp, (unsigned)((rows + RPK_ROWS - 1) / RPK_ROWS));
+      const int pch = turbo_chunk(pk[i].cap);
+      if (f64)
+        hipLaunchKernelGGL(k_repack_gather<double>, grid, dim3(256), 0, s, (const double*)j.blk, j.ch,
+                           (double*)pk[i].blk, pch, (int)rows, pk[i].idx, (int)u, pk[i].used);
+      else
+        hipLaunchKernelGGL(k_repack_gather<float>, grid, dim3(256), 0, s, (const float*)j.blk, j.ch, (float*)pk[i].blk,
+                           pch, (int)rows, pk[i].idx, (int)u, pk[i].used);
+      j = TurboJob{pk[i].blk, pk[i].ck, pk[i].bits, j.K, j.f1, j.f2, Gp, pch};
+    }
+    const int k = j.ch == 1 ? 0 : 1;
+    rj[k].push_back(j);
+    ru[k].push_back(pack ? pk[i].used : used[i]);
+    rn[k].push_back(pack ? (int)u : nv[i]);
+  }
+  if (int e = (int)hipGetLastError()) return e;
+  for (int k = 0; k < 2; ++k)
+    if (!rj[k].empty())
+      if (int e = launch_turbo_jobs_es(s, rj[k].data(), ru[k].data(), rn[k].data(), (int)rj[k].size(), iters, f64, poly,
+                                       &w1))
+        return e;
+  for (int i = 0; i < n; ++i)
+    if (info[3 * i + 2] == TURBO_RP_PACKED)
+      hipLaunchKernelGGL(k_repack_scatter, dim3((unsigned)info[3 * i + 1]), dim3(64), 0, s, pk[i].bits, pk[i].used,
+                         pk[i].idx, (int)info[3 * i], turbo_kw(jobs[i].K), jobs[i].bits, used[i]);
+  return (int)hipGetLastError();
 }
 
 int launch_turbo(hipStream_t s, void* blk, void* ckpt, uint32_t* bits, int K, int f1, int f2, int iters, int G,

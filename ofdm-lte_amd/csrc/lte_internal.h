@@ -265,8 +265,40 @@ int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int
 // have CRC-24 remainder zero over all K bits (poly: CRC24A_POLY / CRC24B_POLY).
 // used[i]: job i's iterations used, [G][64] words (lanes >= nv[i], the job's
 // code-block count, are never written, nor are their bits).
+// win set: one window of a re-packing decode (k_turbo64_esw / k_turbo_esw).
+// The first window (resume 0) stops after the check of D(after) and leaves
+// TURBO_UNDECIDED as the count of every block still undecided; the second
+// (resume 1) takes the blocks whose count is TURBO_UNDECIDED from the
+// decoder-2 pass of iteration after + 1 on.  1 <= after < iters.
+struct TurboWin {
+  int after, resume;
+};
+constexpr uint32_t TURBO_UNDECIDED = 0xFFFFFFFFu;
 int launch_turbo_jobs_es(hipStream_t s, const TurboJob* jobs, uint32_t* const* used, const int* nv, int n, int iters,
-                         int f64, uint32_t poly);
+                         int f64, uint32_t poly, const TurboWin* win = nullptr);
+// Early stop with the undecided blocks re-packed at the boundary `after`.
+// pk[i]: job i's packed arrays -- rows / checkpoints / decision words / counts
+// of cap groups laid out as the job's own (chunk width turbo_chunk(cap), so
+// turbo_galloc(cap) groups of rows and checkpoints), idx: cap * 64 words.
+// A job whose undecided blocks fit cap groups and are fewer than its blocks is
+// packed; another continues in place on its own arrays; one with none runs no
+// second window.  counts: n device words.  info: per job the blocks undecided
+// at the boundary, the groups the second window ran, and TURBO_RP_*.  Outputs
+// (decision words, used) are those of launch_turbo_jobs_es, bit for bit.
+// Synchronises the stream once (the counts size the second window).
+struct TurboPack {
+  void* blk;
+  void* ck;
+  uint32_t* bits;
+  uint32_t* used;
+  uint32_t* idx;
+  int cap;
+};
+enum { TURBO_RP_NONE = 0, TURBO_RP_PACKED = 1, TURBO_RP_INPLACE = 2 };
+inline int turbo_pack_cap(int64_t G) { return G > 4 ? (int)((G + 3) / 4) : 1; }
+int launch_turbo_jobs_es_repack(hipStream_t s, const TurboJob* jobs, uint32_t* const* used, const int* nv, int n,
+                                int iters, int f64, uint32_t poly, int after, const TurboPack* pk, uint32_t* counts,
+                                int64_t* info);
 // rate_dematching_turbo for any E (repeats summed in order): llr [ncb][E] -> out [ncb][n_out]
 int launch_rate_dematch(hipStream_t s, const double* llr, int E, int Ncb, int n_out, const int32_t* src0, int64_t ncb,
                         double* out);

@@ -101,6 +101,7 @@ struct ChainBufs {
   DBuf<cx<R>> Ym;
   DBuf<R> link_part, link_sigma, inj_lz, inj_lh;
   std::vector<DBuf<R>> blk, ckpt;
+  std::vector<DBuf<R>> pk_blk, pk_ckpt;   // re-packing: the packed rows / checkpoints per CB slot
   DBuf<R*> blk_ptrs;
 };
 
@@ -167,6 +168,16 @@ struct Plan {
   bool early_stop = false;
   std::vector<DBuf<uint32_t>> es_used;
   int es_frames = 0;
+  // Re-packing of the undecided blocks (lte_plan_set_early_stop_repack): the
+  // boundary (0: off); per CB slot the packed decision words [cap][kw][64],
+  // counts [cap][64] and source indices [cap * 64] (the packed rows and
+  // checkpoints are ChainBufs' pk_blk / pk_ckpt), cap = turbo_pack_cap of the
+  // plan's groups; rp_cnt: the slots' undecided counts; rp_last: the last
+  // run's (undecided, groups resumed, state) per slot
+  int repack_after = 0;
+  std::vector<DBuf<uint32_t>> pk_decb, pk_used, pk_idx;
+  DBuf<uint32_t> rp_cnt;
+  std::vector<int64_t> rp_last;
   // HARQ (lte_plan_create_harq).  tx_map / rx_map hold one map per distinct rv
   // of rv_seq back to back (n_re_bits entries each, hq_slot[rv] its index).
   // hq_round: the next lte_run's transmission; hq_done: last completed round

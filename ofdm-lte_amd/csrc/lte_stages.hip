@@ -673,9 +673,12 @@ int lte_turbo_encode_host(int K, int64_t ncb, const uint8_t* bits, uint8_t* out)
 // turbo entry points.  T = float (fast mode) / double (the reference's precision).
 // es_used set (mode TM_DEC1): the early-stop decoder with generator es_poly
 // (CRC24A_POLY / CRC24B_POLY), the iterations used per code block to es_used.
+// rp_after > 0: early stop with re-packing at that boundary (packed arrays of
+// turbo_pack_cap(G) groups), rp_info: undecided blocks, groups resumed, state.
 template <class T>
 static int turbo_host_run(int K, int iters, int64_t ncb, const T* llr, const T* ls, const T* lp, const T* la,
-                          int mode, uint8_t* bits, T* app, uint32_t es_poly = 0, uint8_t* es_used = nullptr) {
+                          int mode, uint8_t* bits, T* app, uint32_t es_poly = 0, uint8_t* es_used = nullptr,
+                          int rp_after = 0, int64_t* rp_info = nullptr) {
   int f1, f2;
   if (!qpp_lookup(K, &f1, &f2)) return fail(LTE_EINVAL, "Invalid interleaver size K=" + std::to_string(K));
   if (ncb < 0) return fail(LTE_EINVAL, "bad ncb");
@@ -716,13 +719,26 @@ static int turbo_host_run(int K, int iters, int64_t ncb, const T* llr, const T* 
   if (db.alloc(h.size()) || dck.alloc((size_t)turbo_galloc(G) * turbo_nwin(K) * turbo_ck_rows(f64) * 64) ||
       dbits.alloc((size_t)G * KW * 64) || (es_used && dused.alloc((size_t)G * 64)))
     return fail(LTE_ENOMEM, "turbo buffers");
+  // re-packing: the packed set of the one job
+  DBuf<T> pb, pck;
+  DBuf<uint32_t> pbits, pused, pidx, pcnt;
+  const int cap = turbo_pack_cap(G);
+  if (rp_after > 0 &&
+      (pb.alloc((size_t)turbo_galloc(cap) * rows * 64) ||
+       pck.alloc((size_t)turbo_galloc(cap) * turbo_nwin(K) * turbo_ck_rows(f64) * 64) ||
+       pbits.alloc((size_t)cap * KW * 64) || pused.alloc((size_t)cap * 64) || pidx.alloc((size_t)cap * 64) ||
+       pcnt.alloc(1)))
+    return fail(LTE_ENOMEM, "turbo re-packing buffers");
+  const TurboPack pk{pb.p, pck.p, pbits.p, pused.p, pidx.p, cap};
   int rc = LTE_OK;
   std::vector<uint32_t> hb((size_t)G * KW * 64);
   const TurboJob job{db.p, dck.p, dbits.p, K, f1, f2, G, ch};
   const int nv = (int)ncb;
   if (hipMemcpy(db.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess ||
-      (es_used ? launch_turbo_jobs_es(nullptr, &job, &dused.p, &nv, 1, iters, f64, es_poly)
-               : launch_turbo_jobs(nullptr, &job, 1, iters, mode, f64)) ||
+      (rp_after > 0 ? launch_turbo_jobs_es_repack(nullptr, &job, &dused.p, &nv, 1, iters, f64, es_poly, rp_after, &pk,
+                                                  pcnt.p, rp_info)
+       : es_used    ? launch_turbo_jobs_es(nullptr, &job, &dused.p, &nv, 1, iters, f64, es_poly)
+                    : launch_turbo_jobs(nullptr, &job, 1, iters, mode, f64)) ||
       hipDeviceSynchronize() != hipSuccess)
     rc = fail(LTE_EHIP, std::string("turbo failed: ") + hipGetErrorString(hipGetLastError()));
   if (rc == LTE_OK && es_used) {
@@ -781,6 +797,36 @@ int lte_turbo_decode_es_host64(int K, int iters, int64_t ncb, const double* llr,
   if (rc) return rc;
   return turbo_host_run<double>(K, iters, ncb, llr, nullptr, nullptr, nullptr, TM_DEC1, bits, nullptr, poly,
                                 iters_used);
+}
+
+// the re-packing entries: the early-stop entries' checks, then the boundary and info
+static int turbo_es_repack_args(int iters, int after, int64_t* info) {
+  if (!info) return fail(LTE_EINVAL, "null argument");
+  if (after < 1 || after >= iters)
+    return fail(LTE_EINVAL, "re-packing boundary must be in 1..iters-1 (after = " + std::to_string(after) +
+                                ", iters = " + std::to_string(iters) + ")");
+  info[0] = info[1] = info[2] = 0;
+  return LTE_OK;
+}
+
+int lte_turbo_decode_es_repack_host(int K, int iters, int64_t ncb, const float* llr, uint32_t crc_poly, int after,
+                                    uint8_t* bits, uint8_t* iters_used, int64_t* info) {
+  uint32_t poly;
+  int rc = turbo_es_args(K, iters, ncb, llr, crc_poly, bits, iters_used, &poly);
+  if (!rc) rc = turbo_es_repack_args(iters, after, info);
+  if (rc) return rc;
+  return turbo_host_run<float>(K, iters, ncb, llr, nullptr, nullptr, nullptr, TM_DEC1, bits, nullptr, poly, iters_used,
+                               after, info);
+}
+
+int lte_turbo_decode_es_repack_host64(int K, int iters, int64_t ncb, const double* llr, uint32_t crc_poly, int after,
+                                      uint8_t* bits, uint8_t* iters_used, int64_t* info) {
+  uint32_t poly;
+  int rc = turbo_es_args(K, iters, ncb, llr, crc_poly, bits, iters_used, &poly);
+  if (!rc) rc = turbo_es_repack_args(iters, after, info);
+  if (rc) return rc;
+  return turbo_host_run<double>(K, iters, ncb, llr, nullptr, nullptr, nullptr, TM_DEC1, bits, nullptr, poly,
+                                iters_used, after, info);
 }
 
 int lte_turbo_decode_host(int K, int iters, int64_t ncb, const float* llr, uint8_t* bits) {

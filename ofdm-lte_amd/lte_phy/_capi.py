@@ -85,6 +85,9 @@ _SIGS = {
     'lte_run_path': (ctypes.c_int, [ctypes.c_void_p, P(RunArgs), ctypes.c_char_p, ctypes.c_int]),
     'lte_plan_set_early_stop': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'lte_plan_early_stop': (ctypes.c_int, [ctypes.c_void_p]),
+    'lte_plan_set_early_stop_repack': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'lte_plan_early_stop_repack': (ctypes.c_int, [ctypes.c_void_p]),
+    'lte_plan_repack_info': (ctypes.c_int, [ctypes.c_void_p, P(c_i64), ctypes.c_int]),
     'lte_plan_turbo_iters_used': (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_uint8), c_i64]),
     'lte_plan_create_harq': (ctypes.c_int, [P(PlanDesc), P(HarqDesc), P(ctypes.c_void_p)]),
     'lte_plan_harq_set_round': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
@@ -123,6 +126,12 @@ _SIGS = {
                                                   P(ctypes.c_uint8), P(ctypes.c_uint8)]),
     'lte_turbo_decode_es_host': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i64, P(ctypes.c_float),
                                                 ctypes.c_uint32, P(ctypes.c_uint8), P(ctypes.c_uint8)]),
+    'lte_turbo_decode_es_repack_host64': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i64, P(c_f64), ctypes.c_uint32,
+                                                         ctypes.c_int, P(ctypes.c_uint8), P(ctypes.c_uint8),
+                                                         P(c_i64)]),
+    'lte_turbo_decode_es_repack_host': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i64, P(ctypes.c_float),
+                                                       ctypes.c_uint32, ctypes.c_int, P(ctypes.c_uint8),
+                                                       P(ctypes.c_uint8), P(c_i64)]),
     'lte_bcjr_host64': (ctypes.c_int, [ctypes.c_int, c_i64, P(c_f64), P(c_f64), P(c_f64), P(c_f64)]),
     'lte_crc_host': (ctypes.c_int, [c_i64, P(ctypes.c_uint8), ctypes.c_uint32, ctypes.c_int,
                                     P(ctypes.c_uint32)]),

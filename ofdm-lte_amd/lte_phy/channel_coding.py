@@ -296,7 +296,7 @@ def turbo_decode_batch(llrs, K, num_iterations=8, precision=None):
     return out
 
 
-def turbo_decode_early_stop(llr, K, max_iterations=8, crc='24B', *, precision=None):
+def turbo_decode_early_stop(llr, K, max_iterations=8, crc='24B', *, precision=None, repack=None):
     """Turbo decode with CRC early termination on the GPU (not a reference
     name, so not in __all__).  With D(n) = turbo_decode(llr, K, n), the decode
     stops at n* = the first n in 1..max_iterations for which the CRC-24
@@ -304,10 +304,17 @@ def turbo_decode_early_stop(llr, K, max_iterations=8, crc='24B', *, precision=No
     max_iterations, and returns (D(n*), n*).  D(n*) is not always
     D(max_iterations), and the all-zero word passes (zero-init CRC).  llr
     [3K+12] -> (bits [K], int), or [ncb][3K+12] -> (bits [ncb, K], uint8 [ncb]).
-    Float64 unless precision='f32'; max-log-MAP only."""
+    Float64 unless precision='f32'; max-log-MAP only.
+    repack=after (1 <= after < max_iterations; True: the default boundary): the
+    blocks still undecided after `after` iterations are re-packed into dense
+    groups for the rest (lte_turbo_decode_es_repack_host*); the same bits and
+    n*, and a third return value, the dict {'undecided', 'groups', 'state'} of
+    the boundary (state 'none' / 'packed' / 'in_place')."""
     polys = {'24A': CRC24A_POLYNOMIAL, '24B': CRC24B_POLYNOMIAL}
     if crc not in polys:
         raise ValueError(f"crc must be '24A' or '24B', got {crc!r}")
+    from .engine import REPACK_STATES, repack_boundary
+    after = repack_boundary(repack, True, max_iterations)
     C.device_init()
     prec = C.precision(precision)
     a = np.asarray(llr)
@@ -316,6 +323,13 @@ def turbo_decode_early_stop(llr, K, max_iterations=8, crc='24B', *, precision=No
     L = np.ascontiguousarray(a, dtype=dt).reshape(-1, 3 * K + 12)
     bits = np.zeros((L.shape[0], K), dtype=np.uint8)
     used = np.zeros(L.shape[0], dtype=np.uint8)
+    if after:
+        f = C.load().lte_turbo_decode_es_repack_host64 if prec == 'f64' else C.load().lte_turbo_decode_es_repack_host
+        v = np.zeros(3, dtype=np.int64)
+        C.check(f(K, int(max_iterations), L.shape[0], C.ptr(L, ct), polys[crc], after, C.ptr(bits, C.U8),
+                  C.ptr(used, C.U8), C.ptr(v, C.c_i64)))
+        info = {'undecided': int(v[0]), 'groups': int(v[1]), 'state': REPACK_STATES[int(v[2])]}
+        return (bits[0], int(used[0]), info) if a.ndim == 1 else (bits, used, info)
     C.check(f(K, int(max_iterations), L.shape[0], C.ptr(L, ct), polys[crc], C.ptr(bits, C.U8), C.ptr(used, C.U8)))
     return (bits[0], int(used[0])) if a.ndim == 1 else (bits, used)
 

@@ -31,11 +31,33 @@ class RunResult(dict):
     path = None
 
 
+REPACK_DEFAULT = 1   # the boundary repack=True stands for
+REPACK_STATES = ('none', 'packed', 'in_place')   # lte_plan_repack_info's 0 / 1 / 2
+
+
+def repack_boundary(repack, early_stop, turbo_iters):
+    """The re-packing boundary `after` a repack= keyword stands for (0: off;
+    True: REPACK_DEFAULT), checked against early_stop and turbo_iters.  Raises
+    ValueError; touches no device."""
+    if repack is None or repack is False:
+        return 0
+    after = REPACK_DEFAULT if repack is True else int(repack)
+    if after == 0:
+        return 0
+    if not early_stop:
+        raise ValueError('repack re-packs the blocks early stop leaves undecided: it needs early_stop=True')
+    if not 1 <= after < int(turbo_iters):
+        raise ValueError(f'repack: the boundary must satisfy 1 <= after < turbo_iters (after = {after}, '
+                         f'turbo_iters = {int(turbo_iters)})')
+    return after
+
+
 class Plan:
     def __init__(self, *, N, Nc, cp_len, bps, n_sym, chain, channel, num_rx=1, delays=(), gains=(), fD=0.0,
                  fs=0.0, n_bits, turbo_iters=8, max_frames=1, cell_id=0, num_tx=1, rank=0, detector=0,
                  precoder=(), sc_fdm=0, bf_adaptive=0, no_equalization=0, precision=None, early_stop=False,
-                 harq=None):
+                 harq=None, repack=None):
+        after = repack_boundary(repack, early_stop, turbo_iters)   # before any device call
         C.device_init()
         d = C.PlanDesc()
         d.N, d.Nc, d.cp_len, d.bps, d.n_sym = N, Nc, cp_len, bps, n_sym
@@ -117,6 +139,11 @@ class Plan:
         self.early_stop = bool(early_stop)
         if self.early_stop:
             C.check(C.load().lte_plan_set_early_stop(h, 1))
+        # re-packing of the blocks still undecided after `repack` iterations
+        # (lte_plan_set_early_stop_repack; 0: off): run() then also returns 'repack_info'
+        self.repack = 0
+        if after:
+            self.set_repack(after)
 
     def __del__(self):
         try:
@@ -137,6 +164,8 @@ class Plan:
             used = np.zeros((a.n_frames, self.n_cb), dtype=np.uint8)
             C.check(C.load().lte_plan_turbo_iters_used(self.h, C.ptr(used, C.U8), used.size))
             out['turbo_iters_used'] = used
+            if self.repack:
+                out['repack_info'] = self.repack_info()
         if self.harq is not None and (a.stages & C.STAGE_RX):   # the process's state after this round
             used = np.zeros(a.n_frames, dtype=np.uint8)
             C.check(C.load().lte_plan_harq_tx_used(self.h, C.ptr(used, C.U8), used.size))
@@ -144,6 +173,24 @@ class Plan:
             out['harq_info'] = self.harq_info()
         del keep
         return out
+
+    # ------------------------------------------------------------------ re-packing
+    def set_repack(self, repack):
+        """Switch re-packing to the boundary `repack` (True: the default one), or
+        off (0 / None / False); the packed arrays stay allocated."""
+        after = repack_boundary(repack, self.early_stop, self.desc.turbo_iters)
+        C.check(C.load().lte_plan_set_early_stop_repack(self.h, after))
+        self.repack = after
+
+    def repack_info(self):
+        """lte_plan_repack_info as a dict: after, n_cb and per code block slot the
+        blocks undecided at the boundary, the 64-block groups that ran the
+        remaining iterations and the state ('none' / 'packed' / 'in_place')."""
+        v = np.zeros(2 + 3 * self.n_cb, dtype=np.int64)
+        C.check(C.load().lte_plan_repack_info(self.h, C.ptr(v, C.c_i64), len(v)))
+        t = v[2:].reshape(self.n_cb, 3)
+        return {'after': int(v[0]), 'n_cb': int(v[1]), 'undecided': [int(x) for x in t[:, 0]],
+                'groups': [int(x) for x in t[:, 1]], 'state': [REPACK_STATES[int(x)] for x in t[:, 2]]}
 
     # ------------------------------------------------------------------ HARQ
     def harq_round(self, t):
@@ -318,6 +365,8 @@ _CACHE_MAX = 8
 def get_plan(**kw):
     kw['precision'] = C.precision_of(kw.get('precision'))   # resolved now: part of the cache key
     kw['early_stop'] = bool(kw.get('early_stop', False))   # likewise: an early-stop plan is never a fixed one
+    # likewise the re-packing boundary (True and its default are one plan)
+    kw['repack'] = repack_boundary(kw.get('repack'), kw['early_stop'], kw.get('turbo_iters', 8))
     hq = kw.get('harq')   # likewise, as a sorted tuple of its settings (None: a plain plan)
     kw['harq'] = None if hq is None else tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple, np.ndarray)) else v)
                                                       for k, v in dict(hq).items()))

@@ -20,7 +20,7 @@ import numpy as np
 from . import _capi as C
 from .dist import trial_shard
 from .config import ITU_CHANNEL_MODELS, LTEConfig
-from .engine import get_plan
+from .engine import get_plan, repack_boundary
 
 SLOT_SIZE = 14
 
@@ -471,10 +471,34 @@ class ChannelSimulator:
         return list(y.astype(np.complex128)), Hm
 
 
+def _takes_repack(f):
+    """The grid drivers' `repack=` keyword.  Their parameter lists are part of
+    the interface the suite pins name by name, so `repack` is one more keyword
+    taken here: resolved to its boundary and checked against the call's
+    early_stop and turbo_iters (ValueError, before any device call), and held
+    in self._repack while the driver makes its plan."""
+    import functools
+    import inspect
+    sig = inspect.signature(f)
+
+    @functools.wraps(f)
+    def g(self, *a, repack=None, **kw):
+        b = sig.bind(self, *a, **kw)
+        b.apply_defaults()
+        after = repack_boundary(repack, b.arguments['early_stop'], b.arguments['turbo_iters'])
+        prev, self._repack = self._repack, after
+        try:
+            return f(self, *a, **kw)
+        finally:
+            self._repack = prev
+    return g
+
+
 # ------------------------------------------------------------------ simulator
 class OFDMSimulator:
     """OFDMSimulator (core/ofdm_core.py:560-2486): SISO, SISO+turbo and SIMO-MRC
     on the GPU, plus the device-resident Monte-Carlo grid `run_grid`."""
+    _repack = 0   # the grid drivers' re-packing boundary while one runs (_takes_repack)
 
     def __init__(self, config: Optional[LTEConfig] = None, channel_type: str = 'awgn', mode: str = 'lte',
                  enable_sc_fdm: bool = False, enable_equalization: bool = True, num_channels: int = 1,
@@ -511,7 +535,8 @@ class OFDMSimulator:
     def Nd(self):
         return len(self.grid._data)
 
-    def _plan(self, chain, n_sym, n_bits, num_rx=1, max_frames=1, iters=8, early_stop=False, harq=None, detector=0):
+    def _plan(self, chain, n_sym, n_bits, num_rx=1, max_frames=1, iters=8, early_stop=False, harq=None, detector=0,
+              repack=None):
         """SC-FDM (enable_sc_fdm / mode 'sc-fdm') reaches the uncoded SISO / SIMO
         transmitters and the SISO receiver; simulate_siso_coded ignores it, as
         the reference does (lte_plan_desc.sc_fdm, include/lte_phy.h).  The coded
@@ -525,7 +550,7 @@ class OFDMSimulator:
                         chain=chain, channel=ch.kind, num_rx=num_rx, delays=tuple(ch.delays),
                         gains=tuple(ch.gains), fD=ch.fD, fs=cfg.fs, n_bits=n_bits, turbo_iters=iters,
                         max_frames=max_frames, sc_fdm=sc, no_equalization=noeq, precision=self.precision,
-                        early_stop=early_stop, harq=harq, detector=detector)
+                        early_stop=early_stop, harq=harq, detector=detector, repack=repack)
 
     def _ref_draws(self, L, num_rx=1):
         """Exactly the global-RNG consumption of one reference simulate_* call:
@@ -738,13 +763,14 @@ class OFDMSimulator:
         return res
 
     # -------------------------------------------------------------- SFBC (config 4)
-    def _sfbc_plan(self, n_sym, n_bits, num_rx, coded=False, max_frames=1, iters=8, early_stop=False):
+    def _sfbc_plan(self, n_sym, n_bits, num_rx, coded=False, max_frames=1, iters=8, early_stop=False,
+                   repack=None):
         cfg, ch = self.config, self.channels[0]
         return get_plan(N=cfg.N, Nc=cfg.Nc, cp_len=cfg.cp_length, bps=cfg.bits_per_symbol, n_sym=n_sym,
                         chain=C.CHAIN_SFBC_CODED if coded else C.CHAIN_SFBC, channel=ch.kind, num_rx=num_rx,
                         num_tx=2, delays=tuple(ch.delays), gains=tuple(ch.gains), fD=ch.fD, fs=cfg.fs,
                         n_bits=n_bits, turbo_iters=iters, max_frames=max_frames, precision=self.precision,
-                        early_stop=early_stop)
+                        early_stop=early_stop, repack=repack)
 
     def _simulate_sfbc(self, bits, snr_db, num_rx, mode):
         """simulate_miso (core/ofdm_core.py:1850-2047) / simulate_mimo (:2049-2258)
@@ -866,6 +892,7 @@ class OFDMSimulator:
         return simulate_beamforming(self, self._bits_in(bits), snr_db, num_tx, num_rx, codebook_type, velocity_kmh,
                                     update_mode)
 
+    @_takes_repack
     def run_grid(self, snr_range, num_trials: int, seed: int = 0, coded: bool = False, num_rx: int = 1,
                  n_bits: Optional[int] = None, frames_per_call: int = 4096, rank: int = 0, world_size: int = 1,
                  turbo_iters: int = 8, mimo: Optional[str] = None, velocity_kmh: float = 3,
@@ -900,7 +927,16 @@ class OFDMSimulator:
         decisions -- not always the ones turbo_iters iterations give.  The result
         then also holds 'turbo_iters_hist' (uint64 [S, turbo_iters + 1]: this
         rank's code blocks by n* per SNR point; all-reduce it like `counts`) and
-        'turbo_iters_mean' [S]."""
+        'turbo_iters_mean' [S].
+
+        repack=after (with early_stop=True; 1 <= after < turbo_iters, True: the
+        default boundary): the code blocks still undecided after `after`
+        iterations are re-packed into dense 64-block groups for the remaining
+        ones (lte_plan_set_early_stop_repack) -- the same results bit for bit,
+        fewer decoder waves kept alive by one straggler.  ValueError without
+        early_stop or for a boundary out of range, before any device call.
+        (One more keyword beside the parameters above: _takes_repack.)"""
+        repack = self._repack
         if early_stop and not (coded and mimo in (None, 'sfbc', 'spatial')):
             raise ValueError("early_stop needs a coded chain (coded=True with mimo=None, 'sfbc' or 'spatial'): "
                              "nothing is decoded here")
@@ -912,7 +948,7 @@ class OFDMSimulator:
             if coded:
                 nb = int(n_bits or 27760)
                 plan = self._sfbc_plan(0, nb, num_rx, coded=True, max_frames=frames_per_call, iters=turbo_iters,
-                                       early_stop=early_stop)
+                                       early_stop=early_stop, repack=repack)
             else:
                 nb = int(n_bits or SLOT_SIZE * res * cfg.bits_per_symbol)
                 plan = self._sfbc_plan(int(np.ceil(nb / (res * cfg.bits_per_symbol))), nb, num_rx,
@@ -931,7 +967,7 @@ class OFDMSimulator:
                                  0 if coded else int(np.ceil(nb / (self.Nd * cfg.bits_per_symbol))), nb,
                                  frames_per_call, num_tx=sp['num_tx'], num_rx=sp['num_rx'], rank=sp['rank'],
                                  detector=DETECTORS[sp['detector'].upper()], W=W, precision=self.precision,
-                                 coded=coded, turbo_iters=turbo_iters, early_stop=early_stop)[0]
+                                 coded=coded, turbo_iters=turbo_iters, early_stop=early_stop, repack=repack)[0]
         elif mimo == 'beamforming':
             from .beamforming import bf_plan
             bfo = {'num_tx': 4, 'num_rx': 1, 'update_mode': 'adaptive'}
@@ -945,7 +981,7 @@ class OFDMSimulator:
             nb = int(n_bits or 27760)
             chain = C.CHAIN_SIMO_CODED if num_rx > 1 else C.CHAIN_CODED
             plan = self._plan(chain, 0, nb, num_rx=num_rx, max_frames=frames_per_call, iters=turbo_iters,
-                              early_stop=early_stop)
+                              early_stop=early_stop, repack=repack)
         else:
             nb = int(n_bits or SLOT_SIZE * self.Nd * cfg.bits_per_symbol)
             n_sym = int(np.ceil(nb / (self.Nd * cfg.bits_per_symbol)))
@@ -972,17 +1008,19 @@ class OFDMSimulator:
         return _harq_grid(self, snr_range, num_trials, seed, n_bits, coded_bits, max_tx, rv_seq, frames_per_call,
                           rank, world_size, turbo_iters, other)
 
+    @_takes_repack
     def run_scfdm_grid(self, snr_range, num_trials, seed=0, num_rx=1, equalizer='mmse', n_bits=None,
                        frames_per_call=4096, rank=0, world_size=1, turbo_iters=8, early_stop=False):
         """BER / BLER grid of the coded SC-FDM chain on the device
         (LTE_CHAIN_SCFDM_CODED; simulate_scfdm_coded's chain, equalizer 'mmse' or
         'zf', 1..8 RX; n_bits defaults to 27760).  Frame ids, Philox streams,
-        sharding, the counts layout and early_stop as run_grid(coded=True): the
-        caller all-reduces `counts` (and 'turbo_iters_hist')."""
+        sharding, the counts layout, early_stop and repack as run_grid(coded=True):
+        the caller all-reduces `counts` (and 'turbo_iters_hist')."""
+        repack = self._repack
         det = self._scfdm_equalizer(equalizer)[1]
         snrs = np.atleast_1d(np.asarray(snr_range, dtype=np.float64))
         plan = self._plan(C.CHAIN_SCFDM_CODED, 0, int(n_bits or 27760), num_rx=num_rx, max_frames=frames_per_call,
-                          iters=turbo_iters, early_stop=early_stop, detector=det)
+                          iters=turbo_iters, early_stop=early_stop, detector=det, repack=repack)
         return _run_plan_grid(plan, snrs, int(num_trials), seed, frames_per_call, rank, world_size, turbo_iters,
                               early_stop)
 
@@ -1055,7 +1093,7 @@ def _harq_grid(sim, snr_range, num_trials, seed, n_bits, coded_bits, max_tx, rv_
 
 def _spatial_plan(config, channel_type, itu_profile, velocity_kmh, frequency_ghz, n_sym, n_bits, max_frames=1,
                   num_tx=4, num_rx=4, rank=4, detector=C.DET_MMSE, W=None, precision=None, coded=False,
-                  turbo_iters=8, early_stop=False):
+                  turbo_iters=8, early_stop=False, repack=None):
     ch = {'awgn': C.CH_AWGN, 'rayleigh_mp': C.CH_RAYLEIGH}.get(channel_type)
     if ch is None:
         raise ValueError(f"Tipo de canal desconocido: {channel_type}")
@@ -1070,7 +1108,8 @@ def _spatial_plan(config, channel_type, itu_profile, velocity_kmh, frequency_ghz
         W = np.eye(num_tx, dtype=complex)[:, :rank]
     Wt = tuple(complex(v) for v in np.asarray(W, dtype=complex).ravel())
     # coded: LTE_CHAIN_SPATIAL_CODED (n_sym 0: it follows from the coded length)
-    kw = dict(chain=C.CHAIN_SPATIAL_CODED, turbo_iters=int(turbo_iters), early_stop=early_stop) if coded else \
+    kw = dict(chain=C.CHAIN_SPATIAL_CODED, turbo_iters=int(turbo_iters), early_stop=early_stop,
+              repack=repack) if coded else \
         dict(chain=C.CHAIN_SPATIAL)
     return get_plan(N=config.N, Nc=config.Nc, cp_len=config.cp_length, bps=config.bits_per_symbol, n_sym=n_sym,
                     channel=ch, num_rx=num_rx, num_tx=num_tx, delays=tuple(delays),
