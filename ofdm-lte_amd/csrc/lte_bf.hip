@@ -170,26 +170,25 @@ __global__ __launch_bounds__(BWG) void k_bf_data(int B, int n_sym, int Nd, int n
 
 template <class R>
 int launch_bf(hipStream_t s, int B, int n_sym, int Nd, int bps, int num_tx, int num_rx, int adaptive, int ncb,
-              const double* cb, const uint64_t* fid, uint64_t seed, const R* inj_h, int64_t inj_h_stride,
-              BfFrameT<R>* fr, const R* sigma, const uint32_t* pw, int PW, int n_bits, const R* inj_z,
-              int64_t inj_z_stride, uint32_t* frame_err, cx<R>* cap_syms, uint8_t* cap_bits) {
+              const double* cb, const uint64_t* fid, uint64_t seed, Inj<R> inj_h, BfFrameT<R>* fr, const R* sigma,
+              const Scored& sc, Inj<R> inj_z, const RxCaptures<R>& cap) {
   if (num_tx < 1 || num_tx > LTE_BF_MAX_TX || num_rx < 1 || num_rx > LTE_BF_MAX_RX) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_bf_setup<R>, dim3((B + BWG - 1) / BWG), dim3(BWG), 0, s, B, num_tx, num_rx, adaptive, ncb, cb,
-                     fid, seed, inj_h, inj_h_stride, fr);
+                     fid, seed, inj_h.p, inj_h.stride, fr);
   const int64_t n = (int64_t)B * n_sym * Nd;
   const dim3 grid((unsigned)((n + BWG - 1) / BWG));
   with_int_or<6, 2, 4>(bps, [&](auto Q) {
-    hipLaunchKernelGGL((k_bf_data<R, Q()>), grid, dim3(BWG), 0, s, B, n_sym, Nd, num_tx, num_rx, fr, sigma, pw, PW,
-                       n_bits, fid, seed, inj_z, inj_z_stride, frame_err, cap_syms, cap_bits);
+    hipLaunchKernelGGL((k_bf_data<R, Q()>), grid, dim3(BWG), 0, s, B, n_sym, Nd, num_tx, num_rx, fr, sigma, sc.pw,
+                       sc.PW, sc.n_bits, fid, seed, inj_z.p, inj_z.stride, sc.frame_err, cap.syms, cap.bits);
   });
   return (int)hipGetLastError();
 }
 
 template int launch_bf<float>(hipStream_t, int, int, int, int, int, int, int, int, const double*, const uint64_t*,
-                              uint64_t, const float*, int64_t, BfFrameT<float>*, const float*, const uint32_t*, int,
-                              int, const float*, int64_t, uint32_t*, float2*, uint8_t*);
+                              uint64_t, Inj<float>, BfFrameT<float>*, const float*, const Scored&, Inj<float>,
+                              const RxCaptures<float>&);
 template int launch_bf<double>(hipStream_t, int, int, int, int, int, int, int, int, const double*, const uint64_t*,
-                               uint64_t, const double*, int64_t, BfFrameT<double>*, const double*, const uint32_t*,
-                               int, int, const double*, int64_t, uint32_t*, double2*, uint8_t*);
+                               uint64_t, Inj<double>, BfFrameT<double>*, const double*, const Scored&, Inj<double>,
+                               const RxCaptures<double>&);
 
 }  // namespace lte

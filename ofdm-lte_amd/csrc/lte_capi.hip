@@ -1300,7 +1300,7 @@ int lte_timing_read(lte_plan* p, char* names, int names_len, double* ms, int64_t
 // [0, nf) of `per` values each; synchronous (the host copy is a temporary).
 template <class R>
 static int upload_inj(DBuf<R>& dst, const double* src, int64_t stride, int B, size_t per, hipStream_t s,
-                      const R** out, int64_t* out_stride) {
+                      Inj<R>* out) {
   const int nf = stride ? B : 1;
   if (dst.alloc((size_t)nf * per)) return fail(LTE_ENOMEM, "injection buffer");
   if (sizeof(R) == 8 && (!stride || (size_t)stride == per)) {   // float64, dense: straight from the caller
@@ -1312,8 +1312,7 @@ static int upload_inj(DBuf<R>& dst, const double* src, int64_t stride, int B, si
     HIPCHK(hipMemcpyAsync(dst.p, h.data(), h.size() * sizeof(R), hipMemcpyHostToDevice, s));
   }
   HIPCHK(hipStreamSynchronize(s));
-  *out = dst.p;
-  *out_stride = stride ? (int64_t)per : 0;
+  *out = Inj<R>{dst.p, stride ? (int64_t)per : 0};
   return LTE_OK;
 }
 
@@ -1324,6 +1323,12 @@ static cx<R>* zn_z(lte_plan* p) { return reinterpret_cast<cx<R>*>(cbuf<R>(p).llr
 template <class R>
 static R* zn_nv(lte_plan* p) {
   return cbuf<R>(p).llr.p + 2 * (size_t)p->d.max_frames * (p->n_re_bits / p->d.bps);
+}
+// What a run's receiver writes for the decoder (nothing: an uncoded chain)
+template <class R>
+static SoftOut<R> soft_out(lte_plan* p, bool coded, bool zn) {
+  if (!coded) return {};
+  return zn ? SoftOut<R>{nullptr, zn_z<R>(p), zn_nv<R>(p)} : SoftOut<R>{cbuf<R>(p).llr.p, nullptr, nullptr};
 }
 
 // ---------------------------------------------------------------------------
@@ -1520,38 +1525,32 @@ static MimoPath select_mimo(const lte_plan* p, const lte_run_args* a, const Knob
 // The stages every run driver shares: capture buffers, the coded receive tail
 // and the read-back of the results.
 
-// What a receiver writes beside its counts when a capture asks for it: the
-// data symbols [B][n_syms] and the received bits [B][n_bits] (null: not asked)
+// The buffers of the captures every chain has, and what the receiver writes of
+// them: the data symbols [B][n_syms] into capbuf, and on an uncoded chain the
+// received bits into cap_bits (coded, k_crc_count writes the decoded ones there)
 template <class R>
-struct Captures {
-  cx<R>* syms = nullptr;
-  uint8_t* bits = nullptr;
-  size_t n_syms = 0;
-};
-
-template <class R>
-static int capture_bufs(lte_plan* p, const lte_run_args* a, int B, size_t n_syms, Captures<R>* cap) {
-  cap->n_syms = n_syms;
+static int capture_bufs(lte_plan* p, const lte_run_args* a, int B, size_t n_syms, RxCaptures<R>* cap) {
   if (a->cap_data_syms) {
     if (cbuf<R>(p).capbuf.alloc((size_t)B * n_syms)) return fail(LTE_ENOMEM, "capture");
     cap->syms = cbuf<R>(p).capbuf.p;
   }
   if (a->cap_bits_rx) {
     if (p->cap_bits.alloc((size_t)B * p->d.n_bits)) return fail(LTE_ENOMEM, "capture");
-    cap->bits = p->cap_bits.p;
+    if (!p->ct->coded) cap->bits = p->cap_bits.p;
   }
   return LTE_OK;
 }
 
 // The coded receive tail: the receiver's soft output -> decoder rows (rx_map;
-// zn: k_dematch_zn demaps (z, nv) with nd noise variances per row, nv_pairs:
-// one per Alamouti RE pair), turbo decoding, CRC and error counts per frame.
+// soft.z set: k_dematch_zn demaps (z, nv) with nd noise variances per row,
+// nv_pairs: one per Alamouti RE pair), turbo decoding, CRC and error counts per
+// frame into sc.
 // HARQ (SISO only): add0 = 0 is round 0, which first zeroes the rows its map
 // leaves unwritten, add0 = 1 a later round, which adds to the rows' sums;
 // hq_skip: the skip-aware decoders; the groups they skipped go to hq_last[2].
 template <class R>
 static int decode_blocks(lte_plan* p, const lte_run_args* a, int B, const int32_t* rx_map, int nd, int nv_pairs,
-                         int add0, bool zn, bool hq_skip, uint8_t* cap_bits_dev, const uint32_t* inj_bits) {
+                         int add0, const SoftOut<R>& soft, const Scored& sc, bool hq_skip) {
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
   hipStream_t s = p->stream;
@@ -1560,11 +1559,11 @@ static int decode_blocks(lte_plan* p, const lte_run_args* a, int B, const int32_
     Timer t(p, KN_DEMATCH);
     if (p->harq && !add0 && p->hq_nz)
       LCHK(launch_harq_zero<R>(s, p->hq_zmap.p, p->hq_nz, G, c.blk_ptrs.p, p->rows_dev.p, turbo_plan_ch(p)));
-    if (zn)
-      LCHK(launch_dematch_zn<R>(s, zn_z<R>(p), zn_nv<R>(p), p->n_re_bits / d.bps, nd, d.bps, B, rx_map, p->n_layers,
+    if (soft.z)
+      LCHK(launch_dematch_zn<R>(s, soft.z, soft.nv, p->n_re_bits / d.bps, nd, d.bps, B, rx_map, p->n_layers,
                                 c.blk_ptrs.p, p->rows_dev.p, turbo_plan_ch(p), 0, nv_pairs, add0));
     else
-      LCHK(launch_dematch<R>(s, c.llr.p, p->n_re_bits, B, rx_map, p->n_layers, c.blk_ptrs.p, p->rows_dev.p,
+      LCHK(launch_dematch<R>(s, soft.llr, p->n_re_bits, B, rx_map, p->n_layers, c.blk_ptrs.p, p->rows_dev.p,
                              turbo_plan_ch(p), 0, add0));
   }
   std::vector<TurboJob> jobs(p->C);
@@ -1587,31 +1586,19 @@ static int decode_blocks(lte_plan* p, const lte_run_args* a, int B, const int32_
       LCHK(plan_launch_turbo(p, s, jobs, B, sizeof(R) == 8 ? 1 : 0));
   }
   Timer t(p, KN_CRC);
-  LCHK(launch_crc_count(s, p->cbi.p, p->C, p->dec_ptrs.p, p->kw_dev.p, B, p->pw.p, p->PW, d.n_bits, p->frame_err.p,
-                        p->frame_crc.p, cap_bits_dev, 0, inj_bits ? nullptr : p->fid.p, a->seed));
+  LCHK(launch_crc_count(s, p->cbi.p, p->C, p->dec_ptrs.p, p->kw_dev.p, B, sc, p->frame_crc.p,
+                        a->cap_bits_rx ? p->cap_bits.p : nullptr, 0, a->bits ? nullptr : p->fid.p, a->seed));
   return LTE_OK;
 }
-
-// The received streams as the receivers read them (strides in samples) and
-// the noise draws they add, for the cap_signal_rx capture (k_cap_rx);
-// num_rx = 0: the chain has no time-domain streams (beamforming)
-template <class R>
-struct RxStreams {
-  int num_rx;
-  const cx<R>* y;
-  int64_t rx_stride, frame_stride;
-  uint64_t seed;
-  const R* inj_z;
-  int64_t inj_z_stride;
-};
 
 // End of every run: the per-SNR counters (acc: the receiver ran), then the
 // results and the captures every chain has to the caller, the final
 // synchronise, the launch timings and the host-side adds.  A driver queues its
-// own captures on the stream before it calls this.
+// own captures on the stream before it calls this.  n_syms: the data symbols
+// per frame in capbuf; rxs: the receiver's streams, for the cap_signal_rx capture.
 template <class R>
-static int read_back(lte_plan* p, const lte_run_args* a, int B, int n_snr, bool coded, bool acc,
-                     const Captures<R>& cap, const RxStreams<R>& rxs) {
+static int read_back(lte_plan* p, const lte_run_args* a, int B, int n_snr, bool coded, bool acc, size_t n_syms,
+                     const RxStreams<R>& rxs) {
   using V = cx<R>;
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
@@ -1636,19 +1623,18 @@ static int read_back(lte_plan* p, const lte_run_args* a, int B, int n_snr, bool 
     if (sig_rx.alloc(n)) return fail(LTE_ENOMEM, "capture");
     {
       Timer t(p, KN_CAP);
-      LCHK(launch_cap_rx<R>(s, p->L, rxs.num_rx, B, rxs.y, rxs.rx_stride, rxs.frame_stride, c.npow.p, p->fid.p,
-                            rxs.seed, rxs.inj_z, rxs.inj_z_stride, sig_rx.p));
+      LCHK(launch_cap_rx<R>(s, p->L, B, rxs, sig_rx.p));
     }
     HIPCHK(hipMemcpyAsync(a->cap_signal_rx, sig_rx.p, n * sizeof(V), hipMemcpyDeviceToHost, s));
   }
   if (a->cap_data_syms)
-    HIPCHK(hipMemcpyAsync(a->cap_data_syms, cap.syms, (size_t)B * cap.n_syms * sizeof(V), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(a->cap_data_syms, c.capbuf.p, (size_t)B * n_syms * sizeof(V), hipMemcpyDeviceToHost, s));
   if (a->cap_bits_rx)
-    HIPCHK(hipMemcpyAsync(a->cap_bits_rx, cap.bits, (size_t)B * d.n_bits, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(a->cap_bits_rx, p->cap_bits.p, (size_t)B * d.n_bits, hipMemcpyDeviceToHost, s));
   if (a->cap_llr && coded)
     HIPCHK(hipMemcpyAsync(a->cap_llr, c.llr.p, (size_t)B * p->n_re_bits * sizeof(R), hipMemcpyDeviceToHost, s));
   if (a->cap_noise_power && rxs.num_rx)
-    HIPCHK(hipMemcpyAsync(a->cap_noise_power, c.npow.p, (size_t)B * rxs.num_rx * sizeof(R), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(a->cap_noise_power, rxs.npow, (size_t)B * rxs.num_rx * sizeof(R), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (p->timing) collect_timing(p);
   if (a->counts)
@@ -1662,7 +1648,7 @@ static int read_back(lte_plan* p, const lte_run_args* a, int B, int n_snr, bool 
 // in precision R.
 template <class R>
 static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, int B, int n_snr,
-                    const std::vector<double>& snr_lin, const uint32_t* inj_bits, int64_t inj_bits_stride) {
+                    const std::vector<double>& snr_lin, Inj<uint32_t> inj_bits) {
   using V = cx<R>;
   const lte_plan_desc& d = p->d;
   const Grid& g = p->grid;
@@ -1684,41 +1670,39 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, in
     HIPCHK(hipMemcpyAsync(p->nvar.p, nv.data(), B * sizeof(double), hipMemcpyHostToDevice, s));
   }
   // injections (the reference's own draws, ref-compat mode)
-  const R *inj_ph = nullptr, *inj_z = nullptr, *inj_lz = nullptr, *inj_lh = nullptr;
-  int64_t inj_ph_stride = 0, inj_z_stride = 0, inj_lz_stride = 0, inj_lh_stride = 0;
-  if (a->phases && ray) {
-    const int e = upload_inj<R>(c.inj_ph, a->phases, a->phases_stride, B, links * d.n_paths * 16, s, &inj_ph,
-                                &inj_ph_stride);
-    if (e != LTE_OK) return e;
-  }
-  if (a->noise) {
-    const int e = upload_inj<R>(c.inj_z, a->noise, a->noise_stride, B, (size_t)m.num_rx * 2 * p->L, s, &inj_z,
-                                &inj_z_stride);
-    if (e != LTE_OK) return e;
-  }
-  if (a->link_noise && link_noise) {
-    const int e = upload_inj<R>(c.inj_lz, a->link_noise, a->link_noise_stride, B, links * 2 * p->L, s, &inj_lz,
-                                &inj_lz_stride);
-    if (e != LTE_OK) return e;
-  }
-  if (a->link_h && !ray && !sfbc) {
-    const int e = upload_inj<R>(c.inj_lh, a->link_h, a->link_h_stride, B, links * 2, s, &inj_lh, &inj_lh_stride);
-    if (e != LTE_OK) return e;
-  }
+  Inj<R> inj_ph{}, inj_z{}, inj_lz{}, inj_lh{};
+  if (a->phases && ray)
+    if (const int e = upload_inj<R>(c.inj_ph, a->phases, a->phases_stride, B, links * d.n_paths * 16, s, &inj_ph))
+      return e;
+  if (a->noise)
+    if (const int e = upload_inj<R>(c.inj_z, a->noise, a->noise_stride, B, (size_t)m.num_rx * 2 * p->L, s, &inj_z))
+      return e;
+  if (a->link_noise && link_noise)
+    if (const int e = upload_inj<R>(c.inj_lz, a->link_noise, a->link_noise_stride, B, links * 2 * p->L, s, &inj_lz))
+      return e;
+  if (a->link_h && !ray && !sfbc)
+    if (const int e = upload_inj<R>(c.inj_lh, a->link_h, a->link_h_stride, B, links * 2, s, &inj_lh)) return e;
+  // the launchers' argument groups, each built once
+  const TxSource src{coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, p->tx_map.p};
+  const Scored sc{p->pw.p, p->PW, d.n_bits, p->frame_err.p};
+  const RxStreams<R> rxs{.num_rx = m.num_rx, .y = c.y.p, .rx_stride = p->L, .frame_stride = (int64_t)m.num_rx * p->L,
+                         .npow = c.npow.p, .fid = p->fid.p, .seed = a->seed, .inj_z = inj_z};
+  const LinkNoise<R> ln{p->fid.p, a->seed, inj_lz};
+  const SoftOut<R> soft = soft_out<R>(p, coded, path.zn);
   {
     Timer t(p, KN_PAYLOAD);
-    LCHK(launch_payload(s, p->pw.p, p->PW, d.n_bits, coded ? CRC24A_POLY : 0, p->fid.p, a->seed, B, inj_bits, inj_bits_stride));
+    LCHK(launch_payload(s, p->pw.p, p->PW, d.n_bits, coded ? CRC24A_POLY : 0, p->fid.p, a->seed, B, inj_bits));
   }
   if (coded) {
     Timer t(p, KN_ENCODE);
     LCHK(launch_encode(s, p->pw.p, p->PW, p->KWmax, p->enc.p, p->EW, p->cbi.p, p->C, B, p->enc_qmask.p, p->qstride));
   }
-  const int np = ray ? d.n_paths : 1;
   R* phases = (ray && m.exact_jakes) ? c.phases.p : nullptr;
+  const LinkTaps<R> taps{ray ? d.n_paths : 1, ray ? p->delays.p : nullptr, c.coef.p, phases, c.gains.p, d.fs};
   {
     Timer t(p, KN_FADING);
     LCHK(launch_fading_mimo<R>(s, g, m, B, ray ? 1 : 0, d.n_paths, c.gains.p, d.fD, d.fs, p->fid.p, a->seed, inj_ph,
-                               inj_ph_stride, inj_lh, inj_lh_stride, c.coef.p, phases));
+                               inj_lh, c.coef.p, phases));
   }
   TxLinkPower<R> lp{};
   const int maxd = ray ? *std::max_element(d.delays, d.delays + d.n_paths) : 0;
@@ -1733,8 +1717,7 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, in
     lf.merged = sfbc_merge ? 1 : 0;
     {
       Timer t(p, KN_OFDM_TX);
-      LCHK(launch_ofdm_txch_sfbc<R>(s, g, m, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, p->tx_map.p, lf,
-                                    c.y.p, B));
+      LCHK(launch_ofdm_txch_sfbc<R>(s, g, m, src, lf, c.y.p, B));
     }
     // (chunks of frames with each chunk's noise pass on a second stream beside
     // the next chunk's TX measured no overlap: TX + noise 67.3-68.0 ms per
@@ -1743,24 +1726,20 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, in
     if (sfbc_merge)
       LCHK(launch_npow_sfbc_merged<R>(s, B, m.num_rx, m.num_tx, c.link_part.p, p->L, c.snr_lin.p, c.npow.p));
     else
-      LCHK(launch_link_noise_add<R>(s, g, m, B, c.link_part.p, c.link_sigma.p, c.y.p, p->fid.p, a->seed,
-                                    c.pow_part.p, &npow_nblk));
+      LCHK(launch_link_noise_add<R>(s, g, m, B, c.link_part.p, c.link_sigma.p, c.y.p, ln, c.pow_part.p, &npow_nblk));
   } else if (!path.ch_sep) {
     Timer t(p, KN_OFDM_TX);
-    LCHK(launch_ofdm_txch_flat<R>(s, g, m, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, p->tx_map.p,
-                                  c.coef.p, c.y.p, c.pow_part.p, nch, B,
+    LCHK(launch_ofdm_txch_flat<R>(s, g, m, src, c.coef.p, c.y.p, c.pow_part.p, nch, B,
                                   path.tx == MTX_FLAT_PR ? FLAT_PR : path.tx == MTX_FLAT_W ? FLAT_WAVE : FLAT_BLOCK));
   } else {
     if (c.x.alloc((size_t)d.max_frames * m.num_tx * p->L)) return fail(LTE_ENOMEM, "TX signal buffer");
     {
       Timer t(p, KN_OFDM_TX);
-      LCHK(launch_ofdm_tx_mimo<R>(s, g, m, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, p->tx_map.p, c.x.p,
-                                  B, lp, path.tx == MTX_FRAME ? 1 : 0));
+      LCHK(launch_ofdm_tx_mimo<R>(s, g, m, src, c.x.p, B, lp, path.tx == MTX_FRAME ? 1 : 0));
     }
     Timer t(p, KN_CHANNEL);
-    LCHK(launch_channel_mimo<R>(s, g, m, B, np, ray ? p->delays.p : nullptr, c.coef.p, phases, c.gains.p, d.fs, c.x.p,
-                                c.y.p, link_noise ? 1 : 0, p->fid.p, a->seed, inj_lz, inj_lz_stride, c.link_part.p,
-                                c.link_sigma.p, c.pow_part.p, p->nblk, path.ch, path.lp_fuse ? 1 : 0));
+    LCHK(launch_channel_mimo<R>(s, g, m, B, taps, c.x.p, c.y.p, link_noise ? 1 : 0, ln, c.link_part.p, c.link_sigma.p,
+                                c.pow_part.p, p->nblk, path.ch, path.lp_fuse ? 1 : 0));
   }
   if (!sfbc_merge) {
     Timer t(p, KN_CHANNEL);
@@ -1768,12 +1747,10 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, in
     LCHK(launch_npow_mimo<R>(s, B, m.num_rx, c.pow_part.p, npow_nblk, p->L, c.snr_lin.p, sfbc ? (double)m.num_tx : 1.0,
                              c.npow.p));
   }
-  const bool rx_fuse = path.rx == MRX_SFBC, h_pilots = path.h_pilots, zn = path.zn;
-  if (rx_fuse) {
+  const bool rx_fuse = path.rx == MRX_SFBC, h_pilots = path.h_pilots;
+  if (rx_fuse) {   // (coded: select_mimo fuses the receiver only with the (z, nv) hand-off)
     Timer t(p, KN_RX_CHEST);
-    LCHK(launch_rx_sfbc<R>(s, g, m, coded ? 1 : 0, B, c.y.p, c.npow.p, p->fid.p, a->seed, c.snr_lin.p, p->pw.p,
-                           p->PW, d.n_bits, p->frame_err.p, coded ? zn_z<R>(p) : nullptr,
-                           coded ? zn_nv<R>(p) : nullptr));
+    LCHK(launch_rx_sfbc<R>(s, g, m, coded ? 1 : 0, B, rxs, c.snr_lin.p, sc, soft));
   } else {
     if (c.Ym.alloc((size_t)d.max_frames * p->n_sym * m.num_rx * m.n_dsc) ||
         c.H.alloc((size_t)d.max_frames * m.num_rx * m.n_est * m.num_tx * (h_pilots ? m.maxP : m.n_dsc)))
@@ -1781,30 +1758,26 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, in
     Timer t(p, KN_RX_CHEST);
     if (path.rx == MRX_FFT_W) {
       if constexpr (std::is_same_v<R, double>)
-        LCHK(launch_rx_fft_mimo_w(s, g, m, B, c.y.p, c.npow.p, p->fid.p, a->seed, inj_z, inj_z_stride, c.Ym.p, c.H.p));
+        LCHK(launch_rx_fft_mimo_w(s, g, m, B, rxs, c.Ym.p, c.H.p));
       else
         return fail(LTE_EINVAL, "the wave receiver runs in float64 plans only");
     } else {
-      LCHK(launch_rx_fft_mimo<R>(s, g, m, B, c.y.p, c.npow.p, p->fid.p, a->seed, inj_z, inj_z_stride, c.Ym.p, c.H.p,
-                                 h_pilots ? 1 : 0));
+      LCHK(launch_rx_fft_mimo<R>(s, g, m, B, rxs, c.Ym.p, c.H.p, h_pilots ? 1 : 0));
     }
   }
-  Captures<R> cap;
-  if (const int e = capture_bufs<R>(p, a, B, (size_t)p->n_sym * m.res, &cap)) return e;
+  const size_t n_syms = (size_t)p->n_sym * m.res;
+  RxCaptures<R> cap{};   // (H is no capture here: the receiver always writes it for the detector)
+  if (const int e = capture_bufs<R>(p, a, B, n_syms, &cap)) return e;
   if (!rx_fuse) {
     Timer t(p, KN_RX_DATA);
     if (sfbc)
-      LCHK(launch_det_sfbc<R>(s, g, m, coded ? 1 : 0, ray ? 1 : 0, B, c.Ym.p, c.H.p, c.snr_lin.p, p->pw.p, p->PW,
-                              d.n_bits, p->frame_err.p, c.llr.p, cap.syms, coded ? nullptr : cap.bits,
-                              zn ? zn_z<R>(p) : nullptr, zn ? zn_nv<R>(p) : nullptr));
+      LCHK(launch_det_sfbc<R>(s, g, m, coded ? 1 : 0, ray ? 1 : 0, B, c.Ym.p, c.H.p, c.snr_lin.p, sc, soft, cap));
     else   // (coded: the soft instance -- LLRs for k_dematch; the received bits come from k_crc_count)
-      LCHK(launch_det_spatial<R>(s, g, m, B, c.Ym.p, c.H.p, p->nvar.p, p->pw.p, p->PW, d.n_bits, p->frame_err.p,
-                                 cap.syms, coded ? nullptr : cap.bits, h_pilots ? 1 : 0, path.det_stage ? 1 : 0,
-                                 coded ? c.llr.p : nullptr));
+      LCHK(launch_det_spatial<R>(s, g, m, B, c.Ym.p, c.H.p, p->nvar.p, sc, soft, cap, h_pilots ? 1 : 0,
+                                 path.det_stage ? 1 : 0));
   }
   if (coded)   // (k_det_sfbc's noise variances are per Alamouti RE pair; m.res = Nd for spatial)
-    if (const int e = decode_blocks<R>(p, a, B, p->rx_map.p, m.res, sfbc ? 1 : 0, 0, zn, false, cap.bits, inj_bits))
-      return e;
+    if (const int e = decode_blocks<R>(p, a, B, p->rx_map.p, m.res, sfbc ? 1 : 0, 0, soft, sc, false)) return e;
   // this chain's own captures; lpart / lstats live until read_back has synchronised
   if (a->cap_signal_tx)
     HIPCHK(hipMemcpyAsync(a->cap_signal_tx, c.x.p, (size_t)B * m.num_tx * p->L * sizeof(V), hipMemcpyDeviceToHost, s));
@@ -1818,22 +1791,19 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, in
       return fail(LTE_ENOMEM, "capture");
     {
       Timer t(p, KN_CAP);
-      LCHK(launch_link_stats<R>(s, g, m, B, np, ray ? p->delays.p : nullptr, c.coef.p, phases, c.gains.p, d.fs, c.x.p,
-                                link_noise ? c.link_sigma.p : nullptr, p->fid.p, a->seed, inj_lz, inj_lz_stride,
-                                lpart.p, nb, lstats.p));
+      LCHK(launch_link_stats<R>(s, g, m, B, taps, c.x.p, link_noise ? c.link_sigma.p : nullptr, ln, lpart.p, nb,
+                                lstats.p));
     }
     HIPCHK(hipMemcpyAsync(a->cap_link_stats, lstats.p, (size_t)B * links * 4 * sizeof(R), hipMemcpyDeviceToHost, s));
   }
-  return read_back<R>(p, a, B, n_snr, coded, true, cap,
-                      RxStreams<R>{m.num_rx, c.y.p, (int64_t)p->L, (int64_t)m.num_rx * p->L, a->seed, inj_z,
-                                   inj_z_stride});
+  return read_back<R>(p, a, B, n_snr, coded, true, n_syms, rxs);
 }
 
 // Beamforming chain (frequency domain, flat H per frame), R = double (the
 // default) / float.  sig: the per-frame noise scale sqrt(10^(-SNR/10) / 2).
 template <class R>
 static int run_bf(lte_plan* p, const lte_run_args* a, int B, int n_snr, const std::vector<double>& sig,
-                  const uint32_t* inj_bits, int64_t inj_bits_stride) {
+                  Inj<uint32_t> inj_bits) {
   const lte_plan_desc& d = p->d;
   hipStream_t s = p->stream;
   ChainBufs<R>& c = cbuf<R>(p);
@@ -1842,35 +1812,30 @@ static int run_bf(lte_plan* p, const lte_run_args* a, int B, int n_snr, const st
   std::vector<R> sg(B);
   for (int b = 0; b < B; ++b) sg[b] = (R)sig[b];
   HIPCHK(hipMemcpyAsync(c.snr_lin.p, sg.data(), B * sizeof(R), hipMemcpyHostToDevice, s));
-  const R *inj_h = nullptr, *inj_z = nullptr;
-  int64_t inj_h_stride = 0, inj_z_stride = 0;
-  if (a->link_h) {
-    const int e = upload_inj<R>(c.inj_lh, a->link_h, a->link_h_stride, B, links * 2, s, &inj_h, &inj_h_stride);
-    if (e != LTE_OK) return e;
-  }
-  if (a->noise) {
-    const int e = upload_inj<R>(c.inj_z, a->noise, a->noise_stride, B, (size_t)d.num_rx * 2 * p->L, s, &inj_z,
-                                &inj_z_stride);
-    if (e != LTE_OK) return e;
-  }
+  Inj<R> inj_h{}, inj_z{};
+  if (a->link_h)
+    if (const int e = upload_inj<R>(c.inj_lh, a->link_h, a->link_h_stride, B, links * 2, s, &inj_h)) return e;
+  if (a->noise)
+    if (const int e = upload_inj<R>(c.inj_z, a->noise, a->noise_stride, B, (size_t)d.num_rx * 2 * p->L, s, &inj_z))
+      return e;
   {
     Timer t(p, KN_PAYLOAD);
-    LCHK(launch_payload(s, p->pw.p, p->PW, d.n_bits, 0, p->fid.p, a->seed, B, inj_bits, inj_bits_stride));
+    LCHK(launch_payload(s, p->pw.p, p->PW, d.n_bits, 0, p->fid.p, a->seed, B, inj_bits));
   }
-  Captures<R> cap;
+  RxCaptures<R> cap{};
   if (const int e = capture_bufs<R>(p, a, B, (size_t)p->L, &cap)) return e;
   {
     Timer t(p, KN_RX_DATA);
     LCHK(launch_bf<R>(s, B, p->n_sym, p->Nd, d.bps, d.num_tx, d.num_rx, d.bf_adaptive, p->bf_ncb, p->bf_cb.p,
-                      p->fid.p, a->seed, inj_h, inj_h_stride, frd, c.snr_lin.p, p->pw.p, p->PW, d.n_bits, inj_z,
-                      inj_z_stride, p->frame_err.p, cap.syms, cap.bits));
+                      p->fid.p, a->seed, inj_h, frd, c.snr_lin.p, Scored{p->pw.p, p->PW, d.n_bits, p->frame_err.p},
+                      inj_z, cap));
   }
   std::vector<BfFrameT<R>> fr;   // this chain's own capture: the per-frame state
   if (a->cap_H || a->cap_pmi || a->cap_bf_gain) {
     fr.resize(B);
     HIPCHK(hipMemcpyAsync(fr.data(), frd, B * sizeof(BfFrameT<R>), hipMemcpyDeviceToHost, s));
   }
-  if (const int e = read_back<R>(p, a, B, n_snr, false, true, cap, RxStreams<R>{})) return e;
+  if (const int e = read_back<R>(p, a, B, n_snr, false, true, (size_t)p->L, RxStreams<R>{})) return e;
   for (int b = 0; b < (int)fr.size(); ++b) {
     if (a->cap_H)   // [n_frames][num_rx][num_tx] complex in the plan's type
       for (int r = 0; r < d.num_rx; ++r)
@@ -1887,9 +1852,9 @@ static int run_bf(lte_plan* p, const lte_run_args* a, int B, int n_snr, const st
 
 // Fading taps, fused TX + channel, first-samples power fix-up and noise power.
 template <class R>
-static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const SisoPath& path, int B, bool coded,
-                    uint64_t cseed, const int32_t* tx_map, const R* inj_ph, int64_t inj_ph_stride,
-                    cx<R>* cap_tx_syms, cx<R>* x_out, TxChannelT<R>* ch_out) {
+static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const SisoPath& path, int B,
+                    const TxSource& src, uint64_t cseed, Inj<R> inj_ph, cx<R>* cap_tx_syms, cx<R>* x_out,
+                    TxChannelT<R>* ch_out) {
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
   const int maxd = *std::max_element(d.delays, d.delays + d.n_paths);
@@ -1902,8 +1867,7 @@ static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const Sis
     return fail(LTE_ENOMEM, "tx channel");
   {
     Timer t(p, KN_FADING, s);
-    LCHK(launch_fading<R>(s, B, rx, d.n_paths, c.gains.p, p->fid.p, cseed, inj_ph, inj_ph_stride, c.phases.p,
-                          c.coef.p));
+    LCHK(launch_fading<R>(s, B, rx, d.n_paths, c.gains.p, p->fid.p, cseed, inj_ph, c.phases.p, c.coef.p));
     if (tv)   // one (frame, RX) at a time: phases / sets are [B][rx][path]
       LCHK(launch_jakes_sets<R>(s, B * rx, d.n_paths, p->n_sym, d.N + d.cp_len, c.phases.p, c.gains.p, d.fD, d.fs,
                                 c.tcoef.p));
@@ -1923,17 +1887,15 @@ static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const Sis
   {
     Timer t(p, KN_OFDM_TX, s);
     if (path.tx == TX_FRAME) {
-      LCHK(launch_ofdm_txf<R>(s, p->grid, p->enc.p, p->enc_words, tx_map, p->txf_map.p, p->txf_re.p, B,
-                              cap_tx_syms, ch));
+      LCHK(launch_ofdm_txf<R>(s, p->grid, src, p->txf_map.p, p->txf_re.p, B, cap_tx_syms, ch));
     } else if (path.tx == TX_SYM_CH) {
-      LCHK(launch_ofdm_tx_ch<R>(s, p->grid, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, tx_map, B,
-                                cap_tx_syms, ch, precode_on(p->ct->precode, d.sc_fdm), path.tx_stage ? 1 : 0));
+      LCHK(launch_ofdm_tx_ch<R>(s, p->grid, src, B, cap_tx_syms, ch, precode_on(p->ct->precode, d.sc_fdm),
+                                path.tx_stage ? 1 : 0));
     } else if constexpr (std::is_same_v<R, double>) {   // the wave-private transmitters (lte_wave.hip)
       if (path.tx == TX_FRAME_W)
-        LCHK(launch_ofdm_txf_w(s, p->grid, p->enc.p, p->enc_words, tx_map, B, cap_tx_syms, ch,
-                               path.tx_stage ? 1 : 0));
+        LCHK(launch_ofdm_txf_w(s, p->grid, src, B, cap_tx_syms, ch, path.tx_stage ? 1 : 0));
       else
-        LCHK(launch_ofdm_tx_simo_w(s, p->grid, p->pw.p, p->PW, B, cap_tx_syms, ch));
+        LCHK(launch_ofdm_tx_simo_w(s, p->grid, src, B, cap_tx_syms, ch));
     } else {
       return fail(LTE_EINVAL, "the wave transmitters run in float64 plans only");
     }
@@ -1949,7 +1911,7 @@ static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const Sis
 // SISO / SIMO chains (uncoded, coded, MRC) in precision R.
 template <class R>
 static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, int B, int n_snr,
-                    const std::vector<double>& snr_lin, const uint32_t* inj_bits, int64_t inj_bits_stride) {
+                    const std::vector<double>& snr_lin, Inj<uint32_t> inj_bits) {
   using V = cx<R>;
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
@@ -1964,20 +1926,12 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
   std::vector<R> sl(B);
   for (int b = 0; b < B; ++b) sl[b] = do_ch ? (R)snr_lin[b] : (R)INFINITY;
   HIPCHK(hipMemcpyAsync(c.snr_lin.p, sl.data(), B * sizeof(R), hipMemcpyHostToDevice, s));
-  const R* inj_ph = nullptr;
-  int64_t inj_ph_stride = 0;
-  if (a->phases && ray_cfg) {
-    const int e = upload_inj<R>(c.inj_ph, a->phases, a->phases_stride, B, (size_t)rx * d.n_paths * 16, s, &inj_ph,
-                                &inj_ph_stride);
-    if (e != LTE_OK) return e;
-  }
-  const R* inj_z = nullptr;
-  int64_t inj_z_stride = 0;
-  if (a->noise) {
-    const int e = upload_inj<R>(c.inj_z, a->noise, a->noise_stride, B, (size_t)rx * 2 * p->L, s, &inj_z,
-                                &inj_z_stride);
-    if (e != LTE_OK) return e;
-  }
+  Inj<R> inj_ph{}, inj_z{};
+  if (a->phases && ray_cfg)
+    if (const int e = upload_inj<R>(c.inj_ph, a->phases, a->phases_stride, B, (size_t)rx * d.n_paths * 16, s, &inj_ph))
+      return e;
+  if (a->noise)
+    if (const int e = upload_inj<R>(c.inj_z, a->noise, a->noise_stride, B, (size_t)rx * 2 * p->L, s, &inj_z)) return e;
   const bool fuse = path.fused(), xhand = path.xhand;
   // HARQ round t: its own rate-matching maps, and channel / noise streams keyed
   // by seed_t (the payload stream, and k_crc_count's re-draw of it, keep seed)
@@ -1985,10 +1939,13 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
   const uint64_t cseed = a->seed + (uint64_t)hq_t * 0x9E3779B97F4A7C15ull;
   const int32_t* const tx_map = p->tx_map.p + (size_t)p->hq_slot[hq_rv] * p->n_re_bits;
   const int32_t* const rx_map = p->rx_map.p + (size_t)p->hq_slot[hq_rv] * p->n_layers * p->n_re_bits;
+  // the launchers' argument groups, each built once (the receiver's further down, when its buffers are)
+  const TxSource src{coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, tx_map};
+  const Scored sc{p->pw.p, p->PW, d.n_bits, p->frame_err.p};
   TxChannelT<R> xch{};
   if (do_tx || a->bits) {
     Timer t(p, KN_PAYLOAD);
-    LCHK(launch_payload(s, p->pw.p, p->PW, d.n_bits, coded ? CRC24A_POLY : 0, p->fid.p, a->seed, B, inj_bits, inj_bits_stride));
+    LCHK(launch_payload(s, p->pw.p, p->PW, d.n_bits, coded ? CRC24A_POLY : 0, p->fid.p, a->seed, B, inj_bits));
   }
   if ((!fuse || xhand) && c.x.alloc((size_t)d.max_frames * p->L)) return fail(LTE_ENOMEM, "TX signal buffer");
   if (do_tx) {
@@ -2002,13 +1959,11 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
       cts = c.captx.p;
     }
     if (fuse) {
-      const int e = run_txch<R>(p, s, a, path, B, coded, cseed, tx_map, inj_ph, inj_ph_stride, cts,
-                                xhand ? c.x.p : nullptr, &xch);
+      const int e = run_txch<R>(p, s, a, path, B, src, cseed, inj_ph, cts, xhand ? c.x.p : nullptr, &xch);
       if (e != LTE_OK) return e;
     } else {
       Timer t(p, KN_OFDM_TX);
-      LCHK(launch_ofdm_tx<R>(s, g, coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, tx_map, c.x.p, B, cts,
-                             precode_on(p->ct->precode, d.sc_fdm), path.tx_stage ? 1 : 0));
+      LCHK(launch_ofdm_tx<R>(s, g, src, c.x.p, B, cts, precode_on(p->ct->precode, d.sc_fdm), path.tx_stage ? 1 : 0));
     }
   } else {
     const R* in = static_cast<const R*>(a->in_signal);
@@ -2019,12 +1974,13 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
     HIPCHK(hipStreamSynchronize(s));
   }
   const bool ray = ray_cfg && do_ch;
-  const V* ysrc = ray ? c.y.p : c.x.p;
-  const int64_t yrs = ray ? p->L : 0, yfs = ray ? (int64_t)rx * p->L : p->L;
+  // the streams the receiver reads: the channel's output, or on AWGN the one TX stream for every RX
+  const RxStreams<R> rxs{.num_rx = rx, .y = ray ? c.y.p : c.x.p, .rx_stride = ray ? p->L : 0,
+                         .frame_stride = ray ? (int64_t)rx * p->L : p->L, .npow = c.npow.p, .fid = p->fid.p,
+                         .seed = cseed, .inj_z = inj_z};
   if (ray && !fuse) {
     Timer t(p, KN_FADING);
-    LCHK(launch_fading<R>(s, B, rx, d.n_paths, c.gains.p, p->fid.p, cseed, inj_ph, inj_ph_stride, c.phases.p,
-                          c.coef.p));
+    LCHK(launch_fading<R>(s, B, rx, d.n_paths, c.gains.p, p->fid.p, cseed, inj_ph, c.phases.p, c.coef.p));
   }
   if (!fuse) {
     Timer t(p, KN_CHANNEL);
@@ -2035,62 +1991,46 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
   }
   if (path.rx == RX_CHEST_DATA) {
     Timer t(p, KN_RX_CHEST);
-    LCHK(launch_rx_chest<R>(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, cseed, inj_z, inj_z_stride, c.H.p,
-                            c.pstats.p));
+    LCHK(launch_rx_chest<R>(s, g, B, rxs, c.H.p, c.pstats.p));
   }
-  Captures<R> cap;
-  if (const int e = capture_bufs<R>(p, a, B, (size_t)p->n_sym * p->Nd, &cap)) return e;
-  V* const cap_syms_dev = cap.syms;
-  uint8_t* const cap_bits_dev = cap.bits;
+  const size_t n_syms = (size_t)p->n_sym * p->Nd;
+  RxCaptures<R> cap{};
+  if (const int e = capture_bufs<R>(p, a, B, n_syms, &cap)) return e;
+  cap.H = a->cap_H ? c.H.p : nullptr;
+  cap.pstats = a->cap_pilot_stats ? c.pstats.p : nullptr;
   const bool zn = path.zn;
   if (coded && !zn && c.llr.alloc((size_t)d.max_frames * p->n_re_bits)) return fail(LTE_ENOMEM, "LLR buffer");
+  const SoftOut<R> soft = soft_out<R>(p, coded, zn);
   if (path.rx == RX_FRAME_W) {
     Timer t(p, KN_RX_DATA);
     if constexpr (std::is_same_v<R, double>)
-      LCHK(launch_rx_frame_w(s, g, ray ? 1 : 0, B, ysrc, yfs, c.npow.p, c.snr_lin.p, p->fid.p, cseed, inj_z,
-                             inj_z_stride, reinterpret_cast<R*>(zn_z<R>(p)), zn_nv<R>(p), cap_syms_dev,
-                             a->cap_H ? c.H.p : nullptr, a->cap_pilot_stats ? c.pstats.p : nullptr));
+      LCHK(launch_rx_frame_w(s, g, ray ? 1 : 0, B, rxs, c.snr_lin.p, soft, cap));
     else
       return fail(LTE_EINVAL, "the wave receivers run in float64 plans only");
   } else if (path.rx == RX_SIMO_W) {
     Timer t(p, KN_RX_DATA);
     if constexpr (std::is_same_v<R, double>)
-      LCHK(launch_rx_frame_simo_w(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, cseed, inj_z, inj_z_stride,
-                                  p->pw.p, p->PW, d.n_bits, p->frame_err.p, cap_syms_dev, cap_bits_dev));
+      LCHK(launch_rx_frame_simo_w(s, g, B, rxs, sc, cap));
     else
       return fail(LTE_EINVAL, "the wave receivers run in float64 plans only");
   } else if (path.rx == RX_FRAME) {
     Timer t(p, KN_RX_DATA);
-    LCHK(launch_rx_frame<R>(s, g, d.chain, ray ? 1 : 0, B, ysrc, yfs, c.npow.p, c.snr_lin.p, p->fid.p, cseed, inj_z,
-                            inj_z_stride, p->pw.p, p->PW, d.n_bits, p->frame_err.p,
-                            zn ? reinterpret_cast<R*>(zn_z<R>(p)) : c.llr.p, cap_syms_dev,
-                            coded ? nullptr : cap_bits_dev, zn ? zn_nv<R>(p) : nullptr,
-                            a->cap_H ? c.H.p : nullptr, a->cap_pilot_stats ? c.pstats.p : nullptr));
+    LCHK(launch_rx_frame<R>(s, g, d.chain, ray ? 1 : 0, B, rxs, c.snr_lin.p, sc, soft, cap));
   } else if (path.rx == RX_SIMO || path.rx == RX_SIMO2) {
     Timer t(p, KN_RX_DATA);
-    LCHK(launch_rx_frame_simo<R>(s, g, B, rx, ysrc, yrs, yfs, c.npow.p, p->fid.p, cseed, inj_z, inj_z_stride,
-                                 p->pw.p, p->PW, d.n_bits, p->frame_err.p, cap_syms_dev,
-                                 coded ? nullptr : cap_bits_dev,
-                                 a->cap_H ? c.H.p : nullptr, a->cap_pilot_stats ? c.pstats.p : nullptr,
-                                 path.rx == RX_SIMO2 ? 1 : 0, xhand ? &xch : nullptr, c.snr_lin.p,
-                                 !coded ? nullptr : zn ? reinterpret_cast<R*>(zn_z<R>(p)) : c.llr.p,
-                                 coded && zn ? zn_nv<R>(p) : nullptr));
+    LCHK(launch_rx_frame_simo<R>(s, g, B, rxs, sc, cap, path.rx == RX_SIMO2 ? 1 : 0, xhand ? &xch : nullptr,
+                                 c.snr_lin.p, soft));
   } else if (path.rx == RX_CHEST_DATA) {
     Timer t(p, KN_RX_DATA);
-    LCHK(launch_rx_data<R>(s, g, d.chain, ray ? 1 : 0, B, rx, ysrc, yrs, yfs, c.H.p, c.npow.p, c.snr_lin.p, p->fid.p,
-                           cseed, inj_z, inj_z_stride, p->pw.p, p->PW, d.n_bits, p->frame_err.p,
-                           zn ? reinterpret_cast<R*>(zn_z<R>(p)) : c.llr.p, cap_syms_dev,
-                           coded ? nullptr : cap_bits_dev,
-                           // the IDFT runs in receive_and_decode only (core/lte_receiver.py:318-333): the SIMO
-                           // MRC receiver (core/ofdm_core.py:1340-1534) never de-precodes
-                           precode_on(p->ct->deprecode, d.sc_fdm), zn ? zn_nv<R>(p) : nullptr,
-                           d.detector == LTE_DET_ZF ? 1 : 0));
+    // the IDFT runs in receive_and_decode only (core/lte_receiver.py:318-333): the SIMO
+    // MRC receiver (core/ofdm_core.py:1340-1534) never de-precodes
+    LCHK(launch_rx_data<R>(s, g, d.chain, ray ? 1 : 0, B, rxs, c.H.p, c.snr_lin.p, sc, soft, cap,
+                           precode_on(p->ct->deprecode, d.sc_fdm), d.detector == LTE_DET_ZF ? 1 : 0));
   }
   if (coded && do_rx) {
     // HARQ: round 0 stores zeros in the rows its map does not cover (an earlier
     // process has left sums there), later rounds add to every row they cover
-    if (const int e = decode_blocks<R>(p, a, B, rx_map, p->Nd, 0, hq_t >= 1 ? 1 : 0, zn, path.hq_skip, cap_bits_dev,
-                                       inj_bits))
+    if (const int e = decode_blocks<R>(p, a, B, rx_map, p->Nd, 0, hq_t >= 1 ? 1 : 0, soft, sc, path.hq_skip))
       return e;
     if (p->harq) {
       {
@@ -2117,7 +2057,7 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
   if (a->cap_tx_syms && do_tx)
     HIPCHK(hipMemcpyAsync(a->cap_tx_syms, c.captx.p, (size_t)B * p->n_sym * p->Nd * sizeof(V), hipMemcpyDeviceToHost,
                           s));
-  return read_back<R>(p, a, B, n_snr, coded, do_rx, cap, RxStreams<R>{rx, ysrc, yrs, yfs, cseed, inj_z, inj_z_stride});
+  return read_back<R>(p, a, B, n_snr, coded, do_rx, n_syms, rxs);
 }
 
 extern "C" {
@@ -2165,8 +2105,7 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
   HIPCHK(hipMemcpyAsync(p->snr_idx.p, si.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, s));
   HIPCHK(hipMemcpyAsync(p->fid.p, fid.data(), B * sizeof(uint64_t), hipMemcpyHostToDevice, s));
   // payload injection (packed MSB-first)
-  const uint32_t* inj_bits = nullptr;
-  int64_t inj_bits_stride = 0;
+  Inj<uint32_t> inj_bits{};
   if (a->bits) {   // one uint8 per bit from the caller, packed MSB-first on the device
     const int nf = a->bits_stride ? B : 1;
     const int nwd = (d.n_bits + 31) / 32;
@@ -2174,8 +2113,7 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
     if (p->inj_bytes.alloc(nb) || p->inj_bits.alloc((size_t)nf * nwd)) return fail(LTE_ENOMEM, "inj bits");
     HIPCHK(hipMemcpyAsync(p->inj_bytes.p, a->bits, nb, hipMemcpyHostToDevice, s));
     LCHK(launch_pack_bits(s, p->inj_bytes.p, a->bits_stride, d.n_bits, nwd, nf, p->inj_bits.p));
-    inj_bits = p->inj_bits.p;
-    inj_bits_stride = a->bits_stride ? nwd : 0;
+    inj_bits = {p->inj_bits.p, a->bits_stride ? nwd : 0};
   }
   HIPCHK(hipMemsetAsync(p->counts.p, 0, 4 * n_snr * sizeof(unsigned long long), s));
   HIPCHK(hipMemsetAsync(p->frame_err.p, 0, B * sizeof(uint32_t), s));
@@ -2189,22 +2127,22 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
   const Knobs knobs = read_knobs();   // the environment switches, once per run
   if (!p->mimo && !p->bf) {
     const SisoPath path = select_siso(p, a, knobs);
-    const int e = p->f64 ? run_siso<double>(p, a, path, B, n_snr, sl, inj_bits, inj_bits_stride)
-                         : run_siso<float>(p, a, path, B, n_snr, sl, inj_bits, inj_bits_stride);
+    const int e = p->f64 ? run_siso<double>(p, a, path, B, n_snr, sl, inj_bits)
+                         : run_siso<float>(p, a, path, B, n_snr, sl, inj_bits);
     HIPCHK(hipStreamSynchronize(s));
     p->hq_round = 0;   // the next run opens a new process unless lte_plan_harq_set_round says otherwise
     return e;
   }
   if (stages != LTE_STAGE_ALL) return fail(LTE_EUNSUP, "multi-antenna chains run all stages");
   if (p->mimo)
-    return p->f64 ? run_mimo<double>(p, a, select_mimo<double>(p, a, knobs), B, n_snr, sl, inj_bits, inj_bits_stride)
-                  : run_mimo<float>(p, a, select_mimo<float>(p, a, knobs), B, n_snr, sl, inj_bits, inj_bits_stride);
+    return p->f64 ? run_mimo<double>(p, a, select_mimo<double>(p, a, knobs), B, n_snr, sl, inj_bits)
+                  : run_mimo<float>(p, a, select_mimo<float>(p, a, knobs), B, n_snr, sl, inj_bits);
   // beamforming chain: noise scale sqrt(noise_variance / 2), noise_variance =
   // 10 ** (-snr_db / 10) (core/ofdm_core.py:2397-2399)
   std::vector<double> sig(B);
   for (int b = 0; b < B; ++b) sig[b] = std::sqrt(std::pow(10.0, -a->snr_db[b] / 10.0) / 2.0);
-  return p->f64 ? run_bf<double>(p, a, B, n_snr, sig, inj_bits, inj_bits_stride)
-                : run_bf<float>(p, a, B, n_snr, sig, inj_bits, inj_bits_stride);
+  return p->f64 ? run_bf<double>(p, a, B, n_snr, sig, inj_bits)
+                : run_bf<float>(p, a, B, n_snr, sig, inj_bits);
 }
 
 // The kernel path lte_run would take for (plan, args) under the current

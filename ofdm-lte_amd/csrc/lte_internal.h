@@ -63,11 +63,95 @@ template <> struct GridT<double> {
   __host__ __device__ static const double2* bhat(const Grid& g) { return g.bhat64; }
 };
 
+// ---------------------------------------------------------------- launcher argument groups
+// The values most launchers share, as plain aggregates: a run driver fills each
+// once (positional or designated initialisers) and hands the same object to
+// every launcher that takes it; the launcher expands the fields into its
+// kernel's parameter list.  R = float / double.
+
+// Values injected in place of the Philox draws (the reference's own, ref-compat mode)
+template <class R>
+struct Inj {
+  const R* p;       // frame b's values at p + b * stride; null: the kernel draws from Philox
+  int64_t stride;   // values between frames (0: every frame reads the same ones)
+};
+
+// The received streams as the receivers read them, and the noise they add
+template <class R>
+struct RxStreams {
+  int num_rx;             // 0: the chain has no time-domain streams (beamforming)
+  const cx<R>* y;         // sample n of (frame b, RX r) at y[b * frame_stride + r * rx_stride + n];
+  int64_t rx_stride;      //   the multi-antenna receivers read the dense [B][num_rx][L] only
+  int64_t frame_stride;   //   (strides in samples; AWGN SISO / SIMO: rx_stride 0, one stream for every RX)
+  const R* npow;          // [B][num_rx] noise power of each stream
+  const uint64_t* fid;    // [B] frame ids: with seed, the key of the Philox noise draws
+  uint64_t seed;
+  Inj<R> inj_z;           // [num_rx][2][L] unit normals per frame (re block, im block)
+};
+
+// What a transmitter maps to QAM symbols
+struct TxSource {
+  int coded;               // 1: the rate-matched stream enc through tx_map; 0: the payload words pw
+  const uint32_t* pw;      // [B][PW] payload bits, MSB first
+  int PW;
+  const uint32_t* enc;     // [B][enc_words] encoder output (coded)
+  int enc_words;
+  const int32_t* tx_map;   // [n_re_bits] source bit in enc of each RE bit (coded)
+};
+
+// What hard decisions are scored against
+struct Scored {
+  const uint32_t* pw;    // [B][PW] the transmitted payload (TxSource::pw)
+  int PW, n_bits;        // words per frame, payload bits per frame
+  uint32_t* frame_err;   // [B] bit errors per frame
+};
+
+// A receiver's soft output for the coded chains: LLRs, or the (z, nv) hand-off
+// that k_dematch_zn demaps -- llr, or z and nv together; all null: hard decisions only
+template <class R>
+struct SoftOut {
+  R* llr;     // [B][n_re][bps] max-log LLRs in RE order
+  cx<R>* z;   // [B][n_re] equalised symbols
+  R* nv;      // their sigma^2_eff: [B][n_grp][Nd] per data subcarrier; the SFBC detectors'
+              // [B][n_sym][res / 2] per Alamouti RE pair
+  bool ok() const { return (z != nullptr) == (nv != nullptr) && !(z && llr); }
+  // the kernels with one soft pointer for either form take z through it
+  R* ptr() const { return z ? reinterpret_cast<R*>(z) : llr; }
+};
+
+// What a receiver writes beside its counts when a capture asks for it (null: not asked)
+template <class R>
+struct RxCaptures {
+  cx<R>* syms;     // [B][n_syms] equalised data symbols
+  uint8_t* bits;   // [B][n_bits] hard decisions (uncoded chains; coded, k_crc_count writes the decoded bits)
+  cx<R>* H;        // SISO / SIMO fused receivers: [B][num_rx][n_grp][N] channel estimates
+  R* pstats;       // SISO / SIMO fused receivers: [B][num_rx][n_grp][2] pilot statistics
+};
+
+// The link-noise draws of the multi-antenna channel passes (transmit_mimo's 100 dB per link)
+template <class R>
+struct LinkNoise {
+  const uint64_t* fid;   // [B] frame ids: with seed, the key of the Philox draws
+  uint64_t seed;
+  Inj<R> inj_lz;         // [num_rx * num_tx][2][L] unit normals per frame (re block, im block)
+};
+
+// The links' taps the multi-antenna channel passes apply (launch_fading_mimo's outputs)
+template <class R>
+struct LinkTaps {
+  int n_paths;
+  const int32_t* delays;   // [n_paths] (device; null: flat links)
+  const cx<R>* coef;       // [B][num_rx][num_tx] links, each n_paths * n_cs sets of mimo_ncf<R>() terms
+  const R* phases;         // exact-Jakes mode (MimoGrid::exact_jakes) only: [B][links][n_paths][16]
+  const R* gains;          // exact-Jakes mode only: [n_paths]
+  double fs;
+};
+
 // launchers (return hipError_t as int)
 constexpr int CRC24A_POLY = 0x864CFB, CRC24B_POLY = 0x800063;   // crc.py polynomials without x^24
-// crc: CRC polynomial to append (0: none)
+// crc: CRC polynomial to append (0: none); inj: the caller's payload words [PW] per frame in place of the Philox ones
 int launch_payload(hipStream_t s, uint32_t* pw, int PW, int n_bits, int crc, const uint64_t* fid,
-                   uint64_t seed, int B, const uint32_t* inj, int64_t inj_stride);
+                   uint64_t seed, int B, Inj<uint32_t> inj);
 // qmask: encode_qmask(cbs, C, qstride) on the host, C x qstride uint16, qstride >= max K + 32 and a
 // multiple of 2 (the kernel reads whole 32-entry rows as uint32 pairs; entries past K are zero)
 void encode_qmask(const CbInfo* cbs, int C, int qstride, uint16_t* out);
@@ -76,14 +160,14 @@ int launch_encode(hipStream_t s, const uint32_t* pw, int PW, int KWmax, uint32_t
 // Signal-chain launchers, R = double (the reference's precision, default) or
 // float (fast mode); explicit instances in lte_kernels.hip.
 template <class R>
-int launch_ofdm_tx(hipStream_t s, const Grid& g, int coded, const uint32_t* pw, int PW, const uint32_t* enc,
-                   int enc_words, const int32_t* tx_map, cx<R>* x, int B, cx<R>* cap_syms, int sc_fdm, int stage);
+int launch_ofdm_tx(hipStream_t s, const Grid& g, const TxSource& src, cx<R>* x, int B, cx<R>* cap_syms, int sc_fdm,
+                   int stage);
 // stage: the coded stream staged in LDS per slot (k_ofdm_tx, with or without the channel);
 // scf_el: sizeof(cx<R>) for the coded SC-FDM transmitter (a second symbol buffer), else 0
 bool tx_stage_supported(const Grid& g, int coded, int enc_words, int scf_el = 0);
 template <class R>
 int launch_fading(hipStream_t s, int B, int num_rx, int n_paths, const R* gains_dev, const uint64_t* fid,
-                  uint64_t seed, const R* inj_ph, int64_t inj_stride, R* phases, cx<R>* coef);
+                  uint64_t seed, Inj<R> inj_ph, R* phases, cx<R>* coef);
 template <class R>
 int launch_channel(hipStream_t s, const Grid& g, int B, int num_rx, int rayleigh, int n_paths,
                    const int32_t* delays_dev, const R* gains_dev, R fD, R fs, const R* phases, const cx<R>* coef,
@@ -91,11 +175,10 @@ int launch_channel(hipStream_t s, const Grid& g, int B, int num_rx, int rayleigh
 template <class R>
 int launch_npow(hipStream_t s, int B, int num_rx, const R* pow_part, int nblk, int L, const R* snr_lin, R* npow);
 int channel_nblk(int L);   // power partials per (frame, rx) written by launch_channel
-// capture of the received streams [B][num_rx][L] with their noise added (k_cap_rx): y as the
-// receivers read it (strides in samples), the receivers' noise draws (Philox, or inj_z)
+// capture of the received streams [B][rx.num_rx][L] with their noise added (k_cap_rx): the
+// streams as the receivers read them, the receivers' noise draws
 template <class R>
-int launch_cap_rx(hipStream_t s, int L, int num_rx, int B, const cx<R>* y, int64_t y_rx_stride, int64_t y_frame_stride,
-                  const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z, int64_t inj_stride, cx<R>* out);
+int launch_cap_rx(hipStream_t s, int L, int B, const RxStreams<R>& rx, cx<R>* out);
 // OFDM TX with the static-tap multipath channel fused in (SISO, fD = 0, every
 // delay <= CP, N >= 512): k_ofdm_tx<.., CH> writes the received stream outside
 // each symbol's CP (the only samples the receiver reads) and the power of the
@@ -135,25 +218,23 @@ template <class R>
 int launch_jakes_sets(hipStream_t s, int B, int n_paths, int n_sym, int sym_len, const R* phases, const R* gains,
                       double fD, double fs, cx<R>* tcoef);
 template <class R>
-int launch_ofdm_tx_ch(hipStream_t s, const Grid& g, int coded, const uint32_t* pw, int PW, const uint32_t* enc,
-                      int enc_words, const int32_t* tx_map, int B, cx<R>* cap_syms, const TxChannelT<R>& ch,
-                      int sc_fdm, int stage);
+int launch_ofdm_tx_ch(hipStream_t s, const Grid& g, const TxSource& src, int B, cx<R>* cap_syms,
+                      const TxChannelT<R>& ch, int sc_fdm, int stage);
 template <class R>
 int launch_chan_fix(hipStream_t s, const Grid& g, int B, const TxChannelT<R>& ch);
 // coded TX + channel with one slot per frame (the frame's coded streams staged
-// in LDS once); same outputs as launch_ofdm_tx_ch(coded = 1).  txf_map / txf_re
+// in LDS once); same outputs as launch_ofdm_tx_ch on a coded source.  txf_map / txf_re
 // (both or neither): the bank-aware lane order of plan_txf_lane_order --
 // [n_sym][N/2][bps] sources and [n_sym][N/2] RE of each slot.
 template <class R>
-int launch_ofdm_txf(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_words, const int32_t* tx_map,
-                    const int32_t* txf_map, const int32_t* txf_re, int B, cx<R>* cap_syms,
-                    const TxChannelT<R>& ch);
+int launch_ofdm_txf(hipStream_t s, const Grid& g, const TxSource& src, const int32_t* txf_map, const int32_t* txf_re,
+                    int B, cx<R>* cap_syms, const TxChannelT<R>& ch);
 // wave-private f64 coded TX + static taps (lte_wave.hip), N = 2048, SISO, four
 // paths with every delay <= 64: launch_ofdm_txf's outputs (Knobs::tx_wave, off
 // by default).  stage: the coded streams staged in the wave's LDS
 bool txf_w_supported(const Grid& g, int f64, int n_paths, int max_delay, int num_rx, int tv);
-int launch_ofdm_txf_w(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_words, const int32_t* tx_map, int B,
-                      double2* cap_syms, const TxChannelT<double>& ch, int stage);
+int launch_ofdm_txf_w(hipStream_t s, const Grid& g, const TxSource& src, int B, double2* cap_syms,
+                      const TxChannelT<double>& ch, int stage);
 // the lane order: for each OFDM symbol a permutation of its Nd data REs over
 // the N/2 TX slots, greedy per 32-slot group (one ds_read_b32 lane group) so
 // that each of the bps coded-bit gathers sees as few distinct words per LDS
@@ -164,52 +245,40 @@ void plan_txf_lane_order(const std::vector<int32_t>& tx_map, const std::vector<i
                          int Nd, int bps, int slots, std::vector<int32_t>& txf_map, std::vector<int32_t>& txf_re,
                          double model[2]);
 template <class R>
-int launch_rx_chest(hipStream_t s, const Grid& g, int B, int num_rx, const cx<R>* y, int64_t y_rx_stride,
-                    int64_t y_frame_stride, const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z,
-                    int64_t inj_stride, cx<R>* H, R* pstats);
-// coded: nv_out set -> llr takes z (cx<R> per RE), nv_out sigma^2_eff.
+int launch_rx_chest(hipStream_t s, const Grid& g, int B, const RxStreams<R>& rx, cx<R>* H, R* pstats);
+// H: launch_rx_chest's estimates (cap.H / cap.pstats are not read: launch_rx_chest always writes both).
 // LTE_CHAIN_SCFDM_CODED: always de-precodes (sc_fdm is not read), LLRs only; eq_zf: its ZF rule (0: MMSE).
 template <class R>
-int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B, int num_rx, const cx<R>* y,
-                   int64_t y_rx_stride, int64_t y_frame_stride, const cx<R>* H, const R* npow, const R* snr_lin,
-                   const uint64_t* fid, uint64_t seed, const R* inj_z, int64_t inj_stride, const uint32_t* pw, int PW,
-                   int n_bits, uint32_t* frame_err, R* llr, cx<R>* cap_syms, uint8_t* cap_bits, int sc_fdm = 0,
-                   R* nv_out = nullptr, int eq_zf = 0);
+int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B, const RxStreams<R>& rx,
+                   const cx<R>* H, const R* snr_lin, const Scored& sc, const SoftOut<R>& soft,
+                   const RxCaptures<R>& cap, int sc_fdm = 0, int eq_zf = 0);
 // k_rx_data's CHAIN argument for LTE_CHAIN_SCFDM_CODED with the ZF rule (the chain value plus this bit)
 constexpr int RX_EQ_ZF = 0x100;
 // Fused SISO receiver (estimation + data path, one slot per frame): coded or
-// uncoded, one RX, no SC-FDM.  nv_out set: llr takes z per RE and nv_out
-// sigma^2_eff per (frame, group, data subcarrier); H / pstats: optional captures.
+// uncoded, one RX, no SC-FDM.  soft.nv: sigma^2_eff per (frame, group, data
+// subcarrier); cap.H / cap.pstats: optional captures.
 bool rx_frame_supported(const Grid& g, int chain, int num_rx, int sc_fdm);
 // wave-private f64 coded receiver (lte_wave.hip): k_rx_frame's outputs (ZN demap:
-// equalised symbols zo + sigma^2_eff nv_out) for N = 2048 (Knobs::rx_wave, off
-// by default)
+// equalised symbols soft.z + sigma^2_eff soft.nv, both required) for N = 2048
+// (Knobs::rx_wave, off by default)
 bool rx_frame_w_supported(const Grid& g, int chain, int f64);
-int launch_rx_frame_w(hipStream_t s, const Grid& g, int rayleigh, int B, const double2* y, int64_t y_frame_stride,
-                      const double* npow, const double* snr_lin, const uint64_t* fid, uint64_t seed,
-                      const double* inj_z, int64_t inj_stride, double* zo, double* nv_out, double2* cap_syms,
-                      double2* H, double* pstats);
+int launch_rx_frame_w(hipStream_t s, const Grid& g, int rayleigh, int B, const RxStreams<double>& rx,
+                      const double* snr_lin, const SoftOut<double>& soft, const RxCaptures<double>& cap);
 template <class R>
-int launch_rx_frame(hipStream_t s, const Grid& g, int chain, int rayleigh, int B, const cx<R>* y,
-                    int64_t y_frame_stride, const R* npow, const R* snr_lin, const uint64_t* fid, uint64_t seed,
-                    const R* inj_z, int64_t inj_stride, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                    R* llr, cx<R>* cap_syms, uint8_t* cap_bits, R* nv_out, cx<R>* H, R* pstats);
+int launch_rx_frame(hipStream_t s, const Grid& g, int chain, int rayleigh, int B, const RxStreams<R>& rx,
+                    const R* snr_lin, const Scored& sc, const SoftOut<R>& soft, const RxCaptures<R>& cap);
 // Fused SIMO MRC receiver (2..RXS_MAXRX RX): one slot per frame walks
-// its symbols, every RX's estimate in registers; H / pstats: optional captures
-// [B][num_rx][n_grp][N] / [B][num_rx][n_grp][2].  pairs: k_rx_frame_simo2
-// (rx_simo2_ok), else k_rx_frame_simo.  llr null: uncoded (hard decisions
-// against pw, bit errors into frame_err).  llr set (LTE_CHAIN_SIMO_CODED; needs
-// snr_lin, no xc hand-over): soft output and no error count -- with nv_out
-// (16 / 64-QAM) llr takes z per RE and nv_out sigma^2_eff per (frame, group,
-// data subcarrier) as launch_rx_frame's, else llr takes bps LLRs per RE.
+// its symbols, every RX's estimate in registers; cap.H / cap.pstats: optional
+// captures.  pairs: k_rx_frame_simo2 (rx_simo2_ok), else k_rx_frame_simo.
+// soft empty: uncoded (hard decisions scored against sc).  soft set
+// (LTE_CHAIN_SIMO_CODED; needs snr_lin, no xc hand-over): soft output and no
+// error count -- (z, nv) (16 / 64-QAM) as launch_rx_frame's, else LLRs.
 constexpr int RXS_MAXRX = 4;
 bool rx_frame_simo_supported(const Grid& g, int num_rx);
 template <class R>
-int launch_rx_frame_simo(hipStream_t s, const Grid& g, int B, int num_rx, const cx<R>* y, int64_t y_rx_stride,
-                         int64_t y_frame_stride, const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z,
-                         int64_t inj_stride, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                         cx<R>* cap_syms, uint8_t* cap_bits, cx<R>* H, R* pstats, int pairs,
-                         const TxChannelT<R>* xc, const R* snr_lin, R* llr, R* nv_out);
+int launch_rx_frame_simo(hipStream_t s, const Grid& g, int B, const RxStreams<R>& rx, const Scored& sc,
+                         const RxCaptures<R>& cap, int pairs, const TxChannelT<R>* xc, const R* snr_lin,
+                         const SoftOut<R>& soft);
 // the paired SIMO receiver applies (N = 1024, an even RX count, no H / pilot
 // statistics capture); xc->x_out (the TX's symbol handoff) needs it
 bool rx_simo2_ok(const Grid& g, int num_rx, bool H, bool pstats);
@@ -223,7 +292,7 @@ int launch_dematch(hipStream_t s, const R* llr, int T, int B, const int32_t* rx_
                    const int64_t* rows, int ch, int g0 = 0, int add0 = 0);
 // dematch with the soft demapper fused in: reads the equalised symbols z
 // ([B][n_re]) and their noise variances ([B][n_grp][nd] per data subcarrier,
-// from the receivers' nv_out mode; nv_pairs: [B][n_sym][nd / 2] per Alamouti
+// from the receivers' SoftOut::nv; nv_pairs: [B][n_sym][nd / 2] per Alamouti
 // RE pair, k_det_sfbc's) instead of LLRs; same decoder rows as
 // launch_dematch (bps 4 / 6)
 template <class R>
@@ -310,9 +379,9 @@ int logmap_on();
 int launch_bcjr64(hipStream_t s, const double* ls, const double* lp, const double* la, int n, int ncb,
                   double* alpha_scratch, double* app);
 int launch_crc_count(hipStream_t s, const CbInfo* cbi_dev, int C, uint32_t* const* dec, const int* KW, int B,
-                     const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err, uint32_t* frame_crc,
-                     uint8_t* cap_bits, int b0 = 0, const uint64_t* fid = nullptr, uint64_t seed = 0);
-// (fid given: the transmitted words are re-drawn from k_payload's Philox counters instead of read from pw)
+                     const Scored& sc, uint32_t* frame_crc, uint8_t* cap_bits, int b0 = 0,
+                     const uint64_t* fid = nullptr, uint64_t seed = 0);
+// (fid given: the transmitted words are re-drawn from k_payload's Philox counters instead of read from sc.pw)
 int launch_accumulate(hipStream_t s, int B, int coded, int n_bits, int n_snr, const int32_t* snr_idx,
                       const uint32_t* frame_err, const uint32_t* frame_crc, unsigned long long* counts);
 template <class R>
@@ -397,26 +466,23 @@ struct TxLinkPower {
   int merged;
 };
 template <class R>
-int launch_ofdm_tx_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, const uint32_t* pw, int PW,
-                        const uint32_t* enc, int enc_words, const int32_t* tx_map, cx<R>* x, int B,
+int launch_ofdm_tx_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, const TxSource& src, cx<R>* x, int B,
                         const TxLinkPower<R>& lp, int per_frame);
 bool tx_mimo_frame_supported(const Grid& g, int coded, int enc_words);
 // per link path: f32 h(n) = A + B d + C d^2 around the centre of n's OFDM
 // symbol (fD != 0), or A (fD == 0); f64 A (fD == 0) or the phases (exact Jakes)
 template <class R>
 int launch_fading_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, int rayleigh, int n_paths,
-                       const R* gains, double fD, double fs, const uint64_t* fid, uint64_t seed,
-                       const R* inj_ph, int64_t inj_ph_stride, const R* inj_h, int64_t inj_h_stride,
-                       cx<R>* coef, R* phases);
+                       const R* gains, double fD, double fs, const uint64_t* fid, uint64_t seed, Inj<R> inj_ph,
+                       Inj<R> inj_h, cx<R>* coef, R* phases);
 // TX + flat (AWGN) channel in one pass per (frame, symbol, RX): y [B][num_rx][L]
 // and pow_part [B][num_rx][nblk] (per OFDM symbol); coef from launch_fading_mimo
 enum FlatTx { FLAT_BLOCK, FLAT_PR, FLAT_WAVE };   // k_ofdm_txch_flat, its <.., PR> form, k_ofdm_txch_flat_w
 bool txch_flat_pr_supported(const Grid& g, const MimoGrid& m);
 bool txch_flat_w_supported(const Grid& g, const MimoGrid& m, int f64);
 template <class R>
-int launch_ofdm_txch_flat(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, const uint32_t* pw, int PW,
-                          const uint32_t* enc, int enc_words, const int32_t* tx_map, const cx<R>* coef, cx<R>* y,
-                          R* pow_part, int nblk, int B, FlatTx variant);
+int launch_ofdm_txch_flat(hipStream_t s, const Grid& g, const MimoGrid& m, const TxSource& src, const cx<R>* coef,
+                          cx<R>* y, R* pow_part, int nblk, int B, FlatTx variant);
 // config 4: SFBC TX + static-tap Rayleigh links in one pass per frame (y gets
 // the faded RX signals, lp.part one power per link); then the link sigmas, the
 // combined link noise added to y and the RX power partials pow_part
@@ -424,9 +490,8 @@ int launch_ofdm_txch_flat(hipStream_t s, const Grid& g, const MimoGrid& m, int c
 template <class R>
 bool sfbc_txch_supported(const Grid& g, const MimoGrid& m, int n_paths, int max_delay);
 template <class R>
-int launch_ofdm_txch_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, const uint32_t* pw, int PW,
-                          const uint32_t* enc, int enc_words, const int32_t* tx_map, const TxLinkPower<R>& lp,
-                          cx<R>* y, int B);
+int launch_ofdm_txch_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, const TxSource& src,
+                          const TxLinkPower<R>& lp, cx<R>* y, int B);
 // config 4's merged link noise (Philox mode, full chain, no capture of the
 // received streams or noise powers): instead of adding the RX's 100 dB link
 // noise to y0_r (k_link_noise_pairs) and measuring the noisy power, the RX's
@@ -441,9 +506,10 @@ int launch_ofdm_txch_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int c
 template <class R>
 int launch_npow_sfbc_merged(hipStream_t s, int B, int num_rx, int num_tx, const R* link_part, int L, const R* snr_lin,
                             R* npow);
+// (Philox draws only: ln.inj_lz is refused)
 template <class R>
 int launch_link_noise_add(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const R* link_part, R* link_sigma,
-                          cx<R>* y, const uint64_t* fid, uint64_t seed, R* pow_part, int* pow_nblk);
+                          cx<R>* y, const LinkNoise<R>& ln, R* pow_part, int* pow_nblk);
 // the channel pass on the coefficient path: k_channel_tay (with its J samples
 // per thread, G RX per group, economised sets) or k_channel_mimo
 struct ChanMimoSel {
@@ -453,23 +519,18 @@ struct ChanMimoSel {
 };
 template <class R>
 ChanMimoSel channel_mimo_select(const MimoGrid& m, int n_paths, int sym_len, double fs, const Knobs& k);
-// phases / gains: exact-Jakes mode (m.exact_jakes) only
 template <class R>
-int launch_channel_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, int n_paths, const int32_t* delays,
-                        const cx<R>* coef, const R* phases, const R* gains, double fs, const cx<R>* x, cx<R>* y,
-                        int link_noise, const uint64_t* fid, uint64_t seed, const R* inj_lz, int64_t inj_lz_stride,
-                        R* link_part, R* link_sigma, R* pow_part, int nblk, const ChanMimoSel& sel,
-                        int link_part_done);
+int launch_channel_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const LinkTaps<R>& taps,
+                        const cx<R>* x, cx<R>* y, int link_noise, const LinkNoise<R>& ln, R* link_part, R* link_sigma,
+                        R* pow_part, int nblk, const ChanMimoSel& sel, int link_part_done);
 // OFDM symbols (blocks of N + cp samples) of a stream: the power partials per
 // (frame, rx) the multi-antenna channel passes write
 int mimo_channel_nblk(int L, int sym_len);
 // per link [mean|x|^2, mean|y|^2, Re, Im mean(y conj x)] of the link's output
 // y (with its 100 dB link noise when link_sigma is set)
 template <class R>
-int launch_link_stats(hipStream_t s, const Grid& g, const MimoGrid& m, int B, int n_paths, const int32_t* delays,
-                      const cx<R>* coef, const R* phases, const R* gains, double fs, const cx<R>* x,
-                      const R* link_sigma, const uint64_t* fid, uint64_t seed, const R* inj_lz, int64_t inj_lz_stride,
-                      R* part, int nblk, R* stats);
+int launch_link_stats(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const LinkTaps<R>& taps,
+                      const cx<R>* x, const R* link_sigma, const LinkNoise<R>& ln, R* part, int nblk, R* stats);
 // noise power per RX: ((P / div) / snr): div = num_tx (transmit_mimo) or 1 (spatial)
 template <class R>
 int launch_npow_mimo(hipStream_t s, int B, int num_rx, const R* pow_part, int nblk, int L, const R* snr_lin,
@@ -480,44 +541,39 @@ bool rx_fft_mimo_w_supported(const Grid& g, const MimoGrid& m, int f64, int h_pi
 bool rx_simo_w_supported(const Grid& g, int chain, int num_rx, int f64, bool H, bool pstats, bool xin);
 bool tx_simo_w_supported(const Grid& g, int f64, int coded, int sc_fdm, int n_paths, int max_delay, int num_rx,
                          bool tv, bool xout);
-int launch_ofdm_tx_simo_w(hipStream_t s, const Grid& g, const uint32_t* pw, int PW, int B, double2* cap_syms,
+int launch_ofdm_tx_simo_w(hipStream_t s, const Grid& g, const TxSource& src, int B, double2* cap_syms,
                           const TxChannelT<double>& ch);
-int launch_rx_frame_simo_w(hipStream_t s, const Grid& g, int B, int num_rx, const double2* y, int64_t y_rx_stride,
-                           int64_t y_frame_stride, const double* npow, const uint64_t* fid, uint64_t seed,
-                           const double* inj_z, int64_t inj_stride, const uint32_t* pw, int PW, int n_bits,
-                           uint32_t* frame_err, double2* cap_syms, uint8_t* cap_bits);
-int launch_rx_fft_mimo_w(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const double2* y, const double* npow,
-                         const uint64_t* fid, uint64_t seed, const double* inj_z, int64_t inj_stride, double2* Y,
-                         double2* H);
+int launch_rx_frame_simo_w(hipStream_t s, const Grid& g, int B, const RxStreams<double>& rx, const Scored& sc,
+                           const RxCaptures<double>& cap);
+int launch_rx_fft_mimo_w(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const RxStreams<double>& rx,
+                         double2* Y, double2* H);
 template <class R>
 // h_pilots: H receives the LS pilot estimates [b][rx][e][tx][maxP] instead of
 // the interpolated [b][rx][e][tx][n_dsc] (launch_det_spatial's h_pilots
 // interpolates them per RE with the same mimo_interp)
-int launch_rx_fft_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const cx<R>* y, const R* npow,
-                       const uint64_t* fid, uint64_t seed, const R* inj_z, int64_t inj_stride, cx<R>* Y, cx<R>* H,
-                       int h_pilots);
+int launch_rx_fft_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const RxStreams<R>& rx, cx<R>* Y,
+                       cx<R>* H, int h_pilots);
 // config 4's receiver + SFBC detector in one pass per frame (k_rx_sfbc): the
 // outputs of launch_rx_fft_mimo + launch_det_sfbc (zn handoff or bit errors)
-// without Y / H in HBM
+// without Y / H in HBM (Philox draws only: rx.inj_z is refused; coded needs soft.z / soft.nv)
 template <class R>
 bool rx_sfbc_supported(const Grid& g, const MimoGrid& m);
 template <class R>
-int launch_rx_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, int B, const cx<R>* y, const R* npow,
-                   const uint64_t* fid, uint64_t seed, const R* snr_lin, const uint32_t* pw, int PW, int n_bits,
-                   uint32_t* frame_err, cx<R>* zo, R* nvo);
+int launch_rx_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, int B, const RxStreams<R>& rx,
+                   const R* snr_lin, const Scored& sc, const SoftOut<R>& soft);
 template <class R>
-// coded: LLRs to llr, or (zo != null) the combined symbols to zo [B][n_sym][res]
-// and sigma^2_eff per RE pair to nvo [B][n_sym][res / 2] for launch_dematch_zn
+// coded: LLRs to soft.llr, or the combined symbols to soft.z [B][n_sym][res]
+// and sigma^2_eff per RE pair to soft.nv [B][n_sym][res / 2] for launch_dematch_zn
 int launch_det_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, int rayleigh, int B, const cx<R>* Y,
-                    const cx<R>* H, const R* snr_lin, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                    R* llr, cx<R>* cap_syms, uint8_t* cap_bits, cx<R>* zo = nullptr, R* nvo = nullptr);
-// llr set (LTE_CHAIN_SPATIAL_CODED; MMSE / ZF / MRC): the soft detector -- cap_syms
-// gets the unbiased estimates, llr [B][n_sym * res][bps] the max-log LLRs in RE
-// order; frame_err and cap_bits are not written
+                    const cx<R>* H, const R* snr_lin, const Scored& sc, const SoftOut<R>& soft,
+                    const RxCaptures<R>& cap);
+// soft.llr set (LTE_CHAIN_SPATIAL_CODED; MMSE / ZF / MRC): the soft detector -- cap.syms
+// gets the unbiased estimates, soft.llr [B][n_sym * res][bps] the max-log LLRs in RE
+// order; sc.frame_err and cap.bits are not written.  No (z, nv) form.
 template <class R>
 int launch_det_spatial(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const cx<R>* Y, const cx<R>* H,
-                       const double* nvar, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                       cx<R>* cap_syms, uint8_t* cap_bits, int h_pilots, int stage, R* llr = nullptr);
+                       const double* nvar, const Scored& sc, const SoftOut<R>& soft, const RxCaptures<R>& cap,
+                       int h_pilots, int stage);
 bool det_spatial_stage_supported(const MimoGrid& m, int f64, int n_sym, int B, int h_pilots);
 // SFBCAlamouti.encode (decode = 0: a = symbols -> o0 = TX0, o1 = TX1) / .decode
 // (decode = 1: a = rx, h0 / h1 the per-SC estimates -> o0), float64 [n] complex, n even
@@ -542,9 +598,8 @@ struct BfFrameT {
 // sigma: per frame noise scale sqrt(10^(-SNR/10) / 2) (core/ofdm_core.py:2397-2399)
 template <class R>
 int launch_bf(hipStream_t s, int B, int n_sym, int Nd, int bps, int num_tx, int num_rx, int adaptive, int ncb,
-              const double* cb, const uint64_t* fid, uint64_t seed, const R* inj_h, int64_t inj_h_stride,
-              BfFrameT<R>* fr, const R* sigma, const uint32_t* pw, int PW, int n_bits, const R* inj_z,
-              int64_t inj_z_stride, uint32_t* frame_err, cx<R>* cap_syms, uint8_t* cap_bits);
+              const double* cb, const uint64_t* fid, uint64_t seed, Inj<R> inj_h, BfFrameT<R>* fr, const R* sigma,
+              const Scored& sc, Inj<R> inj_z, const RxCaptures<R>& cap);
 
 // turbo modes
 enum { TM_DEC1 = 0, TM_DEC2 = 1, TM_DECODE = 2, TM_APP = 3, TM_FINAL = 4 };  // TM_DECODE: full decode (iterations + decisions)

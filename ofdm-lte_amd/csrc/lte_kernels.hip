@@ -127,14 +127,14 @@ __global__ __launch_bounds__(WG) void k_payload(uint32_t* __restrict__ pw, int P
 }
 
 int launch_payload(hipStream_t s, uint32_t* pw, int PW, int n_bits, int crc, const uint64_t* fid, uint64_t seed,
-                   int B, const uint32_t* inj, int64_t inj_stride) {
+                   int B, Inj<uint32_t> inj) {
   const uint32_t poly = (uint32_t)crc & 0xFFFFFFu;
   if (PW < 1 || n_bits < 0 || (poly && (!(poly & 1u) || PW * 32 < n_bits + 24))) return (int)hipErrorInvalidValue;
   const int KG = ((PW + 3) / 4 + 63) / 64;   // 128-bit groups per lane
   const int fpb = WG / 64;
   const int blocks = std::max(1, std::min((B + fpb - 1) / fpb, 1024));   // waves loop over frames (tables amortised)
   hipLaunchKernelGGL(k_payload, dim3(blocks), dim3(WG), 0, s, pw, PW, n_bits, KG,
-                     crc_tree(poly, KG, n_bits), fid, seed, B, inj, inj_stride);
+                     crc_tree(poly, KG, n_bits), fid, seed, B, inj.p, inj.stride);
   return (int)hipGetLastError();
 }
 
@@ -386,8 +386,9 @@ bool tx_stage_supported(const Grid& g, int coded, int enc_words, int scf_el) {
 }
 
 template <class R>
-int launch_ofdm_tx(hipStream_t s, const Grid& g, int coded, const uint32_t* pw, int PW, const uint32_t* enc,
-                   int enc_words, const int32_t* tx_map, cx<R>* x, int B, cx<R>* cap_syms, int sc_fdm, int stage) {
+int launch_ofdm_tx(hipStream_t s, const Grid& g, const TxSource& src, cx<R>* x, int B, cx<R>* cap_syms, int sc_fdm,
+                   int stage) {
+  const int coded = src.coded, enc_words = src.enc_words;
   const int spw = WG / (g.N >> 3);
   const int64_t total = (int64_t)B * g.n_sym;
   if (total > 0x7FFFFFFF - spw || (g.bps != 2 && g.bps != 4 && g.bps != 6)) return (int)hipErrorInvalidValue;
@@ -403,8 +404,8 @@ int launch_ofdm_tx(hipStream_t s, const Grid& g, int coded, const uint32_t* pw, 
     with_bool(coded, [&](auto C) {
       with_bool(sc_fdm, [&](auto S) {
         constexpr bool SCF = S();
-        hipLaunchKernelGGL((k_ofdm_tx<R, C(), Q(), SCF>), dim3(blocks), dim3(WG), shm, s, g, pw, PW, enc, enc_words,
-                           tx_map, x, B, cap_syms, stage_enc, TxChannelT<R>{});
+        hipLaunchKernelGGL((k_ofdm_tx<R, C(), Q(), SCF>), dim3(blocks), dim3(WG), shm, s, g, src.pw, src.PW, src.enc,
+                           src.enc_words, src.tx_map, x, B, cap_syms, stage_enc, TxChannelT<R>{});
       });
     });
   }));
@@ -416,9 +417,9 @@ bool txch_supported(const Grid& g, int n_paths, int max_delay) {
 }
 
 template <class R>
-int launch_ofdm_tx_ch(hipStream_t s, const Grid& g, int coded, const uint32_t* pw, int PW, const uint32_t* enc,
-                      int enc_words, const int32_t* tx_map, int B, cx<R>* cap_syms, const TxChannelT<R>& ch,
-                      int sc_fdm, int stage) {
+int launch_ofdm_tx_ch(hipStream_t s, const Grid& g, const TxSource& src, int B, cx<R>* cap_syms,
+                      const TxChannelT<R>& ch, int sc_fdm, int stage) {
+  const int coded = src.coded, enc_words = src.enc_words;
   const int spw = WG / (g.N >> 3);
   const int64_t total = (int64_t)B * g.n_sym;
   const int scf_el = coded && sc_fdm ? (int)sizeof(cx<R>) : 0;   // (sc_fdm: as launch_ofdm_tx)
@@ -445,8 +446,9 @@ int launch_ofdm_tx_ch(hipStream_t s, const Grid& g, int coded, const uint32_t* p
               // float64 static taps of the ITU path counts 4 and 6: the count at
               // compile time (tx_channel NP)
               constexpr int NP = CH == 1 && !SCF && sizeof(R) == 8 ? P() : 0;
-              hipLaunchKernelGGL((k_ofdm_tx<R, C(), Q(), SCF, CH, NC, NP>), dim3(blocks), dim3(WG), shm, s, g, pw, PW,
-                                 enc, enc_words, tx_map, (cx<R>*)nullptr, B, cap_syms, stage_enc, ch);
+              hipLaunchKernelGGL((k_ofdm_tx<R, C(), Q(), SCF, CH, NC, NP>), dim3(blocks), dim3(WG), shm, s, g, src.pw,
+                                 src.PW, src.enc, src.enc_words, src.tx_map, (cx<R>*)nullptr, B, cap_syms, stage_enc,
+                                 ch);
             });
           });
         });
@@ -577,19 +579,20 @@ __global__ __launch_bounds__(WG * SP, TXF_WAVES) void k_ofdm_txf(Grid g, const u
 // k_ofdm_txf's compile-time-path-count instance (N = 2048): SP = 2 takes one
 // 512-thread block per frame and 64 KB + the staged streams of LDS
 template <class R, int BPS, int SP>
-static void txf_peda_launch(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_words, const int32_t* tx_map,
-                            const int32_t* txf_map, const int32_t* txf_re, int B, cx<R>* cap_syms,
-                            const TxChannelT<R>& ch, int blocks, size_t shm, size_t shm2) {
+static void txf_peda_launch(hipStream_t s, const Grid& g, const TxSource& src, const int32_t* txf_map,
+                            const int32_t* txf_re, int B, cx<R>* cap_syms, const TxChannelT<R>& ch, int blocks,
+                            size_t shm, size_t shm2) {
   auto k = k_ofdm_txf<R, BPS, 2048, false, 4, SP>;
   if (SP == 2) (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm2);
-  hipLaunchKernelGGL(k, dim3(SP == 2 ? B : blocks), dim3(WG * SP), SP == 2 ? shm2 : shm, s, g, enc, enc_words, tx_map,
-                     txf_map, txf_re, B, cap_syms, ch);
+  hipLaunchKernelGGL(k, dim3(SP == 2 ? B : blocks), dim3(WG * SP), SP == 2 ? shm2 : shm, s, g, src.enc, src.enc_words,
+                     src.tx_map, txf_map, txf_re, B, cap_syms, ch);
 }
 template <class R>
-int launch_ofdm_txf(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_words, const int32_t* tx_map,
-                    const int32_t* txf_map, const int32_t* txf_re, int B, cx<R>* cap_syms,
-                    const TxChannelT<R>& ch) {
+int launch_ofdm_txf(hipStream_t s, const Grid& g, const TxSource& src, const int32_t* txf_map, const int32_t* txf_re,
+                    int B, cx<R>* cap_syms, const TxChannelT<R>& ch) {
   const int spw = WG / (g.N >> 3);
+  const int enc_words = src.enc_words;
+  if (!src.coded) return (int)hipErrorInvalidValue;   // a coded transmitter
   if (!txch_supported(g, ch.n_paths, ch.max_delay) || (g.bps != 2 && g.bps != 4 && g.bps != 6)) return (int)hipErrorInvalidValue;
   const size_t shm = (size_t)spw * g.N * sizeof(cx<R>) + (TXF_STAGE ? (size_t)spw * enc_words * sizeof(uint32_t) : 0);
   if (shm > 65536) return (int)hipErrorInvalidValue;
@@ -599,14 +602,14 @@ int launch_ofdm_txf(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_w
   return launch_status(with_bps(g.bps, [&](auto Q) {
     with_n<2048>(g.N, [&](auto NC) {
       if (ch.tcoef)
-        hipLaunchKernelGGL((k_ofdm_txf<R, Q(), NC(), true>), dim3(blocks), dim3(WG), shm, s, g, enc, enc_words,
-                           tx_map, txf_map, txf_re, B, cap_syms, ch);
+        hipLaunchKernelGGL((k_ofdm_txf<R, Q(), NC(), true>), dim3(blocks), dim3(WG), shm, s, g, src.enc,
+                           src.enc_words, src.tx_map, txf_map, txf_re, B, cap_syms, ch);
       else if (NC() == 2048 && ch.n_paths == 4 && sizeof(R) == 8)
-        txf_peda_launch<R, Q(), NC() == 2048 ? LTE_TXF_SP : 1>(s, g, enc, enc_words, tx_map, txf_map, txf_re, B,
-                                                              cap_syms, ch, blocks, shm, shm2);
+        txf_peda_launch<R, Q(), NC() == 2048 ? LTE_TXF_SP : 1>(s, g, src, txf_map, txf_re, B, cap_syms, ch,
+                                                              blocks, shm, shm2);
       else
-        hipLaunchKernelGGL((k_ofdm_txf<R, Q(), NC()>), dim3(blocks), dim3(WG), shm, s, g, enc, enc_words, tx_map,
-                           txf_map, txf_re, B, cap_syms, ch);
+        hipLaunchKernelGGL((k_ofdm_txf<R, Q(), NC()>), dim3(blocks), dim3(WG), shm, s, g, src.enc, src.enc_words,
+                           src.tx_map, txf_map, txf_re, B, cap_syms, ch);
     });
   }));
 }
@@ -711,11 +714,11 @@ __global__ __launch_bounds__(WG) void k_fading(int B, int num_rx, int n_paths, c
 
 template <class R>
 int launch_fading(hipStream_t s, int B, int num_rx, int n_paths, const R* gains_dev, const uint64_t* fid,
-                  uint64_t seed, const R* inj_ph, int64_t inj_stride, R* phases, cx<R>* coef) {
+                  uint64_t seed, Inj<R> inj_ph, R* phases, cx<R>* coef) {
   const int n = B * num_rx * n_paths;
   if (n == 0) return 0;
   hipLaunchKernelGGL(k_fading<R>, dim3((n + WG - 1) / WG), dim3(WG), 0, s, B, num_rx, n_paths, gains_dev, fid, seed,
-                     inj_ph, inj_stride, phases, coef);
+                     inj_ph.p, inj_ph.stride, phases, coef);
   return (int)hipGetLastError();
 }
 
@@ -1167,24 +1170,21 @@ __global__ void k_cap_rx(int L, int num_rx, int B, const cx<R>* __restrict__ y, 
 }
 
 template <class R>
-int launch_cap_rx(hipStream_t s, int L, int num_rx, int B, const cx<R>* y, int64_t y_rx_stride, int64_t y_frame_stride,
-                  const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z, int64_t inj_stride, cx<R>* out) {
-  hipLaunchKernelGGL(k_cap_rx<R>, dim3(((L + 255) / 256) * B, num_rx), dim3(256), 0, s, L, num_rx, B, y, y_rx_stride,
-                     y_frame_stride, npow, fid, seed, inj_z, inj_stride, out);
+int launch_cap_rx(hipStream_t s, int L, int B, const RxStreams<R>& rx, cx<R>* out) {
+  hipLaunchKernelGGL(k_cap_rx<R>, dim3(((L + 255) / 256) * B, rx.num_rx), dim3(256), 0, s, L, rx.num_rx, B, rx.y,
+                     rx.rx_stride, rx.frame_stride, rx.npow, rx.fid, rx.seed, rx.inj_z.p, rx.inj_z.stride, out);
   return (int)hipGetLastError();
 }
 
 template <class R>
-int launch_rx_chest(hipStream_t s, const Grid& g, int B, int num_rx, const cx<R>* y, int64_t y_rx_stride,
-                    int64_t y_frame_stride, const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z,
-                    int64_t inj_stride, cx<R>* H, R* pstats) {
+int launch_rx_chest(hipStream_t s, const Grid& g, int B, const RxStreams<R>& rx, cx<R>* H, R* pstats) {
   const int spw = WG / (g.N >> 3);
-  const int64_t total = (int64_t)B * num_rx * g.n_grp;
+  const int64_t total = (int64_t)B * rx.num_rx * g.n_grp;
   const int blocks = (int)((total + spw - 1) / spw);
   const size_t shm = (size_t)spw * (g.N + g.Np) * sizeof(cx<R>);
   with_n<2048>(g.N, [&](auto NC) {
-    hipLaunchKernelGGL((k_rx_chest<R, NC()>), dim3(blocks), dim3(WG), shm, s, g, B, num_rx, y, y_rx_stride,
-                       y_frame_stride, npow, fid, seed, inj_z, inj_stride, H, pstats);
+    hipLaunchKernelGGL((k_rx_chest<R, NC()>), dim3(blocks), dim3(WG), shm, s, g, B, rx.num_rx, rx.y, rx.rx_stride,
+                       rx.frame_stride, rx.npow, rx.fid, rx.seed, rx.inj_z.p, rx.inj_z.stride, H, pstats);
   });
   return (int)hipGetLastError();
 }
@@ -1591,22 +1591,22 @@ bool rx_frame_supported(const Grid& g, int chain, int num_rx, int sc_fdm) {
 }
 
 template <class R>
-int launch_rx_frame(hipStream_t s, const Grid& g, int chain, int rayleigh, int B, const cx<R>* y,
-                    int64_t y_frame_stride, const R* npow, const R* snr_lin, const uint64_t* fid, uint64_t seed,
-                    const R* inj_z, int64_t inj_stride, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                    R* llr, cx<R>* cap_syms, uint8_t* cap_bits, R* nv_out, cx<R>* H, R* pstats) {
-  if (!rx_frame_supported(g, chain, 1, 0) || (nv_out && !chain_traits(chain).zn)) return (int)hipErrorInvalidValue;
+int launch_rx_frame(hipStream_t s, const Grid& g, int chain, int rayleigh, int B, const RxStreams<R>& rx,
+                    const R* snr_lin, const Scored& sc, const SoftOut<R>& soft, const RxCaptures<R>& cap) {
+  if (!rx_frame_supported(g, chain, rx.num_rx, 0) || !soft.ok() || (soft.z && !chain_traits(chain).zn))
+    return (int)hipErrorInvalidValue;
   const int spw = WG / (g.N >> 3);
   const int blocks = (B + spw - 1) / spw;
   const size_t shm = (size_t)spw * (g.N + g.Np) * sizeof(cx<R>);
   return launch_status(with_int<LTE_CHAIN_CODED, LTE_CHAIN_UNCODED>(chain, [&](auto CH) {
     with_bps(g.bps, [&](auto Q) {
       with_n<2048>(g.N, [&](auto NC) {   // 2048: the headline chain
-        with_bool(nv_out != nullptr, [&](auto NV) {
+        with_bool(soft.z != nullptr, [&](auto NV) {
           constexpr bool ZN = chain_traits(CH()).zn && NV();   // the (z, nv) hand-off is the coded chain's
-          hipLaunchKernelGGL((k_rx_frame<R, CH(), Q(), NC(), ZN>), dim3(blocks), dim3(WG), shm, s, g, rayleigh, B, y,
-                             y_frame_stride, npow, snr_lin, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,
-                             llr, cap_syms, cap_bits, nv_out, H, pstats);
+          hipLaunchKernelGGL((k_rx_frame<R, CH(), Q(), NC(), ZN>), dim3(blocks), dim3(WG), shm, s, g, rayleigh, B,
+                             rx.y, rx.frame_stride, rx.npow, snr_lin, rx.fid, rx.seed, rx.inj_z.p, rx.inj_z.stride,
+                             sc.pw, sc.PW, sc.n_bits, sc.frame_err, soft.ptr(), cap.syms, cap.bits, soft.nv, cap.H,
+                             cap.pstats);
         });
       });
     });
@@ -1996,18 +1996,17 @@ bool rx_simo2_ok(const Grid& g, int num_rx, bool H, bool pstats) {
 }
 
 template <class R>
-int launch_rx_frame_simo(hipStream_t s, const Grid& g, int B, int num_rx, const cx<R>* y, int64_t y_rx_stride,
-                         int64_t y_frame_stride, const R* npow, const uint64_t* fid, uint64_t seed, const R* inj_z,
-                         int64_t inj_stride, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                         cx<R>* cap_syms, uint8_t* cap_bits, cx<R>* H, R* pstats, int pairs,
-                         const TxChannelT<R>* xc, const R* snr_lin, R* llr, R* nv_out) {
-  if (!rx_frame_simo_supported(g, num_rx)) return (int)hipErrorInvalidValue;
-  // soft output (llr non-null): (z, nv) with nv_out, else LLRs; the (z, nv) hand-off is 16 / 64-QAM's
-  const int soft = !llr ? RXS_HARD : nv_out ? RXS_SOFT_ZN : RXS_SOFT_LLR;
+int launch_rx_frame_simo(hipStream_t s, const Grid& g, int B, const RxStreams<R>& rx, const Scored& sc,
+                         const RxCaptures<R>& cap, int pairs, const TxChannelT<R>* xc, const R* snr_lin,
+                         const SoftOut<R>& so) {
+  const int num_rx = rx.num_rx;
+  if (!rx_frame_simo_supported(g, num_rx) || !so.ok()) return (int)hipErrorInvalidValue;
+  // soft output: (z, nv), else LLRs; the (z, nv) hand-off is 16 / 64-QAM's
+  const int soft = so.z ? RXS_SOFT_ZN : so.llr ? RXS_SOFT_LLR : RXS_HARD;
   if (soft != RXS_HARD && (!snr_lin || (xc && xc->x_out))) return (int)hipErrorInvalidValue;
-  if ((soft == RXS_SOFT_ZN && g.bps == 2) || (soft == RXS_HARD && nv_out)) return (int)hipErrorInvalidValue;
+  if (soft == RXS_SOFT_ZN && g.bps == 2) return (int)hipErrorInvalidValue;
   if (pairs) {   // k_rx_frame_simo2
-    if (!rx_simo2_ok(g, num_rx, H != nullptr, pstats != nullptr)) return (int)hipErrorInvalidValue;
+    if (!rx_simo2_ok(g, num_rx, cap.H != nullptr, cap.pstats != nullptr)) return (int)hipErrorInvalidValue;
     const bool xin = xc && xc->x_out;
     const size_t shm2 = (2 * (size_t)g.N + RXS_MAXRX * g.Np + (xin ? g.N : 0)) * sizeof(cx<R>);
     const TxChannelT<R> xcv = xin ? *xc : TxChannelT<R>{};
@@ -2017,8 +2016,9 @@ int launch_rx_frame_simo(hipStream_t s, const Grid& g, int B, int num_rx, const 
           // the symbol hand-over is uncoded only (soft with xin: refused above); no QPSK (z, nv) instance
           constexpr int SOFT = XIN() ? RXS_HARD : Q() == 2 && S() == RXS_SOFT_ZN ? RXS_SOFT_LLR : S();
           hipLaunchKernelGGL((k_rx_frame_simo2<R, Q(), 1024, XIN(), SOFT>), dim3(B), dim3(WG), shm2, s, g, B, num_rx,
-                             y, y_rx_stride, y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits,
-                             frame_err, cap_syms, cap_bits, xcv, snr_lin, llr, nv_out);
+                             rx.y, rx.rx_stride, rx.frame_stride, rx.npow, rx.fid, rx.seed, rx.inj_z.p,
+                             rx.inj_z.stride, sc.pw, sc.PW, sc.n_bits, sc.frame_err, cap.syms, cap.bits, xcv, snr_lin,
+                             so.ptr(), so.nv);
         });
       });
     }));
@@ -2031,24 +2031,24 @@ int launch_rx_frame_simo(hipStream_t s, const Grid& g, int B, int num_rx, const 
     with_n<1024>(g.N, [&](auto NC) {   // 1024: config 3 (10 MHz)
       with_int<RXS_HARD, RXS_SOFT_LLR, RXS_SOFT_ZN>(soft, [&](auto S) {
         constexpr int SOFT = Q() == 2 && S() == RXS_SOFT_ZN ? RXS_SOFT_LLR : S();   // no QPSK (z, nv) instance
-        hipLaunchKernelGGL((k_rx_frame_simo<R, Q(), NC(), SOFT>), dim3(blocks), dim3(WG), shm, s, g, B, num_rx, y,
-                           y_rx_stride, y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,
-                           cap_syms, cap_bits, H, pstats, snr_lin, llr, nv_out);
+        hipLaunchKernelGGL((k_rx_frame_simo<R, Q(), NC(), SOFT>), dim3(blocks), dim3(WG), shm, s, g, B, num_rx, rx.y,
+                           rx.rx_stride, rx.frame_stride, rx.npow, rx.fid, rx.seed, rx.inj_z.p, rx.inj_z.stride, sc.pw,
+                           sc.PW, sc.n_bits, sc.frame_err, cap.syms, cap.bits, cap.H, cap.pstats, snr_lin, so.ptr(),
+                           so.nv);
       });
     });
   }));
 }
 
 template <class R>
-int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B, int num_rx, const cx<R>* y,
-                   int64_t y_rx_stride, int64_t y_frame_stride, const cx<R>* H, const R* npow, const R* snr_lin,
-                   const uint64_t* fid, uint64_t seed, const R* inj_z, int64_t inj_stride, const uint32_t* pw, int PW,
-                   int n_bits, uint32_t* frame_err, R* llr, cx<R>* cap_syms, uint8_t* cap_bits, int sc_fdm,
-                   R* nv_out, int eq_zf) {
-  if (g.bps != 2 && g.bps != 4 && g.bps != 6) return (int)hipErrorInvalidValue;
+int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B, const RxStreams<R>& rx,
+                   const cx<R>* H, const R* snr_lin, const Scored& sc, const SoftOut<R>& soft,
+                   const RxCaptures<R>& cap, int sc_fdm, int eq_zf) {
+  const int num_rx = rx.num_rx;
+  if ((g.bps != 2 && g.bps != 4 && g.bps != 6) || !soft.ok()) return (int)hipErrorInvalidValue;
   const ChainTraits& ct = chain_traits(chain);
   if (ct.fde) {   // one nv per OFDM symbol: LLRs only, no (z, nv) hand-off
-    if (nv_out || !llr || !GridT<R>::chirp(g) || !GridT<R>::bhat(g) || 2 * g.Nd > g.N || num_rx < 1 || num_rx > 8)
+    if (soft.z || !soft.llr || !GridT<R>::chirp(g) || !GridT<R>::bhat(g) || 2 * g.Nd > g.N || num_rx < 1 || num_rx > 8)
       return (int)hipErrorInvalidValue;
     const int spw = WG / (g.N >> 3);
     const int64_t total = (int64_t)B * g.n_sym;
@@ -2058,12 +2058,13 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
       with_bool(eq_zf, [&](auto Z) {
         constexpr int CH = LTE_CHAIN_SCFDM_CODED + (Z() ? RX_EQ_ZF : 0);
         hipLaunchKernelGGL((k_rx_data<R, CH, Q(), true>), dim3((int)((total + spw - 1) / spw)), dim3(WG), shm, s, g,
-                           rayleigh, B, num_rx, y, y_rx_stride, y_frame_stride, H, npow, snr_lin, fid, seed, inj_z,
-                           inj_stride, pw, PW, n_bits, frame_err, llr, cap_syms, cap_bits, (R*)nullptr);
+                           rayleigh, B, num_rx, rx.y, rx.rx_stride, rx.frame_stride, H, rx.npow, snr_lin, rx.fid,
+                           rx.seed, rx.inj_z.p, rx.inj_z.stride, sc.pw, sc.PW, sc.n_bits, sc.frame_err, soft.llr,
+                           cap.syms, cap.bits, (R*)nullptr);
       });
     }));
   }
-  if (nv_out && !ct.zn) return (int)hipErrorInvalidValue;
+  if (soft.z && !ct.zn) return (int)hipErrorInvalidValue;
   if (sc_fdm && (ct.deprecode != PRECODE_FLAG || !GridT<R>::chirp(g) || !GridT<R>::bhat(g)))
     return (int)hipErrorInvalidValue;
   if (ct.mrc && num_rx > 8) return (int)hipErrorInvalidValue;
@@ -2080,8 +2081,9 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
           constexpr bool SCF = S() && chain_traits(CH()).deprecode == PRECODE_FLAG;   // SC-FDM is the uncoded chain's
           constexpr int NC = CH() == LTE_CHAIN_CODED ? N() : 0;    // compile-time N: the headline chain
           hipLaunchKernelGGL((k_rx_data<R, CH(), Q(), SCF, NC>), dim3(blocks), dim3(WG), shm, s, g, rayleigh, B,
-                             num_rx, y, y_rx_stride, y_frame_stride, H, npow, snr_lin, fid, seed, inj_z, inj_stride,
-                             pw, PW, n_bits, frame_err, llr, cap_syms, cap_bits, nv_out);
+                             num_rx, rx.y, rx.rx_stride, rx.frame_stride, H, rx.npow, snr_lin, rx.fid, rx.seed,
+                             rx.inj_z.p, rx.inj_z.stride, sc.pw, sc.PW, sc.n_bits, sc.frame_err, soft.ptr(), cap.syms,
+                             cap.bits, soft.nv);
         });
       });
     });
@@ -2090,33 +2092,25 @@ int launch_rx_data(hipStream_t s, const Grid& g, int chain, int rayleigh, int B,
 
 // explicit instances of the precision-templated launchers (lte_capi.hip, lte_stages.hip)
 #define LTE_INST(R)                                                                                                   \
-  template int launch_ofdm_tx<R>(hipStream_t, const Grid&, int, const uint32_t*, int, const uint32_t*, int,          \
-                                 const int32_t*, cx<R>*, int, cx<R>*, int, int);                                    \
-  template int launch_ofdm_tx_ch<R>(hipStream_t, const Grid&, int, const uint32_t*, int, const uint32_t*, int,       \
-                                    const int32_t*, int, cx<R>*, const TxChannelT<R>&, int, int);                   \
+  template int launch_ofdm_tx<R>(hipStream_t, const Grid&, const TxSource&, cx<R>*, int, cx<R>*, int, int);          \
+  template int launch_ofdm_tx_ch<R>(hipStream_t, const Grid&, const TxSource&, int, cx<R>*, const TxChannelT<R>&,    \
+                                    int, int);                                                                        \
   template int launch_chan_fix<R>(hipStream_t, const Grid&, int, const TxChannelT<R>&);                             \
-  template int launch_ofdm_txf<R>(hipStream_t, const Grid&, const uint32_t*, int, const int32_t*, const int32_t*,   \
-                                  const int32_t*, int, cx<R>*, const TxChannelT<R>&);                                \
-  template int launch_fading<R>(hipStream_t, int, int, int, const R*, const uint64_t*, uint64_t, const R*, int64_t, \
-                                R*, cx<R>*);                                                                         \
+  template int launch_ofdm_txf<R>(hipStream_t, const Grid&, const TxSource&, const int32_t*, const int32_t*, int,    \
+                                  cx<R>*, const TxChannelT<R>&);                                                      \
+  template int launch_fading<R>(hipStream_t, int, int, int, const R*, const uint64_t*, uint64_t, Inj<R>, R*, cx<R>*); \
   template int launch_jakes_sets<R>(hipStream_t, int, int, int, int, const R*, const R*, double, double, cx<R>*);     \
   template int launch_channel<R>(hipStream_t, const Grid&, int, int, int, int, const int32_t*, const R*, R, R,       \
                                  const R*, const cx<R>*, const cx<R>*, cx<R>*, R*, int, int);                       \
   template int launch_npow<R>(hipStream_t, int, int, const R*, int, int, const R*, R*);                             \
-  template int launch_cap_rx<R>(hipStream_t, int, int, int, const cx<R>*, int64_t, int64_t, const R*,                \
-                                const uint64_t*, uint64_t, const R*, int64_t, cx<R>*);                               \
-  template int launch_rx_chest<R>(hipStream_t, const Grid&, int, int, const cx<R>*, int64_t, int64_t, const R*,      \
-                                  const uint64_t*, uint64_t, const R*, int64_t, cx<R>*, R*);                        \
-  template int launch_rx_data<R>(hipStream_t, const Grid&, int, int, int, int, const cx<R>*, int64_t, int64_t,       \
-                                 const cx<R>*, const R*, const R*, const uint64_t*, uint64_t, const R*, int64_t,    \
-                                 const uint32_t*, int, int, uint32_t*, R*, cx<R>*, uint8_t*, int, R*, int);         \
-  template int launch_rx_frame_simo<R>(hipStream_t, const Grid&, int, int, const cx<R>*, int64_t, int64_t, const R*,  \
-                                       const uint64_t*, uint64_t, const R*, int64_t, const uint32_t*, int, int,       \
-                                       uint32_t*, cx<R>*, uint8_t*, cx<R>*, R*, int, const TxChannelT<R>*,           \
-                                       const R*, R*, R*);                                                              \
-  template int launch_rx_frame<R>(hipStream_t, const Grid&, int, int, int, const cx<R>*, int64_t, const R*, const R*, \
-                                  const uint64_t*, uint64_t, const R*, int64_t, const uint32_t*, int, int, uint32_t*, \
-                                  R*, cx<R>*, uint8_t*, R*, cx<R>*, R*);
+  template int launch_cap_rx<R>(hipStream_t, int, int, const RxStreams<R>&, cx<R>*);                                 \
+  template int launch_rx_chest<R>(hipStream_t, const Grid&, int, const RxStreams<R>&, cx<R>*, R*);                   \
+  template int launch_rx_data<R>(hipStream_t, const Grid&, int, int, int, const RxStreams<R>&, const cx<R>*,         \
+                                 const R*, const Scored&, const SoftOut<R>&, const RxCaptures<R>&, int, int);        \
+  template int launch_rx_frame_simo<R>(hipStream_t, const Grid&, int, const RxStreams<R>&, const Scored&,            \
+                                       const RxCaptures<R>&, int, const TxChannelT<R>*, const R*, const SoftOut<R>&); \
+  template int launch_rx_frame<R>(hipStream_t, const Grid&, int, int, int, const RxStreams<R>&, const R*,            \
+                                  const Scored&, const SoftOut<R>&, const RxCaptures<R>&);
 LTE_INST(float)
 LTE_INST(double)
 #undef LTE_INST

@@ -533,9 +533,9 @@ bool txch_flat_pr_supported(const Grid& g, const MimoGrid& m) {
 }
 
 template <class R>
-int launch_ofdm_txch_flat(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, const uint32_t* pw, int PW,
-                          const uint32_t* enc, int enc_words, const int32_t* tx_map, const cx<R>* coef, cx<R>* y,
-                          R* pow_part, int nblk, int B, FlatTx variant) {
+int launch_ofdm_txch_flat(hipStream_t s, const Grid& g, const MimoGrid& m, const TxSource& src, const cx<R>* coef,
+                          cx<R>* y, R* pow_part, int nblk, int B, FlatTx variant) {
+  const int coded = src.coded, enc_words = src.enc_words;
   const int spw = MWG / (g.N >> 3);
   const bool pr = variant == FLAT_PR;
   if (pr && !txch_flat_pr_supported(g, m)) return (int)hipErrorInvalidValue;
@@ -552,8 +552,8 @@ int launch_ofdm_txch_flat(hipStream_t s, const Grid& g, const MimoGrid& m, int c
       const size_t wshm = (size_t)TXMW_WAVES * TXMW_LDS * sizeof(double);
       return launch_status(with_bps(g.bps, [&](auto Q) {
         with_bool(coded, [&](auto C) {
-          hipLaunchKernelGGL((k_ofdm_txch_flat_w<C(), Q()>), dim3(wb), dim3(64 * TXMW_WAVES), wshm, s, g, m, pw, PW,
-                             enc, enc_words, tx_map, reinterpret_cast<const double2*>(coef),
+          hipLaunchKernelGGL((k_ofdm_txch_flat_w<C(), Q()>), dim3(wb), dim3(64 * TXMW_WAVES), wshm, s, g, m, src.pw,
+                             src.PW, src.enc, src.enc_words, src.tx_map, reinterpret_cast<const double2*>(coef),
                              reinterpret_cast<double2*>(y), reinterpret_cast<double*>(pow_part), nblk, B);
         });
       }));
@@ -571,7 +571,8 @@ int launch_ofdm_txch_flat(hipStream_t s, const Grid& g, const MimoGrid& m, int c
           with_bool(pr, [&](auto P) {
             constexpr bool PR = P() && NC() == 2048;   // the per-RX slots are N = 2048's (checked above)
             hipLaunchKernelGGL((k_ofdm_txch_flat<R, M(), C(), Q(), NC(), PR>), dim3(blocks), dim3(MWG), shm, s, g, m,
-                               pw, PW, enc, enc_words, tx_map, coef, y, pow_part, nblk, B, stage_enc);
+                               src.pw, src.PW, src.enc, src.enc_words, src.tx_map, coef, y, pow_part, nblk, B,
+                               stage_enc);
           });
         });
       });
@@ -614,9 +615,9 @@ bool tx_mimo_frame_supported(const Grid& g, int coded, int enc_words) {
 }
 
 template <class R>
-int launch_ofdm_tx_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, const uint32_t* pw, int PW,
-                        const uint32_t* enc, int enc_words, const int32_t* tx_map, cx<R>* x, int B,
+int launch_ofdm_tx_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, const TxSource& src, cx<R>* x, int B,
                         const TxLinkPower<R>& lp, int per_frame) {
+  const int coded = src.coded, enc_words = src.enc_words;
   const int spw = MWG / (g.N >> 3);
   const int64_t total = (int64_t)B * g.n_sym * m.num_tx;
   if (total > 0x7FFFFFFF - spw || (g.bps != 2 && g.bps != 4 && g.bps != 6)) return (int)hipErrorInvalidValue;
@@ -636,7 +637,7 @@ int launch_ofdm_tx_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int cod
           with_bool(pf, [&](auto P) {
             constexpr bool PF = P() && NC() == 2048;   // one slot per frame is N = 2048's (checked above)
             hipLaunchKernelGGL((k_ofdm_tx_mimo<R, M(), C(), Q(), NC(), PF>), dim3(blocks), dim3(MWG), shm, s, g, m,
-                               pw, PW, enc, enc_words, tx_map, x, B, stage_enc, lp);
+                               src.pw, src.PW, src.enc, src.enc_words, src.tx_map, x, B, stage_enc, lp);
           });
         });
       });
@@ -752,14 +753,14 @@ __global__ __launch_bounds__(MWG) void k_fading_mimo(int B, int num_rx, int num_
 
 template <class R>
 int launch_fading_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, int rayleigh, int n_paths,
-                       const R* gains, double fD, double fs, const uint64_t* fid, uint64_t seed, const R* inj_ph,
-                       int64_t inj_ph_stride, const R* inj_h, int64_t inj_h_stride, cx<R>* coef, R* phases) {
+                       const R* gains, double fD, double fs, const uint64_t* fid, uint64_t seed, Inj<R> inj_ph,
+                       Inj<R> inj_h, cx<R>* coef, R* phases) {
   const int np = rayleigh ? n_paths : 1;
   const int n = B * m.num_rx * m.num_tx * np;
   if (rayleigh && m.exact_jakes && !phases) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(k_fading_mimo<R>, dim3((n + MWG - 1) / MWG), dim3(MWG), 0, s, B, m.num_rx, m.num_tx, np, m.n_cs,
-                     m.mode, rayleigh, gains, fD, fs, g.N + g.cp, fid, seed, inj_ph, inj_ph_stride, inj_h,
-                     inj_h_stride, coef, (rayleigh && m.exact_jakes) ? phases : nullptr);
+                     m.mode, rayleigh, gains, fD, fs, g.N + g.cp, fid, seed, inj_ph.p, inj_ph.stride, inj_h.p,
+                     inj_h.stride, coef, (rayleigh && m.exact_jakes) ? phases : nullptr);
   return (int)hipGetLastError();
 }
 
@@ -1322,9 +1323,9 @@ bool sfbc_txch_supported(const Grid& g, const MimoGrid& m, int n_paths, int max_
 #define LTE_SFX_TPB 512
 #endif
 template <class R>
-int launch_ofdm_txch_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, const uint32_t* pw, int PW,
-                          const uint32_t* enc, int enc_words, const int32_t* tx_map, const TxLinkPower<R>& lp,
-                          cx<R>* y, int B) {
+int launch_ofdm_txch_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, const TxSource& src,
+                          const TxLinkPower<R>& lp, cx<R>* y, int B) {
+  const int coded = src.coded, enc_words = src.enc_words;
   if (!sfbc_txch_supported<R>(g, m, lp.n_paths, lp.max_delay) || !lp.part) return (int)hipErrorInvalidValue;
   const size_t enc_shm = (size_t)enc_words * sizeof(uint32_t);
   const int stage_enc = coded && enc_shm <= 32768;
@@ -1338,8 +1339,8 @@ int launch_ofdm_txch_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int c
             constexpr int TPB = NP() == 4 ? LTE_SFX_TPB : MWG;
             auto k = k_ofdm_txch_sfbc<R, C(), Q(), NR(), NP(), TPB, 2048, MRG()>;
             (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-            hipLaunchKernelGGL(k, dim3(B), dim3(TPB), shm, s, g, m, pw, PW, enc, enc_words, tx_map, lp, y, B,
-                               stage_enc);
+            hipLaunchKernelGGL(k, dim3(B), dim3(TPB), shm, s, g, m, src.pw, src.PW, src.enc, src.enc_words,
+                               src.tx_map, lp, y, B, stage_enc);
           });
         });
       });
@@ -1349,8 +1350,8 @@ int launch_ofdm_txch_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int c
 
 template <class R>
 int launch_link_noise_add(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const R* link_part, R* link_sigma,
-                          cx<R>* y, const uint64_t* fid, uint64_t seed, R* pow_part, int* pow_nblk) {
-  if (m.num_rx < 1 || m.num_rx > 2) return (int)hipErrorInvalidValue;
+                          cx<R>* y, const LinkNoise<R>& ln, R* pow_part, int* pow_nblk) {
+  if (m.num_rx < 1 || m.num_rx > 2 || ln.inj_lz.p) return (int)hipErrorInvalidValue;
   const int nl = B * m.num_rx * m.num_tx;   // one partial per link (k_ofdm_txch_sfbc)
   hipLaunchKernelGGL(k_link_sigma<R>, dim3((nl + 255) / 256), dim3(256), 0, s, nl, link_part, 1, g.L, link_sigma);
   *pow_nblk = 1;
@@ -1358,7 +1359,7 @@ int launch_link_noise_add(hipStream_t s, const Grid& g, const MimoGrid& m, int B
 #define LTE_LN_U 8
 #endif
   hipLaunchKernelGGL((k_link_noise_pairs<R, LTE_LN_U, LTE_BM_LDS != 0>), dim3(B * m.num_rx), dim3(MWG), 0, s, g.L, m.num_rx,
-                     m.num_tx, y, link_sigma, fid, seed, pow_part);
+                     m.num_tx, y, link_sigma, ln.fid, ln.seed, pow_part);
   return (int)hipGetLastError();
 }
 
@@ -1665,11 +1666,11 @@ template ChanMimoSel channel_mimo_select<float>(const MimoGrid&, int, int, doubl
 template ChanMimoSel channel_mimo_select<double>(const MimoGrid&, int, int, double, const Knobs&);
 
 template <class R>
-static int launch_channel_tay(hipStream_t s, int B, int nch, int L, const MimoGrid& m, int np, int sym_len,
-                              double fs, const int32_t* delays, const cx<R>* coef, const cx<R>* x, cx<R>* y,
-                              const R* link_sigma, const uint64_t* fid, uint64_t seed, const R* inj_lz,
-                              int64_t inj_lz_stride, R* pow_part, const ChanMimoSel& sel) {
-  const int J = sel.J, G = sel.G;
+static int launch_channel_tay(hipStream_t s, int B, int nch, int L, const MimoGrid& m, const LinkTaps<R>& taps,
+                              int sym_len, const cx<R>* x, cx<R>* y, const R* link_sigma, const LinkNoise<R>& ln,
+                              R* pow_part, const ChanMimoSel& sel) {
+  const int J = sel.J, G = sel.G, np = taps.n_paths;
+  const double fs = taps.fs;
   const bool tay = m.n_cs > 1;
   const size_t shm = channel_tay_lds<R>(m, np);
   if (m.exact_jakes || shm > 32768 || J < 1 || J > 3 || G < 1 || G > 4 || m.num_rx % G != 0 ||
@@ -1683,8 +1684,9 @@ static int launch_channel_tay(hipStream_t s, int B, int nch, int L, const MimoGr
             // the economised degree-4 sets (f64 Taylor path, J = 3; checked above)
             constexpr bool E = EC() && sizeof(R) == 8 && T() && JC() == 3;
             hipLaunchKernelGGL((k_channel_tay<R, JC(), GC(), T(), LN(), E>), dim3(nch * B), dim3(MWG), shm, s, L,
-                               m.num_rx, m.num_tx, np, m.n_cs, sym_len, delays, coef, x, y, link_sigma, fid, seed,
-                               LN() ? inj_lz : nullptr, LN() ? inj_lz_stride : 0, pow_part, nch);
+                               m.num_rx, m.num_tx, np, m.n_cs, sym_len, taps.delays, taps.coef, x, y, link_sigma,
+                               ln.fid, ln.seed, LN() ? ln.inj_lz.p : nullptr, LN() ? ln.inj_lz.stride : 0, pow_part,
+                               nch);
           });
         });
       });
@@ -1694,17 +1696,15 @@ static int launch_channel_tay(hipStream_t s, int B, int nch, int L, const MimoGr
 }
 
 template <class R>
-int launch_channel_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, int n_paths, const int32_t* delays,
-                        const cx<R>* coef, const R* phases, const R* gains, double fs, const cx<R>* x, cx<R>* y,
-                        int link_noise, const uint64_t* fid, uint64_t seed, const R* inj_lz, int64_t inj_lz_stride,
-                        R* link_part, R* link_sigma, R* pow_part, int nblk, const ChanMimoSel& sel,
-                        int link_part_done) {
+int launch_channel_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const LinkTaps<R>& taps,
+                        const cx<R>* x, cx<R>* y, int link_noise, const LinkNoise<R>& ln, R* link_part, R* link_sigma,
+                        R* pow_part, int nblk, const ChanMimoSel& sel, int link_part_done) {
   const int sym_len = g.N + g.cp;
   if (m.num_rx > MC_MAXRX) return (int)hipErrorInvalidValue;
   const int nch = mimo_channel_nblk(g.L, sym_len);
   if (nch > nblk) return (int)hipErrorInvalidValue;   // partial buffers are sized for nblk blocks
-  const R* ph = m.exact_jakes ? phases : nullptr;
-  if (m.exact_jakes && (!phases || !gains)) return (int)hipErrorInvalidValue;
+  const R* ph = m.exact_jakes ? taps.phases : nullptr;
+  if (m.exact_jakes && (!taps.phases || !taps.gains)) return (int)hipErrorInvalidValue;
   // samples per thread per pass: the smallest instantiated J covering one
   // symbol, at most 2 (f64) / 3 (f32) -- larger symbols loop.  The RX-group
   // accumulators take 4 MC_RXG J VGPRs per component pair (f64: v and the
@@ -1725,22 +1725,21 @@ int launch_channel_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, 
         if (link_noise) {
           if (!link_part_done)   // else k_ofdm_tx_mimo + k_link_power_fix wrote the partials
             hipLaunchKernelGGL((k_link_power<R, JC(), EX(), GC()>), dim3(nch * B, m.num_tx), dim3(MWG), 0, s, g.L,
-                               m.num_rx, m.num_tx, n_paths, m.n_cs, sym_len, delays, coef, ph, gains, fs, m, x,
-                               link_part, nch);
+                               m.num_rx, m.num_tx, taps.n_paths, m.n_cs, sym_len, taps.delays, taps.coef, ph,
+                               taps.gains, taps.fs, m, x, link_part, nch);
           const int nl = B * m.num_rx * m.num_tx;
           hipLaunchKernelGGL(k_link_sigma<R>, dim3((nl + 255) / 256), dim3(256), 0, s, nl, link_part, nch, g.L,
                              link_sigma);
         }
         if (!sel.tay)
           hipLaunchKernelGGL((k_channel_mimo<R, JC(), EX(), GC()>), dim3(nch * B), dim3(MWG), 0, s, g.L, m.num_rx,
-                             m.num_tx, n_paths, m.n_cs, sym_len, delays, coef, ph, gains, fs, m, x, y, sigma, fid,
-                             seed, inj_lz, inj_lz_stride, pow_part, nch);
+                             m.num_tx, taps.n_paths, m.n_cs, sym_len, taps.delays, taps.coef, ph, taps.gains, taps.fs,
+                             m, x, y, sigma, ln.fid, ln.seed, ln.inj_lz.p, ln.inj_lz.stride, pow_part, nch);
       });
     });
   });
   if (sel.tay) {
-    const int e = launch_channel_tay<R>(s, B, nch, g.L, m, n_paths, sym_len, fs, delays, coef, x, y, sigma, fid, seed,
-                                        inj_lz, inj_lz_stride, pow_part, sel);
+    const int e = launch_channel_tay<R>(s, B, nch, g.L, m, taps, sym_len, x, y, sigma, ln, pow_part, sel);
     if (e) return e;
   }
   return (int)hipGetLastError();
@@ -1800,16 +1799,15 @@ __global__ void k_link_stats_fin(int n, const R* __restrict__ part, int nblk, in
 }
 
 template <class R>
-int launch_link_stats(hipStream_t s, const Grid& g, const MimoGrid& m, int B, int n_paths, const int32_t* delays,
-                      const cx<R>* coef, const R* phases, const R* gains, double fs, const cx<R>* x,
-                      const R* link_sigma, const uint64_t* fid, uint64_t seed, const R* inj_lz, int64_t inj_lz_stride,
-                      R* part, int nblk, R* stats) {
+int launch_link_stats(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const LinkTaps<R>& taps,
+                      const cx<R>* x, const R* link_sigma, const LinkNoise<R>& ln, R* part, int nblk, R* stats) {
   if (nblk < (g.L + MWG - 1) / MWG) return (int)hipErrorInvalidValue;
-  if (m.exact_jakes && !phases) return (int)hipErrorInvalidValue;
+  if (m.exact_jakes && !taps.phases) return (int)hipErrorInvalidValue;
   with_bool(m.exact_jakes, [&](auto EX) {
     hipLaunchKernelGGL((k_link_stats_part<R, EX()>), dim3(nblk * B, m.num_rx * m.num_tx), dim3(MWG), 0, s, g.L,
-                       m.num_rx, m.num_tx, n_paths, m.n_cs, g.N + g.cp, delays, coef, phases, gains, fs, m, x,
-                       link_sigma, fid, seed, inj_lz, inj_lz_stride, part, nblk);
+                       m.num_rx, m.num_tx, taps.n_paths, m.n_cs, g.N + g.cp, taps.delays, taps.coef, taps.phases,
+                       taps.gains, taps.fs, m, x, link_sigma, ln.fid, ln.seed, ln.inj_lz.p, ln.inj_lz.stride, part,
+                       nblk);
   });
   const int n = B * m.num_rx * m.num_tx * 4;
   hipLaunchKernelGGL(k_link_stats_fin<R>, dim3((n + 255) / 256), dim3(256), 0, s, n, part, nblk, g.L, stats);
@@ -1931,9 +1929,8 @@ __global__ __launch_bounds__(MWG) void k_rx_fft_mimo(Grid g, MimoGrid m, int B, 
 }
 
 template <class R>
-int launch_rx_fft_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const cx<R>* y, const R* npow,
-                       const uint64_t* fid, uint64_t seed, const R* inj_z, int64_t inj_stride, cx<R>* Y, cx<R>* H,
-                       int h_pilots) {
+int launch_rx_fft_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const RxStreams<R>& rx, cx<R>* Y,
+                       cx<R>* H, int h_pilots) {
   const int spw = MWG / (g.N >> 3);
   const int64_t total = (int64_t)B * m.num_rx;
   if (total > 0x7FFFFFFF - spw) return (int)hipErrorInvalidValue;
@@ -1941,8 +1938,8 @@ int launch_rx_fft_mimo(hipStream_t s, const Grid& g, const MimoGrid& m, int B, c
   const size_t shm = spw * (g.N + m.num_tx * m.maxP) * sizeof(cx<R>);
   with_bool(h_pilots, [&](auto HP) {
     with_n<2048>(g.N, [&](auto NC) {   // 20 MHz: compile-time N (unrolled passes, twiddle recurrence)
-      hipLaunchKernelGGL((k_rx_fft_mimo<R, NC(), HP()>), dim3(blocks), dim3(MWG), shm, s, g, m, B, y, npow, fid, seed,
-                         inj_z, inj_stride, Y, H);
+      hipLaunchKernelGGL((k_rx_fft_mimo<R, NC(), HP()>), dim3(blocks), dim3(MWG), shm, s, g, m, B, rx.y, rx.npow,
+                         rx.fid, rx.seed, rx.inj_z.p, rx.inj_z.stride, Y, H);
     });
   });
   return (int)hipGetLastError();
@@ -2070,16 +2067,16 @@ __global__ __launch_bounds__(MWG) void k_det_sfbc(Grid g, MimoGrid m, int B, con
 
 template <class R>
 int launch_det_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, int rayleigh, int B, const cx<R>* Y,
-                    const cx<R>* H, const R* snr_lin, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                    R* llr, cx<R>* cap_syms, uint8_t* cap_bits, cx<R>* zo, R* nvo) {
+                    const cx<R>* H, const R* snr_lin, const Scored& sc, const SoftOut<R>& soft,
+                    const RxCaptures<R>& cap) {
   (void)rayleigh;
-  if (zo && (!coded || !nvo || (m.res & 1) || m.n_dsc > m.res)) return (int)hipErrorInvalidValue;
+  if (!soft.ok() || (soft.z && (!coded || (m.res & 1) || m.n_dsc > m.res))) return (int)hipErrorInvalidValue;
   const int64_t n = (int64_t)B * g.n_sym * (m.n_dsc >> 1);
   const dim3 grid((unsigned)((n + MWG - 1) / MWG));
   with_int_or<6, 2, 4>(g.bps, [&](auto Q) {
     with_bool(coded, [&](auto C) {
-      hipLaunchKernelGGL((k_det_sfbc<R, C(), Q()>), grid, dim3(MWG), 0, s, g, m, B, Y, H, snr_lin, pw, PW, n_bits,
-                         frame_err, llr, cap_syms, cap_bits, zo, nvo);
+      hipLaunchKernelGGL((k_det_sfbc<R, C(), Q()>), grid, dim3(MWG), 0, s, g, m, B, Y, H, snr_lin, sc.pw, sc.PW,
+                         sc.n_bits, sc.frame_err, soft.llr, cap.syms, cap.bits, soft.z, soft.nv);
     });
   });
   return (int)hipGetLastError();
@@ -2201,15 +2198,14 @@ bool rx_sfbc_supported(const Grid& g, const MimoGrid& m) {
 }
 
 template <class R>
-int launch_rx_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, int B, const cx<R>* y, const R* npow,
-                   const uint64_t* fid, uint64_t seed, const R* snr_lin, const uint32_t* pw, int PW, int n_bits,
-                   uint32_t* frame_err, cx<R>* zo, R* nvo) {
-  if (!rx_sfbc_supported<R>(g, m) || (coded && (!zo || !nvo))) return (int)hipErrorInvalidValue;
+int launch_rx_sfbc(hipStream_t s, const Grid& g, const MimoGrid& m, int coded, int B, const RxStreams<R>& rx,
+                   const R* snr_lin, const Scored& sc, const SoftOut<R>& soft) {
+  if (!rx_sfbc_supported<R>(g, m) || rx.inj_z.p || !soft.ok() || (coded && !soft.z)) return (int)hipErrorInvalidValue;
   const size_t shm = ((size_t)g.N + (size_t)m.num_rx * m.num_tx * m.maxP) * sizeof(cx<R>);
   return launch_status(with_bps(g.bps, [&](auto Q) {
     with_bool(coded, [&](auto C) {
-      hipLaunchKernelGGL((k_rx_sfbc<R, C(), Q()>), dim3(B), dim3(MWG), shm, s, g, m, B, y, npow, fid, seed, snr_lin,
-                         pw, PW, n_bits, frame_err, zo, nvo);
+      hipLaunchKernelGGL((k_rx_sfbc<R, C(), Q()>), dim3(B), dim3(MWG), shm, s, g, m, B, rx.y, rx.npow, rx.fid, rx.seed,
+                         snr_lin, sc.pw, sc.PW, sc.n_bits, sc.frame_err, soft.z, soft.nv);
     });
   }));
 }
@@ -2616,8 +2612,10 @@ bool det_spatial_stage_supported(const MimoGrid& m, int f64, int n_sym, int B, i
 
 template <class R>
 int launch_det_spatial(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const cx<R>* Y, const cx<R>* H,
-                       const double* nvar, const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err,
-                       cx<R>* cap_syms, uint8_t* cap_bits, int h_pilots, int stage, R* llr) {
+                       const double* nvar, const Scored& sc, const SoftOut<R>& soft, const RxCaptures<R>& cap,
+                       int h_pilots, int stage) {
+  R* const llr = soft.llr;
+  if (soft.z || soft.nv) return (int)hipErrorInvalidValue;   // LLRs only
   if (m.num_tx < 1 || m.num_tx > DMAX || m.num_rx < 1 || m.num_rx > DMAX || m.rank < 1 || m.rank > m.num_rx ||
       m.rank > m.num_tx || !m.W)
     return (int)hipErrorInvalidValue;
@@ -2636,8 +2634,8 @@ int launch_det_spatial(hipStream_t s, const Grid& g, const MimoGrid& m, int B, c
         with_bool(h_pilots, [&](auto P) {
           constexpr bool HP = P() || STG();   // the staged estimates are the pilots' (checked above)
           hipLaunchKernelGGL((k_det_spatial<R, Q(), K() == 1, HP, STG(), K() == 2>), STG() ? sgrid : grid, dim3(MWG),
-                             STG() ? hshm : 0, s, g, m, B, Y, H, nvar, pw, PW, n_bits, frame_err, cap_syms, cap_bits,
-                             llr);
+                             STG() ? hshm : 0, s, g, m, B, Y, H, nvar, sc.pw, sc.PW, sc.n_bits, sc.frame_err, cap.syms,
+                             cap.bits, llr);
         });
       });
     });
@@ -2729,38 +2727,34 @@ int launch_det_stage(hipStream_t s, int det, int NR, int NT, int R, int bps, int
 
 // explicit instances: float (fast mode) and double (the reference's precision)
 #define LTE_MIMO_INST(R)                                                                                           \
-  template int launch_ofdm_txch_sfbc<R>(hipStream_t, const Grid&, const MimoGrid&, int, const uint32_t*, int,     \
-                                        const uint32_t*, int, const int32_t*, const TxLinkPower<R>&, cx<R>*, int); \
+  template int launch_ofdm_txch_sfbc<R>(hipStream_t, const Grid&, const MimoGrid&, const TxSource&,                \
+                                        const TxLinkPower<R>&, cx<R>*, int);                                       \
   template int launch_npow_sfbc_merged<R>(hipStream_t, int, int, int, const R*, int, const R*, R*);             \
   template int launch_link_noise_add<R>(hipStream_t, const Grid&, const MimoGrid&, int, const R*, R*, cx<R>*,      \
-                                        const uint64_t*, uint64_t, R*, int*);                                      \
+                                        const LinkNoise<R>&, R*, int*);                                            \
   template bool sfbc_txch_supported<R>(const Grid&, const MimoGrid&, int, int);                                   \
-  template int launch_ofdm_tx_mimo<R>(hipStream_t, const Grid&, const MimoGrid&, int, const uint32_t*, int,       \
-                                      const uint32_t*, int, const int32_t*, cx<R>*, int, const TxLinkPower<R>&, int); \
-  template int launch_ofdm_txch_flat<R>(hipStream_t, const Grid&, const MimoGrid&, int, const uint32_t*, int,     \
-                                        const uint32_t*, int, const int32_t*, const cx<R>*, cx<R>*, R*, int, int, FlatTx); \
+  template int launch_ofdm_tx_mimo<R>(hipStream_t, const Grid&, const MimoGrid&, const TxSource&, cx<R>*, int,     \
+                                      const TxLinkPower<R>&, int);                                                 \
+  template int launch_ofdm_txch_flat<R>(hipStream_t, const Grid&, const MimoGrid&, const TxSource&, const cx<R>*,  \
+                                        cx<R>*, R*, int, int, FlatTx);                                             \
   template int launch_fading_mimo<R>(hipStream_t, const Grid&, const MimoGrid&, int, int, int, const R*, double,   \
-                                     double, const uint64_t*, uint64_t, const R*, int64_t, const R*, int64_t,      \
-                                     cx<R>*, R*);                                                                  \
-  template int launch_channel_mimo<R>(hipStream_t, const Grid&, const MimoGrid&, int, int, const int32_t*,         \
-                                      const cx<R>*, const R*, const R*, double, const cx<R>*, cx<R>*, int,         \
-                                      const uint64_t*, uint64_t, const R*, int64_t, R*, R*, R*, int, const ChanMimoSel&, int); \
-  template int launch_link_stats<R>(hipStream_t, const Grid&, const MimoGrid&, int, int, const int32_t*,           \
-                                    const cx<R>*, const R*, const R*, double, const cx<R>*, const R*,              \
-                                    const uint64_t*, uint64_t, const R*, int64_t, R*, int, R*);                    \
+                                     double, const uint64_t*, uint64_t, Inj<R>, Inj<R>, cx<R>*, R*);               \
+  template int launch_channel_mimo<R>(hipStream_t, const Grid&, const MimoGrid&, int, const LinkTaps<R>&,          \
+                                      const cx<R>*, cx<R>*, int, const LinkNoise<R>&, R*, R*, R*, int,             \
+                                      const ChanMimoSel&, int);                                                    \
+  template int launch_link_stats<R>(hipStream_t, const Grid&, const MimoGrid&, int, const LinkTaps<R>&,            \
+                                    const cx<R>*, const R*, const LinkNoise<R>&, R*, int, R*);                     \
   template int launch_npow_mimo<R>(hipStream_t, int, int, const R*, int, int, const R*, double, R*);               \
-  template int launch_rx_fft_mimo<R>(hipStream_t, const Grid&, const MimoGrid&, int, const cx<R>*, const R*,       \
-                                     const uint64_t*, uint64_t, const R*, int64_t, cx<R>*, cx<R>*, int);                \
+  template int launch_rx_fft_mimo<R>(hipStream_t, const Grid&, const MimoGrid&, int, const RxStreams<R>&, cx<R>*,  \
+                                     cx<R>*, int);                                                                 \
   template bool rx_sfbc_supported<R>(const Grid&, const MimoGrid&);                                                \
-  template int launch_rx_sfbc<R>(hipStream_t, const Grid&, const MimoGrid&, int, int, const cx<R>*, const R*,      \
-                                 const uint64_t*, uint64_t, const R*, const uint32_t*, int, int, uint32_t*, cx<R>*,  \
-                                 R*);                                                                              \
+  template int launch_rx_sfbc<R>(hipStream_t, const Grid&, const MimoGrid&, int, int, const RxStreams<R>&,         \
+                                 const R*, const Scored&, const SoftOut<R>&);                                      \
   template int launch_det_sfbc<R>(hipStream_t, const Grid&, const MimoGrid&, int, int, int, const cx<R>*,          \
-                                  const cx<R>*, const R*, const uint32_t*, int, int, uint32_t*, R*, cx<R>*,        \
-                                  uint8_t*, cx<R>*, R*);                                                           \
+                                  const cx<R>*, const R*, const Scored&, const SoftOut<R>&, const RxCaptures<R>&); \
   template int launch_det_spatial<R>(hipStream_t, const Grid&, const MimoGrid&, int, const cx<R>*, const cx<R>*,   \
-                                     const double*, const uint32_t*, int, int, uint32_t*, cx<R>*, uint8_t*, int, int, \
-                                     R*);
+                                     const double*, const Scored&, const SoftOut<R>&, const RxCaptures<R>&, int,   \
+                                     int);
 LTE_MIMO_INST(float)
 LTE_MIMO_INST(double)
 #undef LTE_MIMO_INST

@@ -88,8 +88,8 @@ static int channel_host(int64_t L, int num_rx, int channel, int n_paths, const i
       std::vector<R> hp(phases, phases + (size_t)num_rx * n_paths * 16);
       ok = upload(dinj, hp) == 0;
     }
-    ok = ok && launch_fading<R>(nullptr, 1, num_rx, n_paths, dgain.p, dfid.p, seed, phases ? dinj.p : nullptr, 0,
-                                dph.p, dcoef.p) == 0;
+    ok = ok && launch_fading<R>(nullptr, 1, num_rx, n_paths, dgain.p, dfid.p, seed,
+                                Inj<R>{phases ? dinj.p : nullptr, 0}, dph.p, dcoef.p) == 0;
   }
   if (ok && noise) {
     std::vector<R> hz(noise, noise + (size_t)num_rx * 2 * L);
@@ -99,9 +99,10 @@ static int channel_host(int64_t L, int num_rx, int channel, int n_paths, const i
                                dcoef.p, dx.p, dy.p, dpp.p, nblk, ray ? *std::max_element(delays, delays + n_paths) : 0) == 0;
   ok = ok && launch_npow<R>(nullptr, 1, num_rx, dpp.p, nblk, (int)L, dsl.p, dnp.p) == 0;
   if (ok) {
-    const V* ys = ray ? dy.p : dx.p;
-    ok = launch_cap_rx<R>(nullptr, (int)L, num_rx, 1, ys, ray ? L : 0, ray ? (int64_t)num_rx * L : L, dnp.p, dfid.p,
-                          seed, noise ? dz.p : nullptr, 0, dout.p) == 0 &&
+    const RxStreams<R> rxs{.num_rx = num_rx, .y = ray ? dy.p : dx.p, .rx_stride = ray ? L : 0,
+                           .frame_stride = ray ? (int64_t)num_rx * L : L, .npow = dnp.p, .fid = dfid.p, .seed = seed,
+                           .inj_z = {noise ? dz.p : nullptr, 0}};
+    ok = launch_cap_rx<R>(nullptr, (int)L, 1, rxs, dout.p) == 0 &&
          hipDeviceSynchronize() == hipSuccess &&
          hipMemcpy(y, dout.p, (size_t)num_rx * L * sizeof(V), hipMemcpyDeviceToHost) == hipSuccess &&
          (!noise_power || hipMemcpy(noise_power, dnp.p, num_rx * sizeof(R), hipMemcpyDeviceToHost) == hipSuccess);
@@ -188,20 +189,21 @@ static int channel_mimo_host(int64_t L, int num_tx, int num_rx, int mode, int ch
   if (ok && !ray && mode == 1 && link_h) ok = up(dlh, link_h, links * 2);
   if (ok && noise) ok = up(dz, noise, (size_t)num_rx * 2 * L);
   ok = ok && launch_fading_mimo<R>(nullptr, g, m, 1, ray ? 1 : 0, n_paths, dgain.p, fD, fs, dfid.p, seed,
-                                   (ray && phases) ? dph.p : nullptr, 0,
-                                   (!ray && mode == 1 && link_h) ? dlh.p : nullptr, 0, dcoef.p, dphs.p) == 0;
-  const R* lz = (link_noise_on && link_noise) ? dlz.p : nullptr;
-  ok = ok && launch_channel_mimo<R>(nullptr, g, m, 1, np, ray ? ddel.p : nullptr, dcoef.p, dphs.p, dgain.p, fs, dx.p,
-                                    dy.p, link_noise_on ? 1 : 0, dfid.p, seed, lz, 0, dlp.p, dls.p, dpp.p, nblk,
-                                    channel_mimo_select<R>(m, np, g.N + g.cp, fs, read_knobs()), 0) == 0;
+                                   Inj<R>{(ray && phases) ? dph.p : nullptr, 0},
+                                   Inj<R>{(!ray && mode == 1 && link_h) ? dlh.p : nullptr, 0}, dcoef.p, dphs.p) == 0;
+  const LinkTaps<R> taps{np, ray ? ddel.p : nullptr, dcoef.p, dphs.p, dgain.p, fs};
+  const LinkNoise<R> ln{dfid.p, seed, {(link_noise_on && link_noise) ? dlz.p : nullptr, 0}};
+  const RxStreams<R> rxs{.num_rx = num_rx, .y = dy.p, .rx_stride = (int64_t)L, .frame_stride = (int64_t)num_rx * L,
+                         .npow = dnp.p, .fid = dfid.p, .seed = seed, .inj_z = {noise ? dz.p : nullptr, 0}};
+  ok = ok && launch_channel_mimo<R>(nullptr, g, m, 1, taps, dx.p, dy.p, link_noise_on ? 1 : 0, ln, dlp.p, dls.p, dpp.p,
+                                    nblk, channel_mimo_select<R>(m, np, g.N + g.cp, fs, read_knobs()), 0) == 0;
   ok = ok && launch_npow_mimo<R>(nullptr, 1, num_rx, dpp.p, mimo_channel_nblk(g.L, g.N + g.cp), (int)L, dsl.p,
                                  mode == 0 ? (double)num_tx : 1.0, dnp.p) == 0;
-  ok = ok && launch_cap_rx<R>(nullptr, (int)L, num_rx, 1, dy.p, (int64_t)L, (int64_t)num_rx * L, dnp.p, dfid.p, seed,
-                              noise ? dz.p : nullptr, 0, dout.p) == 0;
+  ok = ok && launch_cap_rx<R>(nullptr, (int)L, 1, rxs, dout.p) == 0;
   if (ok && link_stats) {
     ok = dstp.alloc(links * 4 * nblk) == 0 && dst.alloc(links * 4) == 0 &&
-         launch_link_stats<R>(nullptr, g, m, 1, np, ray ? ddel.p : nullptr, dcoef.p, dphs.p, dgain.p, fs, dx.p,
-                              link_noise_on ? dls.p : nullptr, dfid.p, seed, lz, 0, dstp.p, nblk, dst.p) == 0;
+         launch_link_stats<R>(nullptr, g, m, 1, taps, dx.p, link_noise_on ? dls.p : nullptr, ln, dstp.p, nblk,
+                              dst.p) == 0;
   }
   ok = ok && hipDeviceSynchronize() == hipSuccess &&
        hipMemcpy(y, dout.p, (size_t)num_rx * L * sizeof(V), hipMemcpyDeviceToHost) == hipSuccess &&
@@ -616,7 +618,7 @@ int lte_crc_host(int64_t n, const uint8_t* bits, uint32_t poly, int len, uint32_
   std::vector<uint32_t> o(nw);
   if (hipMemcpy(dinj.p, w.data(), nw * 4, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemset(dfid.p, 0, 8) != hipSuccess ||
-      launch_payload(nullptr, dpw.p, nw, (int)n, (int)(poly & 0xFFFFFFu), dfid.p, 0, 1, dinj.p, 0) ||
+      launch_payload(nullptr, dpw.p, nw, (int)n, (int)(poly & 0xFFFFFFu), dfid.p, 0, 1, {dinj.p, 0}) ||
       hipMemcpy(o.data(), dpw.p, nw * 4, hipMemcpyDeviceToHost) != hipSuccess)
     return fail(LTE_EHIP, "crc failed");
   uint32_t v = 0;

@@ -756,8 +756,9 @@ __global__ __launch_bounds__(64 * CRC_SEG) void k_crc_count(const CbInfo* __rest
 }
 
 int launch_crc_count(hipStream_t s, const CbInfo* cbi_dev, int C, uint32_t* const* dec, const int* KW, int B,
-                     const uint32_t* pw, int PW, int n_bits, uint32_t* frame_err, uint32_t* frame_crc,
-                     uint8_t* cap_bits, int b0, const uint64_t* fid, uint64_t seed) {
+                     const Scored& sc, uint32_t* frame_crc, uint8_t* cap_bits, int b0, const uint64_t* fid,
+                     uint64_t seed) {
+  const int n_bits = sc.n_bits;
   if (b0 < 0 || b0 >= B || n_bits < 0 || C < 1 || C > CRC_MAXC) return (int)hipErrorInvalidValue;
   const int nw = (n_bits + 24 + 31) >> 5;
   const int SW = (nw + CRC_SEG - 1) / CRC_SEG;
@@ -766,8 +767,8 @@ int launch_crc_count(hipStream_t s, const CbInfo* cbi_dev, int C, uint32_t* cons
     const int end = std::min(32 * (sg + 1) * SW, n_bits);   // data bits up to the segment's end
     xs.x[sg] = gf24_xpow((uint64_t)(n_bits - std::max(end, 0)), (uint32_t)CRC24A_POLY);
   }
-  hipLaunchKernelGGL(k_crc_count, dim3((B - b0 + 63) / 64), dim3(64 * CRC_SEG), 0, s, cbi_dev, C, dec, KW, B, pw, PW,
-                     n_bits, SW, xs, frame_err, frame_crc, cap_bits, b0, fid, seed);
+  hipLaunchKernelGGL(k_crc_count, dim3((B - b0 + 63) / 64), dim3(64 * CRC_SEG), 0, s, cbi_dev, C, dec, KW, B, sc.pw,
+                     sc.PW, n_bits, SW, xs, sc.frame_err, frame_crc, cap_bits, b0, fid, seed);
   return (int)hipGetLastError();
 }
 

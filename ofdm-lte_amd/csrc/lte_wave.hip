@@ -867,9 +867,10 @@ bool tx_simo_w_supported(const Grid& g, int f64, int coded, int sc_fdm, int n_pa
          (!TXSW_HALF || (max_delay <= 64 && g.cp <= 512 && num_rx <= 4));
 }
 
-int launch_ofdm_tx_simo_w(hipStream_t s, const Grid& g, const uint32_t* pw, int PW, int B, double2* cap_syms,
+int launch_ofdm_tx_simo_w(hipStream_t s, const Grid& g, const TxSource& src, int B, double2* cap_syms,
                           const TxChannelT<double>& ch) {
-  if (!tx_simo_w_supported(g, 1, 0, 0, ch.n_paths, ch.max_delay, ch.num_rx, ch.tcoef != nullptr, ch.x_out != nullptr))
+  if (!tx_simo_w_supported(g, 1, src.coded, 0, ch.n_paths, ch.max_delay, ch.num_rx, ch.tcoef != nullptr,
+                           ch.x_out != nullptr))
     return (int)hipErrorInvalidValue;
   const int64_t waves = TXSW_FRAME ? (int64_t)B : (int64_t)B * g.n_sym;
   if (waves > 0x7FFFFFFF - TXSW_WAVES) return (int)hipErrorInvalidValue;
@@ -877,63 +878,63 @@ int launch_ofdm_tx_simo_w(hipStream_t s, const Grid& g, const uint32_t* pw, int 
   return launch_status(with_bps(g.bps, [&](auto Q) {
     with_int_or<0, 4, 6>(ch.n_paths, [&](auto NP) {   // the ITU path counts at compile time
       hipLaunchKernelGGL((k_ofdm_tx_simo_w<Q(), NP()>), dim3(blocks), dim3(64 * TXSW_WAVES),
-                         (size_t)TXSW_WAVES * TXSW_XS * sizeof(double2), s, g, pw, PW, B, cap_syms, ch);
+                         (size_t)TXSW_WAVES * TXSW_XS * sizeof(double2), s, g, src.pw, src.PW, B, cap_syms, ch);
     });
   }));
 }
 
-int launch_rx_frame_simo_w(hipStream_t s, const Grid& g, int B, int num_rx, const double2* y, int64_t y_rx_stride,
-                           int64_t y_frame_stride, const double* npow, const uint64_t* fid, uint64_t seed,
-                           const double* inj_z, int64_t inj_stride, const uint32_t* pw, int PW, int n_bits,
-                           uint32_t* frame_err, double2* cap_syms, uint8_t* cap_bits) {
-  if (!rx_simo_w_supported(g, LTE_CHAIN_SIMO, num_rx, 1, false, false, false)) return (int)hipErrorInvalidValue;
+int launch_rx_frame_simo_w(hipStream_t s, const Grid& g, int B, const RxStreams<double>& rx, const Scored& sc,
+                           const RxCaptures<double>& cap) {
+  const int num_rx = rx.num_rx;
+  if (!rx_simo_w_supported(g, LTE_CHAIN_SIMO, num_rx, 1, cap.H != nullptr, cap.pstats != nullptr, false))
+    return (int)hipErrorInvalidValue;
   const int yrow = g.Nd > SIMOW_ROW_MIN ? g.Nd : SIMOW_ROW_MIN;
   const size_t shm = ((size_t)SIMOW_WAVES * yrow + (size_t)num_rx * g.Np) * sizeof(double2) +
                      (size_t)2 * 64 * SIMOW_WAVES * sizeof(int2) + (size_t)g.Np * sizeof(double);
   return launch_status(with_bps(g.bps, [&](auto Q) {
-    hipLaunchKernelGGL(k_rx_frame_simo_w<Q()>, dim3(B), dim3(64 * SIMOW_WAVES), shm, s, g, B, num_rx, yrow, y,
-                       y_rx_stride, y_frame_stride, npow, fid, seed, inj_z, inj_stride, pw, PW, n_bits, frame_err,
-                       cap_syms, cap_bits);
+    hipLaunchKernelGGL(k_rx_frame_simo_w<Q()>, dim3(B), dim3(64 * SIMOW_WAVES), shm, s, g, B, num_rx, yrow, rx.y,
+                       rx.rx_stride, rx.frame_stride, rx.npow, rx.fid, rx.seed, rx.inj_z.p, rx.inj_z.stride, sc.pw,
+                       sc.PW, sc.n_bits, sc.frame_err, cap.syms, cap.bits);
   }));
 }
 
-int launch_rx_frame_w(hipStream_t s, const Grid& g, int rayleigh, int B, const double2* y, int64_t y_frame_stride,
-                      const double* npow, const double* snr_lin, const uint64_t* fid, uint64_t seed,
-                      const double* inj_z, int64_t inj_stride, double* zo, double* nv_out, double2* cap_syms,
-                      double2* H, double* pstats) {
-  if (!rx_frame_w_supported(g, LTE_CHAIN_CODED, 1) || !nv_out) return (int)hipErrorInvalidValue;
+int launch_rx_frame_w(hipStream_t s, const Grid& g, int rayleigh, int B, const RxStreams<double>& rx,
+                      const double* snr_lin, const SoftOut<double>& soft, const RxCaptures<double>& cap) {
+  if (!rx_frame_w_supported(g, LTE_CHAIN_CODED, 1) || rx.num_rx != 1 || !soft.ok() || !soft.z)
+    return (int)hipErrorInvalidValue;
   const size_t shm = (size_t)RXW_WAVES * wfft::LDS_DOUBLES * sizeof(double);
   (void)hipFuncSetAttribute((const void*)k_rx_frame_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
   hipLaunchKernelGGL(k_rx_frame_w, dim3((B + RXW_WAVES - 1) / RXW_WAVES), dim3(64 * RXW_WAVES), shm, s, g, rayleigh,
-                     B, y, y_frame_stride, npow, snr_lin, fid, seed, inj_z, inj_stride,
-                     reinterpret_cast<double2*>(zo), nv_out, cap_syms, H, pstats);
+                     B, rx.y, rx.frame_stride, rx.npow, snr_lin, rx.fid, rx.seed, rx.inj_z.p, rx.inj_z.stride, soft.z,
+                     soft.nv, cap.syms, cap.H, cap.pstats);
   return (int)hipGetLastError();
 }
 
-int launch_ofdm_txf_w(hipStream_t s, const Grid& g, const uint32_t* enc, int enc_words, const int32_t* tx_map, int B,
-                      double2* cap_syms, const TxChannelT<double>& ch, int stage) {
-  if (!txf_w_supported(g, 1, ch.n_paths, ch.max_delay, ch.num_rx, ch.tcoef != nullptr)) return (int)hipErrorInvalidValue;
+int launch_ofdm_txf_w(hipStream_t s, const Grid& g, const TxSource& src, int B, double2* cap_syms,
+                      const TxChannelT<double>& ch, int stage) {
+  if (!src.coded || !txf_w_supported(g, 1, ch.n_paths, ch.max_delay, ch.num_rx, ch.tcoef != nullptr))
+    return (int)hipErrorInvalidValue;
+  const int enc_words = src.enc_words;
   const size_t shm = (size_t)TXW_WAVES * (TXW_XS + (stage ? 4 * (size_t)((enc_words + 3) & ~3) : 0));
   if (shm > 160 * 1024) return (int)hipErrorInvalidValue;
   return launch_status(with_bps(g.bps, [&](auto Q) {
     with_bool(stage, [&](auto STAGE) {
       auto k = k_ofdm_txf_w<Q(), 4, STAGE()>;
       (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      hipLaunchKernelGGL(k, dim3((B + TXW_WAVES - 1) / TXW_WAVES), dim3(64 * TXW_WAVES), shm, s, g, enc, enc_words,
-                         tx_map, B, cap_syms, ch);
+      hipLaunchKernelGGL(k, dim3((B + TXW_WAVES - 1) / TXW_WAVES), dim3(64 * TXW_WAVES), shm, s, g, src.enc,
+                         src.enc_words, src.tx_map, B, cap_syms, ch);
     });
   }));
 }
 
-int launch_rx_fft_mimo_w(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const double2* y, const double* npow,
-                         const uint64_t* fid, uint64_t seed, const double* inj_z, int64_t inj_stride, double2* Y,
-                         double2* H) {
+int launch_rx_fft_mimo_w(hipStream_t s, const Grid& g, const MimoGrid& m, int B, const RxStreams<double>& rx,
+                         double2* Y, double2* H) {
   if (!rx_fft_mimo_w_supported(g, m, 1, 1)) return (int)hipErrorInvalidValue;
   const int64_t total = (int64_t)B * m.num_rx;
   if (total > 0x7FFFFFFF - RXMW_WAVES) return (int)hipErrorInvalidValue;
   const size_t shm = (size_t)RXMW_WAVES * wfft::LDS_DOUBLES * sizeof(double);
   hipLaunchKernelGGL(k_rx_fft_mimo_w, dim3((unsigned)((total + RXMW_WAVES - 1) / RXMW_WAVES)), dim3(64 * RXMW_WAVES),
-                     shm, s, g, m, B, y, npow, fid, seed, inj_z, inj_stride, Y, H);
+                     shm, s, g, m, B, rx.y, rx.npow, rx.fid, rx.seed, rx.inj_z.p, rx.inj_z.stride, Y, H);
   return (int)hipGetLastError();
 }
 

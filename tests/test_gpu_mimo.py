@@ -228,6 +228,51 @@ def test_link_power_in_tx_matches_separate_pass(C, prec, monkeypatch):
     assert np.array_equal(a['frame_errors'], b['frame_errors']) and np.array_equal(a['crc_ok'], b['crc_ok'])
 
 
+@pytest.mark.parametrize('inject', [False, True])
+def test_channel_mimo_matches_channel_tay_under_link_noise(C, inject, monkeypatch):
+    """SFBC 2x2 over Rayleigh links (static taps, transmit_mimo's 100 dB link
+    noise), the channel as its own pass: k_channel_mimo (LTE_CHM_TAY=0) against
+    k_channel_tay (default) on the same frames, the link noise drawn from Philox
+    or injected.  Both sum the same <= 2 x 4 tap products per sample in another
+    order (a few ulps of the terms), so the received streams agree to 1e-13 of
+    their norm and the measured noise powers to 1e-13; identical bit errors.
+    Philox draws only: the link statistics (k_link_stats_part draws each link's
+    noise itself) against a run with zeros injected as link noise -- the noise
+    is 1e-10 of the link's power P, so over L samples mean|y|^2 moves by
+    P sqrt(2 / (1e10 L)) = 3e-7 P (one sigma) and mean(y conj x) likewise:
+    within 1e-5 of the statistic's scale, and mean|x|^2 is the same number.
+    One slot of 14 symbols at N = 128, 5 frames."""
+    sim = _sim(1.25, 'QPSK', 'rayleigh_mp', 'f64')
+    B = 5
+    plan = sim._sfbc_plan(14, 14 * (sim.Nd & ~1) * 2, 2, max_frames=B)
+    snrs = np.array([0.0, 4.0, 8.0, 16.0, 30.0])
+    kw = {}
+    if inject:
+        kw = dict(link_noise=np.random.default_rng(17).standard_normal((B, 2, 2, 2, plan.L)))
+    cap = ('signal_rx', 'noise_power', 'link_stats')
+    monkeypatch.setenv('LTE_SFBC_TXCH_FUSE', '0')   # the separate TX / channel kernels on either side
+    outs = []
+    for tay in ('1', '0'):
+        monkeypatch.setenv('LTE_CHM_TAY', tay)
+        outs.append(plan.run(snrs, seed=41, frame_id0=300, capture=cap, **kw))
+    a, b = outs
+    assert path_diff(a.path, b.path) == {'ch'}, (a.path, b.path)
+    assert a.path['ch'].startswith('k_channel_tay') and b.path['ch'] == 'k_channel_mimo', (a.path, b.path)
+    y0, y1 = a['signal_rx'], b['signal_rx']
+    assert y0.shape == (B, 2, plan.L)
+    assert np.linalg.norm(y0 - y1) / np.linalg.norm(y1) < 1e-13
+    assert np.max(np.abs(a['noise_power'] / b['noise_power'] - 1)) < 1e-13
+    assert np.array_equal(a['frame_errors'], b['frame_errors']) and 0 < int(a['frame_errors'].sum())
+    if not inject:
+        z = plan.run(snrs, seed=41, frame_id0=300, capture=cap, link_noise=np.zeros((B, 2, 2, 2, plan.L)))
+        s0, s1 = z['link_stats'], a['link_stats']   # [B][rx][tx]: mean|x|^2, mean|y|^2, Re, Im mean(y conj x)
+        assert s0.shape == (B, 2, 2, 4) and np.all(s0[..., 1] > 0)
+        assert np.array_equal(s0[..., 0], s1[..., 0])
+        assert np.max(np.abs(s1[..., 1] / s0[..., 1] - 1)) < 1e-5 and not np.array_equal(s0[..., 1], s1[..., 1])
+        scale = np.sqrt(s0[..., 0] * s0[..., 1])
+        assert np.max(np.abs(s1[..., 2:] - s0[..., 2:]) / scale[..., None]) < 1e-5
+
+
 @pytest.mark.parametrize('prec', ['f64', 'f32'])
 @pytest.mark.parametrize('coded,nrx', [(True, 2), (False, 2), (False, 1)])
 def test_sfbc_txch_fused_matches_separate_kernels(C, prec, coded, nrx, monkeypatch):

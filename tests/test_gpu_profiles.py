@@ -456,7 +456,7 @@ def test_siso_pedestrian_a_15mhz_coded(C, oracle, monkeypatch):
     (txf_peda_launch) by default.  LTE_TX_WAVE=1: txf_w_supported holds (N 2048, 4
     taps, max 13 <= 64) -> k_ofdm_txf_w; LTE_RX_WAVE=1 without an llr capture:
     rx_frame_w_supported holds (cp 144 even, Np = 150) -> k_rx_frame_w; with the
-    llr capture nv_out is null and k_rx_frame runs after the wave TX."""
+    llr capture SoftOut::z is null and k_rx_frame runs after the wave TX."""
     check_case(C, oracle, monkeypatch, 'siso_pa15_cod', V_CODED)
 
 
