@@ -348,6 +348,33 @@ int lte_plan_repack_info(const lte_plan *plan, int64_t *info, int n);
  * LTE_EINVAL when early stop is off, nothing has run since it was set, or n
  * is not that run's size. */
 int lte_plan_turbo_iters_used(const lte_plan *plan, uint8_t *out, int64_t n);
+/* Extrinsic scaling of the turbo decoder, scaled max-log-MAP (ABI 3, additions;
+ * opt-in; coded chains only, HARQ plans and early-stop / re-packing plans
+ * included, in either order with their setters).
+ * A scale s is a number with 0 < s <= 1.  In every decoder-1 and decoder-2
+ * half-iteration the extrinsic is
+ *     e = s * ((L - La) - Ls)
+ * - The two subtractions are as without scaling (turbo_decoder.py:270).
+ * - One further multiply follows, rounded separately in the plan's arithmetic.
+ * - In float32 plans the factor is (float)s.
+ * - The multiply is not contracted into a neighbouring add.
+ * - The decoder rows hold halves: s * ((0.5 L - la) - ls) is exactly half of
+ *   e, so the row convention does not change.
+ * - The a-posteriori L is not scaled.  That covers the final pass and the
+ *   decoder-1 decisions the early-stop kernels pack.
+ * - The inputs Ls, Lp and the HARQ soft rows are not scaled.
+ * - The early-stop rule is unchanged.  D(n) are now the decisions of the scaled
+ *   decode of n iterations.
+ * - Re-packing stays "bit for bit the plan without re-packing".
+ * - s = 1 means no scaling.  It launches the unscaled kernels, with no
+ *   multiply-by-one instance, and every output is bit for bit the unscaled one.
+ * A new plan has scale 1.  LTE_EINVAL before the device is touched: NULL plan,
+ * an uncoded chain, a scale that is NaN or outside (0, 1].  Max-log decoding
+ * only: lte_run refuses a plan whose scale is not 1 with LTE_EUNSUP while
+ * lte_set_decoder_mode(0) holds.  lte_run_path appends " ext=<scale, %g>" as
+ * its last item when the scale is not 1. */
+int lte_plan_set_turbo_scale(lte_plan *plan, double scale);
+double lte_plan_turbo_scale(const lte_plan *plan);   /* as passed; 1.0 on a new plan, NaN for NULL */
 /* HARQ retransmissions with soft combining (ABI 3, additions; coded SISO chain
  * LTE_CHAIN_CODED only: any other chain LTE_EUNSUP).  A HARQ plan sends each
  * transport block up to max_tx times; transmission t is rate matched with
@@ -483,6 +510,24 @@ int lte_turbo_decode_es_repack_host64(int K, int iters, int64_t ncb, const doubl
                                       uint32_t crc_poly, int after, uint8_t *bits, uint8_t *iters_used, int64_t *info);
 int lte_turbo_decode_es_repack_host(int K, int iters, int64_t ncb, const float *llr /*[ncb][3K+12]*/,
                                     uint32_t crc_poly, int after, uint8_t *bits, uint8_t *iters_used, int64_t *info);
+/* The turbo decode entries with extrinsic scaling (lte_plan_set_turbo_scale):
+ * layouts and checks of lte_turbo_decode_host64 / _host.  A scale that is NaN
+ * or outside (0, 1]: LTE_EINVAL; a scale other than 1 under
+ * lte_set_decoder_mode(0): LTE_EUNSUP.  scale = 1 is the unscaled entry. */
+int lte_turbo_decode_scaled_host64(int K, int iters, int64_t ncb, const double *llr /*[ncb][3K+12]*/, double scale,
+                                   uint8_t *bits);
+int lte_turbo_decode_scaled_host(int K, int iters, int64_t ncb, const float *llr /*[ncb][3K+12]*/, double scale,
+                                 uint8_t *bits);
+/* The early-stop entries with extrinsic scaling: after = 0 is plain early stop
+ * (lte_turbo_decode_es_host64 / _host; info may be NULL), 1 <= after < iters
+ * the re-packing form with info [3] (lte_turbo_decode_es_repack_host64 /
+ * _host); another after, or a bad scale: LTE_EINVAL. */
+int lte_turbo_decode_es_scaled_host64(int K, int iters, int64_t ncb, const double *llr /*[ncb][3K+12]*/,
+                                      uint32_t crc_poly, double scale, int after, uint8_t *bits, uint8_t *iters_used,
+                                      int64_t *info);
+int lte_turbo_decode_es_scaled_host(int K, int iters, int64_t ncb, const float *llr /*[ncb][3K+12]*/,
+                                    uint32_t crc_poly, double scale, int after, uint8_t *bits, uint8_t *iters_used,
+                                    int64_t *info);
 /* float64 single BCJR pass of any length n, a-posteriori output for every step:
  * LogMAPDecoder.decode (turbo_decoder.py:181-278) with return_extrinsic=False.
  * n = 0 is valid (nothing written), like the reference's zero-step recursion. */

@@ -350,14 +350,16 @@ int turbo_plan_ch(const lte_plan* p) { return turbo_chunk((p->d.max_frames + 63)
 // code block's CRC-24 holds -- gCRC24A for a transport block of one code block,
 // gCRC24B for several (segmentation.py:74-263)
 int plan_launch_turbo(lte_plan* p, hipStream_t s, const std::vector<TurboJob>& jobs, int B, int f64) {
-  if (!p->early_stop) return launch_turbo_jobs(s, jobs.data(), p->C, p->d.turbo_iters, TM_DEC1, f64);
+  const double sc = p->turbo_scale;
+  if (!p->early_stop) return launch_turbo_jobs(s, jobs.data(), p->C, p->d.turbo_iters, TM_DEC1, f64, nullptr, sc);
   std::vector<uint32_t*> used(p->C);
   std::vector<int> nv(p->C, B);
   for (int r = 0; r < p->C; ++r) used[r] = p->es_used[r].p;
   p->es_frames = B;
   const uint32_t poly = p->C == 1 ? CRC24A_POLY : CRC24B_POLY;
   if (!p->repack_after)
-    return launch_turbo_jobs_es(s, jobs.data(), used.data(), nv.data(), p->C, p->d.turbo_iters, f64, poly);
+    return launch_turbo_jobs_es(s, jobs.data(), used.data(), nv.data(), p->C, p->d.turbo_iters, f64, poly, nullptr,
+                                sc);
   // re-packing: the undecided blocks continue in the plan's packed arrays
   std::vector<TurboPack> pk(p->C);
   const int cap = turbo_pack_cap((p->d.max_frames + 63) / 64);
@@ -368,7 +370,7 @@ int plan_launch_turbo(lte_plan* p, hipStream_t s, const std::vector<TurboJob>& j
   }
   p->rp_last.assign((size_t)3 * p->C, 0);
   return launch_turbo_jobs_es_repack(s, jobs.data(), used.data(), nv.data(), p->C, p->d.turbo_iters, f64, poly,
-                                     p->repack_after, pk.data(), p->rp_cnt.p, p->rp_last.data());
+                                     p->repack_after, pk.data(), p->rp_cnt.p, p->rp_last.data(), sc);
 }
 
 // the packed rows / checkpoints of re-packing, cap groups per CB slot (true: out of memory)
@@ -1210,6 +1212,23 @@ int lte_plan_repack_info(const lte_plan* p, int64_t* info, int n) {
   return (int)v.size();
 }
 
+int lte_plan_set_turbo_scale(lte_plan* p, double scale) {
+  if (!p) return fail(LTE_EINVAL, "null plan");
+  if (!p->ct->coded)
+    return fail(LTE_EINVAL, "extrinsic scaling applies to the coded chains only (nothing is decoded in this plan)");
+  if (!(scale > 0.0 && scale <= 1.0)) return fail(LTE_EINVAL, "turbo scale must be in (0, 1]");
+  p->turbo_scale = scale;
+  return LTE_OK;
+}
+
+double lte_plan_turbo_scale(const lte_plan* p) {
+  if (!p) {
+    fail(LTE_EINVAL, "null plan");
+    return (double)NAN;
+  }
+  return p->turbo_scale;
+}
+
 int lte_plan_early_stop(const lte_plan* p) {
   if (!p) return fail(LTE_EINVAL, "null plan");
   return p->early_stop ? 1 : 0;
@@ -1581,7 +1600,8 @@ static int decode_blocks(lte_plan* p, const lte_run_args* a, int B, const int32_
   if (!(skip && nskip == G)) {
     Timer t(p, KN_TURBO);
     if (skip)
-      LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, sizeof(R) == 8 ? 1 : 0, p->hq_skip.p));
+      LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, sizeof(R) == 8 ? 1 : 0, p->hq_skip.p,
+                             p->turbo_scale));
     else
       LCHK(plan_launch_turbo(p, s, jobs, B, sizeof(R) == 8 ? 1 : 0));
   }
@@ -2124,6 +2144,8 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
     return fail(LTE_EUNSUP, "exact log-MAP decoding runs in float64 plans only");
   if (logmap_on() && p->early_stop)
     return fail(LTE_EUNSUP, "CRC early termination runs the max-log decoders only (set_decoder_mode(True))");
+  if (logmap_on() && p->turbo_scale != 1.0)
+    return fail(LTE_EUNSUP, "extrinsic scaling runs the max-log decoders only (set_decoder_mode(True))");
   const Knobs knobs = read_knobs();   // the environment switches, once per run
   if (!p->mimo && !p->bf) {
     const SisoPath path = select_siso(p, a, knobs);
@@ -2177,6 +2199,7 @@ int lte_run_path(const lte_plan* p, const lte_run_args* a, char* buf, int len) {
   if (p->harq && n >= 0 && n < len)
     n += std::snprintf(buf + n, len - n, " harq=t%d,rv%d,skip=%d", p->hq_round, p->hq.rv_seq[p->hq_round],
                        select_siso(p, a, knobs).hq_skip ? 1 : 0);
+  if (p->turbo_scale != 1.0 && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " ext=%g", p->turbo_scale);
   return n < len ? n : len - 1;
 }
 

@@ -273,11 +273,16 @@ struct RowPtr {
 // ES (the early-stop kernels, MODE TM_DEC1 only): the decoder-1 pass packs the
 // same decisions next to its extrinsic store -- its L is TM_FINAL's L, same
 // inputs, same operations -- and only lanes with `live` set store their words.
-template <class T, int MODE, bool LM = false, int CH = TURBO_CH, bool ES = false>
+// SC (the scaled kernels k_turbo*_sc, MODE TM_DEC1 / TM_DEC2 only): the stored
+// extrinsic is sc * ((L/2 - La/2) - Ls/2), one more separately rounded multiply
+// (lte_phy.h lte_plan_set_turbo_scale); sc is wave-uniform (a kernel argument).
+// The a-posteriori L, and with it every decision, is not scaled.
+template <class T, int MODE, bool LM = false, int CH = TURBO_CH, bool ES = false, bool SC = false>
 __device__ __forceinline__ void half_pass(T* __restrict__ wbase, T* __restrict__ wck, int slot, int lane, int K,
                                           int f1, int f2, bool first, uint32_t* __restrict__ bo = nullptr,
-                                          bool live = true) {
+                                          bool live = true, T sc = (T)1) {
   static_assert(!ES || MODE == TM_DEC1, "early stop packs in the decoder-1 pass");
+  static_assert(!SC || (!LM && (MODE == TM_DEC1 || MODE == TM_DEC2)), "the max-log extrinsic stores scale");
   using TT = TurboT<T>;
   using DRow = RowPtr<T, RS * CH * (int)sizeof(T), LTE_TURBO_CPOL>;   // the block arrays' rows (CH groups side by side)
   constexpr int TSUB = TT::TSUB, SW = TW * TSUB, CK = TT::CK, CK0 = 8 - CK;   // CK0: first stored state
@@ -471,12 +476,15 @@ __device__ __forceinline__ void half_pass(T* __restrict__ wbase, T* __restrict__
           gam(ls[i], lp[i], la[i], c);
           const T L = bstep<T, LM>(b, c, A[j]);
           if (MODE == TM_DEC1) {
-            LE.st(k, ((T)0.5 * L - la[i]) - ls[i]);
+            // (SC: a product of a difference, stored: nothing there contracts into an fma)
+            if constexpr (SC) LE.st(k, sc * (((T)0.5 * L - la[i]) - ls[i]));
+            else LE.st(k, ((T)0.5 * L - la[i]) - ls[i]);
             if constexpr (ES) acc |= (L < (T)0 ? 1u : 0u) << (31 - (k & 31));
           } else if (MODE == TM_DEC2) {
             dd = modsub(dd, tf2, K);
             pp = modsub(pp, dd, K);   // pp = pi(k)
-            LE.st(pp, ((T)0.5 * L - la[i]) - ls[i]);
+            if constexpr (SC) LE.st(pp, sc * (((T)0.5 * L - la[i]) - ls[i]));
+            else LE.st(pp, ((T)0.5 * L - la[i]) - ls[i]);
           } else if (MODE == TM_APP) {  // a-posteriori LLR in place of the extrinsic row
             LE.st(k, L);
           } else {  // TM_FINAL
@@ -509,9 +517,12 @@ __device__ __forceinline__ void half_pass(T* __restrict__ wbase, T* __restrict__
 // SKIP (the HARQ kernels k_turbo64_skip / k_turbo_skip): skip[g] != 0 marks a
 // frame group with nothing left to decode; g is wave-uniform, so the flag is a
 // scalar load and the wave leaves before it touches a row.
-template <class T, bool LM = false, int CH = TURBO_CH, bool SKIP = false>
+// SC (the scaled kernels k_turbo64_sc / k_turbo_sc): the decoder-1 / decoder-2
+// passes scale their extrinsic by sc; their skip may be null (no flags:
+// nothing is skipped), so one twin serves both fixed forms.
+template <class T, bool LM = false, int CH = TURBO_CH, bool SKIP = false, bool SC = false>
 __device__ __forceinline__ void turbo_body(const TurboJobs& jobs, int iters, int mode,
-                                           const uint32_t* __restrict__ skip = nullptr) {
+                                           const uint32_t* __restrict__ skip = nullptr, T sc = (T)1) {
   const int wg = blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (wg >= jobs.prefix[jobs.n]) return;
@@ -519,7 +530,9 @@ __device__ __forceinline__ void turbo_body(const TurboJobs& jobs, int iters, int
   while (wg >= jobs.prefix[r + 1]) ++r;
   const TurboJob jb = jobs.j[r];
   const int g = wg - jobs.prefix[r];
-  if constexpr (SKIP) {
+  if constexpr (SC) {
+    if (skip != nullptr && skip[g] != 0u) return;
+  } else if constexpr (SKIP) {
     if (skip[g] != 0u) return;
   }
   const int K = jb.K;
@@ -533,8 +546,8 @@ __device__ __forceinline__ void turbo_body(const TurboJobs& jobs, int iters, int
     return;
   }
   for (int it = 0; it < iters; ++it) {
-    half_pass<T, TM_DEC1, LM, CH>(base, ck, slot, lane, K, jb.f1, jb.f2, it == 0);
-    half_pass<T, TM_DEC2, LM, CH>(base, ck, slot, lane, K, jb.f1, jb.f2, false);
+    half_pass<T, TM_DEC1, LM, CH, false, SC>(base, ck, slot, lane, K, jb.f1, jb.f2, it == 0, nullptr, true, sc);
+    half_pass<T, TM_DEC2, LM, CH, false, SC>(base, ck, slot, lane, K, jb.f1, jb.f2, false, nullptr, true, sc);
   }
   // final pass = decoder 1 a-posteriori LLRs (turbo_decoder.py:440-447) and
   // the hard decisions L < 0 (:276), packed MSB-first
@@ -595,6 +608,29 @@ __global__ __launch_bounds__(256, LTE_TURBO64_ONE_WAVE ? 1 : 2) void k_turbo64_s
   turbo_body<double, false, CH, true>(jobs, iters, mode, skip);
 }
 
+// The fixed decoders with extrinsic scaling (opt-in): the bodies
+// and register caps of k_turbo_skip / k_turbo64_skip with the factor as one
+// more kernel argument (wave-uniform, so it lives in SGPRs); skip may be null.
+template <int CH>
+__global__ __launch_bounds__(256, LTE_TURBO32_WAVES == 3 ? 2 : 1) void k_turbo_sc(TurboJobs jobs, int iters, int mode,
+                                                                                   const uint32_t* skip, float sc) {
+#if LTE_TURBO32_WAVES == 2
+  asm volatile("" ::: "a47");
+#elif LTE_TURBO32_WAVES == 1
+  asm volatile("" ::: "a127");
+#endif
+  turbo_body<float, false, CH, false, true>(jobs, iters, mode, skip, sc);
+}
+
+template <int CH>
+__global__ __launch_bounds__(256, LTE_TURBO64_ONE_WAVE ? 1 : 2) void k_turbo64_sc(TurboJobs jobs, int iters, int mode,
+                                                                                   const uint32_t* skip, double sc) {
+#if LTE_TURBO64_ONE_WAVE
+  asm volatile("" ::: "a31");
+#endif
+  turbo_body<double, false, CH, false, true>(jobs, iters, mode, skip, sc);
+}
+
 // f64 exact log-MAP (set_decoder_mode(False)); not a hot path
 template <int CH>
 __global__ __launch_bounds__(256, 1) void k_turbo64_logmap(TurboJobs jobs, int iters, int mode) {
@@ -633,9 +669,13 @@ struct TurboEs {
 // rows (LE as decoder 1 left it); the checkpoints are scratch.  (TurboWin:
 // lte_internal.h)
 
-template <class T, int CH, bool WIN = false>
+// SC (the scaled kernels k_turbo64_es_sc / k_turbo_es_sc): both passes scale
+// their extrinsic by sc.  These are WIN instances; win.after = 0 (no iteration
+// is the boundary, resume 0) makes them the unwindowed decode, so one twin
+// serves k_turbo*_es and k_turbo*_esw.
+template <class T, int CH, bool WIN = false, bool SC = false>
 __device__ __forceinline__ void turbo_body_es(const TurboJobs& jobs, const TurboEs& es, int iters, uint32_t* crc_t,
-                                              TurboWin win = {}) {
+                                              TurboWin win = {}, T sc = (T)1) {
   crc24_slice4_fill(crc_t, es.poly);
   __syncthreads();   // the only barrier (one wave)
   const int wg = blockIdx.x;
@@ -669,8 +709,8 @@ __device__ __forceinline__ void turbo_body_es(const TurboJobs& jobs, const Turbo
       // iterations: from it = 1 on (and at it = iters, where the decode ends)
       // its decisions are D(it)
       const bool last = it == iters;
-      half_pass<T, TM_DEC1, false, CH, true>(base, ck, slot, lane, K, jb.f1, jb.f2, it == 0, bo,
-                                             !done && (it > 0 || last));
+      half_pass<T, TM_DEC1, false, CH, true, SC>(base, ck, slot, lane, K, jb.f1, jb.f2, it == 0, bo,
+                                                 !done && (it > 0 || last), sc);
       if (last) {
         if (!done) used.st(0, (uint32_t)it);
         return;
@@ -693,7 +733,7 @@ __device__ __forceinline__ void turbo_body_es(const TurboJobs& jobs, const Turbo
       }
     }
     resumed = false;
-    half_pass<T, TM_DEC2, false, CH>(base, ck, slot, lane, K, jb.f1, jb.f2, false);
+    half_pass<T, TM_DEC2, false, CH, false, SC>(base, ck, slot, lane, K, jb.f1, jb.f2, false, nullptr, true, sc);
   }
 }
 
@@ -742,6 +782,33 @@ __global__ __launch_bounds__(64, LTE_TURBO64_ONE_WAVE ? 1 : 2) void k_turbo64_es
   asm volatile("" ::: "a31");
 #endif
   turbo_body_es<double, CH, true>(jobs, es, iters, crc_t, win);
+}
+
+// The early-stop decoders with extrinsic scaling, windowed or not (win.after =
+// 0: not): the bodies and register caps of k_turbo_esw / k_turbo64_esw, the
+// factor as one more kernel argument.
+template <int CH>
+__global__ __launch_bounds__(64, LTE_TURBO32_WAVES == 3 ? 2 : 1) void k_turbo_es_sc(TurboJobs jobs, TurboEs es,
+                                                                                      int iters, TurboWin win,
+                                                                                      float sc) {
+  __shared__ uint32_t crc_t[1024];
+#if LTE_TURBO32_WAVES == 2
+  asm volatile("" ::: "a47");
+#elif LTE_TURBO32_WAVES == 1
+  asm volatile("" ::: "a127");
+#endif
+  turbo_body_es<float, CH, true, true>(jobs, es, iters, crc_t, win, sc);
+}
+
+template <int CH>
+__global__ __launch_bounds__(64, LTE_TURBO64_ONE_WAVE ? 1 : 2) void k_turbo64_es_sc(TurboJobs jobs, TurboEs es,
+                                                                                      int iters, TurboWin win,
+                                                                                      double sc) {
+  __shared__ uint32_t crc_t[1024];
+#if LTE_TURBO64_ONE_WAVE
+  asm volatile("" ::: "a31");
+#endif
+  turbo_body_es<double, CH, true, true>(jobs, es, iters, crc_t, win, sc);
 }
 
 // ---------------------------------------------------------------------------
@@ -836,8 +903,13 @@ static int g_logmap = 0;
 void set_logmap(int on) { g_logmap = on ? 1 : 0; }
 int logmap_on() { return g_logmap; }
 
-int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int mode, int f64, const uint32_t* skip) {
+// a scale the launchers take: 1 (off), or in (0, 1) with the max-log decoders
+static bool scale_ok(double scale) { return scale == 1.0 || (scale > 0.0 && scale < 1.0 && !g_logmap); }
+
+int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int mode, int f64, const uint32_t* skip,
+                      double scale) {
   if (skip && g_logmap) return (int)hipErrorInvalidValue;   // max-log only (the caller does not ask for it)
+  if (!scale_ok(scale) || (scale != 1.0 && mode != TM_DEC1)) return (int)hipErrorInvalidValue;
   for (int o = 0; o < n; o += TURBO_MAX_JOBS) {
     TurboJobs J{};
     J.n = n - o < TURBO_MAX_JOBS ? n - o : TURBO_MAX_JOBS;
@@ -861,7 +933,11 @@ int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int
     auto with_form = [&](auto&& f) {
       return with_int<TURBO_CH, 1>(ch, [&](auto CH) { with_bool(f64, [&](auto F64) { f(CH, F64); }); });
     };
-    const int e = launch_status(skip ? with_form([&](auto CH, auto F64) {
+    // (a scale of 1 launches the unscaled kernels: there is no multiply-by-one instance)
+    const int e = launch_status(scale != 1.0 ? with_form([&](auto CH, auto F64) {
+      if constexpr (F64()) hipLaunchKernelGGL(k_turbo64_sc<CH()>, grid, dim3(256), 0, s, J, iters, mode, skip, scale);
+      else hipLaunchKernelGGL(k_turbo_sc<CH()>, grid, dim3(256), 0, s, J, iters, mode, skip, (float)scale);
+    }) : skip ? with_form([&](auto CH, auto F64) {
       if constexpr (F64()) hipLaunchKernelGGL(k_turbo64_skip<CH()>, grid, dim3(256), 0, s, J, iters, mode, skip);
       else hipLaunchKernelGGL(k_turbo_skip<CH()>, grid, dim3(256), 0, s, J, iters, mode, skip);
     }) : with_form([&](auto CH, auto F64) {
@@ -880,8 +956,9 @@ int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int
 // the early-stop decoders: used[i] / nv[i] per job (TurboEs), poly CRC24A_POLY / CRC24B_POLY
 // win set: one window of a re-packing decode (k_turbo*_esw)
 int launch_turbo_jobs_es(hipStream_t s, const TurboJob* jobs, uint32_t* const* used, const int* nv, int n, int iters,
-                         int f64, uint32_t poly, const TurboWin* win) {
+                         int f64, uint32_t poly, const TurboWin* win, double scale) {
   if (g_logmap || iters < 0) return (int)hipErrorInvalidValue;   // max-log only (the callers refuse it first)
+  if (!scale_ok(scale)) return (int)hipErrorInvalidValue;
   if (win && (win->after < 1 || win->after >= iters)) return (int)hipErrorInvalidValue;
   for (int o = 0; o < n; o += TURBO_MAX_JOBS) {
     TurboJobs J{};
@@ -904,7 +981,11 @@ int launch_turbo_jobs_es(hipStream_t s, const TurboJob* jobs, uint32_t* const* u
     auto with_form = [&](auto&& f) {
       return with_int<TURBO_CH, 1>(ch, [&](auto CH) { with_bool(f64, [&](auto F64) { f(CH, F64); }); });
     };
-    const int e = launch_status(win ? with_form([&](auto CH, auto F64) {
+    const TurboWin ws = win ? *win : TurboWin{0, 0};   // the scaled twins: after 0 = not windowed
+    const int e = launch_status(scale != 1.0 ? with_form([&](auto CH, auto F64) {
+      if constexpr (F64()) hipLaunchKernelGGL(k_turbo64_es_sc<CH()>, grid, block, 0, s, J, E, iters, ws, scale);
+      else hipLaunchKernelGGL(k_turbo_es_sc<CH()>, grid, block, 0, s, J, E, iters, ws, (float)scale);
+    }) : win ? with_form([&](auto CH, auto F64) {
       if constexpr (F64()) hipLaunchKernelGGL(k_turbo64_esw<CH()>, grid, block, 0, s, J, E, iters, *win);
       else hipLaunchKernelGGL(k_turbo_esw<CH()>, grid, block, 0, s, J, E, iters, *win);
     }) : with_form([&](auto CH, auto F64) {
@@ -924,9 +1005,9 @@ int launch_turbo_jobs_es(hipStream_t s, const TurboJob* jobs, uint32_t* const* u
 // width; the scatter of the packed jobs.  info: 3 per job (lte_internal.h).
 int launch_turbo_jobs_es_repack(hipStream_t s, const TurboJob* jobs, uint32_t* const* used, const int* nv, int n,
                                 int iters, int f64, uint32_t poly, int after, const TurboPack* pk, uint32_t* counts,
-                                int64_t* info) {
+                                int64_t* info, double scale) {
   const TurboWin w0{after, 0}, w1{after, 1};
-  if (int e = launch_turbo_jobs_es(s, jobs, used, nv, n, iters, f64, poly, &w0)) return e;
+  if (int e = launch_turbo_jobs_es(s, jobs, used, nv, n, iters, f64, poly, &w0, scale)) return e;
   for (int i = 0; i < n; ++i)
     hipLaunchKernelGGL(k_repack_index, dim3(1), dim3(64 * RPK_WAVES), 0, s, used[i], nv[i], jobs[i].G, pk[i].idx,
                        pk[i].cap * RS, counts + i);
@@ -969,7 +1050,7 @@ int launch_turbo_jobs_es_repack(hipStream_t s, const TurboJob* jobs, uint32_t* c
   for (int k = 0; k < 2; ++k)
     if (!rj[k].empty())
       if (int e = launch_turbo_jobs_es(s, rj[k].data(), ru[k].data(), rn[k].data(), (int)rj[k].size(), iters, f64, poly,
-                                       &w1))
+                                       &w1, scale))
         return e;
   for (int i = 0; i < n; ++i)
     if (info[3 * i + 2] == TURBO_RP_PACKED)
@@ -979,9 +1060,9 @@ int launch_turbo_jobs_es_repack(hipStream_t s, const TurboJob* jobs, uint32_t* c
 }
 
 int launch_turbo(hipStream_t s, void* blk, void* ckpt, uint32_t* bits, int K, int f1, int f2, int iters, int G,
-                 int mode, int f64, int ch) {
+                 int mode, int f64, int ch, double scale) {
   TurboJob j{blk, ckpt, bits, K, f1, f2, G, ch};
-  return launch_turbo_jobs(s, &j, 1, iters, mode, f64);
+  return launch_turbo_jobs(s, &j, 1, iters, mode, f64, nullptr, scale);
 }
 
 // ---------------------------------------------------------------------------

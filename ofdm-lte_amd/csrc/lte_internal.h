@@ -310,8 +310,13 @@ int launch_harq_zero(hipStream_t s, const int32_t* zmap, int nz, int G, R* const
 int launch_harq_latch(hipStream_t s, int B, int t, uint32_t* frame_err, uint32_t* frame_crc, uint32_t* tx_used,
                       uint32_t* l_err, uint32_t* l_crc, uint32_t* skip);
 // f64 != 0: the float64 decoder (bit-exact with the reference), blk / ckpt hold doubles
+// scale (here and in the launchers below): the extrinsic scaling of
+// lte_plan_set_turbo_scale (lte_phy.h), 0 < scale <= 1.  1 launches the kernels
+// named; another value their scaled twins (k_turbo64_sc / k_turbo_sc for the
+// fixed and skip forms, k_turbo64_es_sc / k_turbo_es_sc for the early-stop and
+// windowed ones), max-log and mode TM_DEC1 only: hipErrorInvalidValue otherwise.
 int launch_turbo(hipStream_t s, void* blk, void* ckpt, uint32_t* bits, int K, int f1, int f2, int iters,
-                 int G, int mode, int f64, int ch);
+                 int G, int mode, int f64, int ch, double scale = 1.0);
 struct TurboJob {           // one CB slot of a batch: G groups of 64 code blocks of size K
   void* blk;                // float / double rows (lte_decoder.hip)
   void* ck;
@@ -328,7 +333,7 @@ struct TurboJobs {
 // skip set (max-log decoders, one group count for every job): group g's waves
 // return at once where skip[g] != 0 (k_turbo64_skip / k_turbo_skip)
 int launch_turbo_jobs(hipStream_t s, const TurboJob* jobs, int n, int iters, int mode, int f64,
-                      const uint32_t* skip = nullptr);
+                      const uint32_t* skip = nullptr, double scale = 1.0);
 // Full decode with CRC early termination (k_turbo64_es / k_turbo_es, max-log
 // only): a code block stops after the first iteration n >= 1 whose decisions
 // have CRC-24 remainder zero over all K bits (poly: CRC24A_POLY / CRC24B_POLY).
@@ -344,7 +349,7 @@ struct TurboWin {
 };
 constexpr uint32_t TURBO_UNDECIDED = 0xFFFFFFFFu;
 int launch_turbo_jobs_es(hipStream_t s, const TurboJob* jobs, uint32_t* const* used, const int* nv, int n, int iters,
-                         int f64, uint32_t poly, const TurboWin* win = nullptr);
+                         int f64, uint32_t poly, const TurboWin* win = nullptr, double scale = 1.0);
 // Early stop with the undecided blocks re-packed at the boundary `after`.
 // pk[i]: job i's packed arrays -- rows / checkpoints / decision words / counts
 // of cap groups laid out as the job's own (chunk width turbo_chunk(cap), so
@@ -367,7 +372,7 @@ enum { TURBO_RP_NONE = 0, TURBO_RP_PACKED = 1, TURBO_RP_INPLACE = 2 };
 inline int turbo_pack_cap(int64_t G) { return G > 4 ? (int)((G + 3) / 4) : 1; }
 int launch_turbo_jobs_es_repack(hipStream_t s, const TurboJob* jobs, uint32_t* const* used, const int* nv, int n,
                                 int iters, int f64, uint32_t poly, int after, const TurboPack* pk, uint32_t* counts,
-                                int64_t* info);
+                                int64_t* info, double scale = 1.0);
 // rate_dematching_turbo for any E (repeats summed in order): llr [ncb][E] -> out [ncb][n_out]
 int launch_rate_dematch(hipStream_t s, const double* llr, int E, int Ncb, int n_out, const int32_t* src0, int64_t ncb,
                         double* out);

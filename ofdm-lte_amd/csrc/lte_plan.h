@@ -178,6 +178,8 @@ struct Plan {
   std::vector<DBuf<uint32_t>> pk_decb, pk_used, pk_idx;
   DBuf<uint32_t> rp_cnt;
   std::vector<int64_t> rp_last;
+  // Extrinsic scaling of the decoders (lte_plan_set_turbo_scale): 1 = off
+  double turbo_scale = 1.0;
   // HARQ (lte_plan_create_harq).  tx_map / rx_map hold one map per distinct rv
   // of rv_seq back to back (n_re_bits entries each, hq_slot[rv] its index).
   // hq_round: the next lte_run's transmission; hq_done: last completed round

@@ -677,10 +677,11 @@ int lte_turbo_encode_host(int K, int64_t ncb, const uint8_t* bits, uint8_t* out)
 // (CRC24A_POLY / CRC24B_POLY), the iterations used per code block to es_used.
 // rp_after > 0: early stop with re-packing at that boundary (packed arrays of
 // turbo_pack_cap(G) groups), rp_info: undecided blocks, groups resumed, state.
+// scale: the extrinsic scaling (lte_plan_set_turbo_scale; 1: the unscaled kernels).
 template <class T>
 static int turbo_host_run(int K, int iters, int64_t ncb, const T* llr, const T* ls, const T* lp, const T* la,
                           int mode, uint8_t* bits, T* app, uint32_t es_poly = 0, uint8_t* es_used = nullptr,
-                          int rp_after = 0, int64_t* rp_info = nullptr) {
+                          int rp_after = 0, int64_t* rp_info = nullptr, double scale = 1.0) {
   int f1, f2;
   if (!qpp_lookup(K, &f1, &f2)) return fail(LTE_EINVAL, "Invalid interleaver size K=" + std::to_string(K));
   if (ncb < 0) return fail(LTE_EINVAL, "bad ncb");
@@ -738,9 +739,9 @@ static int turbo_host_run(int K, int iters, int64_t ncb, const T* llr, const T* 
   const int nv = (int)ncb;
   if (hipMemcpy(db.p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess ||
       (rp_after > 0 ? launch_turbo_jobs_es_repack(nullptr, &job, &dused.p, &nv, 1, iters, f64, es_poly, rp_after, &pk,
-                                                  pcnt.p, rp_info)
-       : es_used    ? launch_turbo_jobs_es(nullptr, &job, &dused.p, &nv, 1, iters, f64, es_poly)
-                    : launch_turbo_jobs(nullptr, &job, 1, iters, mode, f64)) ||
+                                                  pcnt.p, rp_info, scale)
+       : es_used    ? launch_turbo_jobs_es(nullptr, &job, &dused.p, &nv, 1, iters, f64, es_poly, nullptr, scale)
+                    : launch_turbo_jobs(nullptr, &job, 1, iters, mode, f64, nullptr, scale)) ||
       hipDeviceSynchronize() != hipSuccess)
     rc = fail(LTE_EHIP, std::string("turbo failed: ") + hipGetErrorString(hipGetLastError()));
   if (rc == LTE_OK && es_used) {
@@ -840,6 +841,55 @@ int lte_turbo_decode_host(int K, int iters, int64_t ncb, const float* llr, uint8
 int lte_turbo_decode_host64(int K, int iters, int64_t ncb, const double* llr, uint8_t* bits) {
   if (iters < 0 || (ncb > 0 && (!llr || !bits))) return fail(LTE_EINVAL, "bad arguments");
   return turbo_host_run<double>(K, iters, ncb, llr, nullptr, nullptr, nullptr, TM_DEC1, bits, nullptr);
+}
+
+// the scaled entries' check of the factor, before the device is touched
+static int turbo_scale_arg(double scale) {
+  if (!(scale > 0.0 && scale <= 1.0)) return fail(LTE_EINVAL, "turbo scale must be in (0, 1]");
+  if (scale != 1.0 && logmap_on())
+    return fail(LTE_EUNSUP, "extrinsic scaling runs the max-log decoders only (set_decoder_mode(True))");
+  return LTE_OK;
+}
+
+int lte_turbo_decode_scaled_host(int K, int iters, int64_t ncb, const float* llr, double scale, uint8_t* bits) {
+  if (iters < 0 || (ncb > 0 && (!llr || !bits))) return fail(LTE_EINVAL, "bad arguments");
+  if (const int rc = turbo_scale_arg(scale)) return rc;
+  if (logmap_on()) return fail(LTE_EUNSUP, "exact log-MAP runs in float64 only (the f32 decoder is max-log)");
+  return turbo_host_run<float>(K, iters, ncb, llr, nullptr, nullptr, nullptr, TM_DEC1, bits, nullptr, 0, nullptr, 0,
+                               nullptr, scale);
+}
+
+int lte_turbo_decode_scaled_host64(int K, int iters, int64_t ncb, const double* llr, double scale, uint8_t* bits) {
+  if (iters < 0 || (ncb > 0 && (!llr || !bits))) return fail(LTE_EINVAL, "bad arguments");
+  if (const int rc = turbo_scale_arg(scale)) return rc;
+  return turbo_host_run<double>(K, iters, ncb, llr, nullptr, nullptr, nullptr, TM_DEC1, bits, nullptr, 0, nullptr, 0,
+                                nullptr, scale);
+}
+
+}  // extern "C"
+
+template <class T>
+static int turbo_es_scaled(int K, int iters, int64_t ncb, const T* llr, uint32_t crc_poly, double scale, int after,
+                           uint8_t* bits, uint8_t* iters_used, int64_t* info) {
+  uint32_t poly;
+  int rc = turbo_es_args(K, iters, ncb, llr, crc_poly, bits, iters_used, &poly);
+  if (!rc) rc = turbo_scale_arg(scale);
+  if (!rc && after != 0) rc = turbo_es_repack_args(iters, after, info);
+  if (rc) return rc;
+  return turbo_host_run<T>(K, iters, ncb, llr, nullptr, nullptr, nullptr, TM_DEC1, bits, nullptr, poly, iters_used,
+                           after, info, scale);
+}
+
+extern "C" {
+
+int lte_turbo_decode_es_scaled_host(int K, int iters, int64_t ncb, const float* llr, uint32_t crc_poly, double scale,
+                                    int after, uint8_t* bits, uint8_t* iters_used, int64_t* info) {
+  return turbo_es_scaled<float>(K, iters, ncb, llr, crc_poly, scale, after, bits, iters_used, info);
+}
+
+int lte_turbo_decode_es_scaled_host64(int K, int iters, int64_t ncb, const double* llr, uint32_t crc_poly, double scale,
+                                      int after, uint8_t* bits, uint8_t* iters_used, int64_t* info) {
+  return turbo_es_scaled<double>(K, iters, ncb, llr, crc_poly, scale, after, bits, iters_used, info);
 }
 
 int lte_bcjr_host(int K, int64_t ncb, const float* ls, const float* lp, const float* la, float* app) {

@@ -89,6 +89,8 @@ _SIGS = {
     'lte_plan_early_stop_repack': (ctypes.c_int, [ctypes.c_void_p]),
     'lte_plan_repack_info': (ctypes.c_int, [ctypes.c_void_p, P(c_i64), ctypes.c_int]),
     'lte_plan_turbo_iters_used': (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_uint8), c_i64]),
+    'lte_plan_set_turbo_scale': (ctypes.c_int, [ctypes.c_void_p, c_f64]),
+    'lte_plan_turbo_scale': (c_f64, [ctypes.c_void_p]),
     'lte_plan_create_harq': (ctypes.c_int, [P(PlanDesc), P(HarqDesc), P(ctypes.c_void_p)]),
     'lte_plan_harq_set_round': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'lte_plan_harq_tx_used': (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_uint8), c_i64]),
@@ -131,6 +133,16 @@ _SIGS = {
                                                          P(c_i64)]),
     'lte_turbo_decode_es_repack_host': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i64, P(ctypes.c_float),
                                                        ctypes.c_uint32, ctypes.c_int, P(ctypes.c_uint8),
+                                                       P(ctypes.c_uint8), P(c_i64)]),
+    'lte_turbo_decode_scaled_host64': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i64, P(c_f64), c_f64,
+                                                      P(ctypes.c_uint8)]),
+    'lte_turbo_decode_scaled_host': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i64, P(ctypes.c_float), c_f64,
+                                                    P(ctypes.c_uint8)]),
+    'lte_turbo_decode_es_scaled_host64': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i64, P(c_f64), ctypes.c_uint32,
+                                                         c_f64, ctypes.c_int, P(ctypes.c_uint8), P(ctypes.c_uint8),
+                                                         P(c_i64)]),
+    'lte_turbo_decode_es_scaled_host': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, c_i64, P(ctypes.c_float),
+                                                       ctypes.c_uint32, c_f64, ctypes.c_int, P(ctypes.c_uint8),
                                                        P(ctypes.c_uint8), P(c_i64)]),
     'lte_bcjr_host64': (ctypes.c_int, [ctypes.c_int, c_i64, P(c_f64), P(c_f64), P(c_f64), P(c_f64)]),
     'lte_crc_host': (ctypes.c_int, [c_i64, P(ctypes.c_uint8), ctypes.c_uint32, ctypes.c_int,
@@ -343,6 +355,34 @@ def sfbc_decode(rx, H0, H1, regularization=1e-10):
                                         ptr(h1.view(np.float64), F64), float(regularization),
                                         ptr(out.view(np.float64), F64)))
     return out
+
+
+def turbo_decode_scaled(llr, K, iters, scale, precision=None):
+    """lte_turbo_decode_scaled_host64 / _host: llr [ncb, 3K + 12] -> bits [ncb, K]."""
+    device_init()
+    prec = precision_of(precision)
+    _, rdt, ct = _cdtype(prec)
+    l = np.ascontiguousarray(llr, dtype=rdt).reshape(-1, 3 * int(K) + 12)
+    bits = np.empty((len(l), int(K)), dtype=np.uint8)
+    f = load().lte_turbo_decode_scaled_host64 if prec == 'f64' else load().lte_turbo_decode_scaled_host
+    check(f(int(K), int(iters), len(l), ptr(l, ct), float(scale), ptr(bits, U8)))
+    return bits
+
+
+def turbo_decode_es_scaled(llr, K, iters, crc_poly, scale, after=0, precision=None):
+    """lte_turbo_decode_es_scaled_host64 / _host: (bits [ncb, K], iters_used [ncb],
+    info [3] or None for after = 0)."""
+    device_init()
+    prec = precision_of(precision)
+    _, rdt, ct = _cdtype(prec)
+    l = np.ascontiguousarray(llr, dtype=rdt).reshape(-1, 3 * int(K) + 12)
+    bits = np.empty((len(l), int(K)), dtype=np.uint8)
+    used = np.empty(len(l), dtype=np.uint8)
+    info = np.zeros(3, dtype=np.int64) if after else None
+    f = load().lte_turbo_decode_es_scaled_host64 if prec == 'f64' else load().lte_turbo_decode_es_scaled_host
+    check(f(int(K), int(iters), len(l), ptr(l, ct), int(crc_poly), float(scale), int(after), ptr(bits, U8),
+            ptr(used, U8), ptr(info, c_i64)))
+    return bits, used, info
 
 
 precision = precision_of   # short alias used by the coding entry points

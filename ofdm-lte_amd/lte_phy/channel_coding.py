@@ -334,6 +334,20 @@ def turbo_decode_early_stop(llr, K, max_iterations=8, crc='24B', *, precision=No
     return (bits[0], int(used[0])) if a.ndim == 1 else (bits, used)
 
 
+def turbo_decode_scaled(llr, K, num_iterations=8, scale=0.75):
+    """Turbo decode with extrinsic scaling, scaled max-log-MAP, on the GPU in
+    float64 (not a reference name, so not in __all__): turbo_decode with every
+    half-iteration's extrinsic multiplied by `scale`, 0 < scale <= 1, before it
+    is passed on (lte_plan_set_turbo_scale in lte_phy.h has the definition;
+    scale = 1 is turbo_decode).  llr [3K+12] -> bits [K], or a batch
+    [ncb][3K+12] -> bits [ncb, K] as turbo_decode_batch."""
+    from .engine import turbo_scale_value
+    s = turbo_scale_value(scale)   # ValueError before any device call
+    a = np.asarray(llr)
+    bits = C.turbo_decode_scaled(a, K, num_iterations, s, 'f64')
+    return bits[0] if a.ndim == 1 else bits
+
+
 class LogMAPDecoder:
     """turbo_decoder.py:118-335: one BCJR pass of the 8-state RSC over any
     length (tail steps included), float64 on the GPU (lte_bcjr_host64), max*

@@ -52,12 +52,24 @@ def repack_boundary(repack, early_stop, turbo_iters):
     return after
 
 
+def turbo_scale_value(scale):
+    """The extrinsic scale a turbo_scale= keyword stands for (None: 1.0, off),
+    checked to lie in (0, 1].  Raises ValueError; touches no device."""
+    if scale is None:
+        return 1.0
+    s = float(scale)
+    if not 0.0 < s <= 1.0:   # (NaN fails both comparisons)
+        raise ValueError(f'turbo_scale must satisfy 0 < scale <= 1 (got {scale!r})')
+    return s
+
+
 class Plan:
     def __init__(self, *, N, Nc, cp_len, bps, n_sym, chain, channel, num_rx=1, delays=(), gains=(), fD=0.0,
                  fs=0.0, n_bits, turbo_iters=8, max_frames=1, cell_id=0, num_tx=1, rank=0, detector=0,
                  precoder=(), sc_fdm=0, bf_adaptive=0, no_equalization=0, precision=None, early_stop=False,
-                 harq=None, repack=None):
+                 harq=None, repack=None, turbo_scale=None):
         after = repack_boundary(repack, early_stop, turbo_iters)   # before any device call
+        scale = turbo_scale_value(turbo_scale)                     # likewise
         C.device_init()
         d = C.PlanDesc()
         d.N, d.Nc, d.cp_len, d.bps, d.n_sym = N, Nc, cp_len, bps, n_sym
@@ -144,6 +156,9 @@ class Plan:
         self.repack = 0
         if after:
             self.set_repack(after)
+        # extrinsic scaling of the decoders (lte_plan_set_turbo_scale; coded chains only; 1.0: off)
+        if scale != 1.0:
+            self.set_turbo_scale(scale)
 
     def __del__(self):
         try:
@@ -191,6 +206,16 @@ class Plan:
         t = v[2:].reshape(self.n_cb, 3)
         return {'after': int(v[0]), 'n_cb': int(v[1]), 'undecided': [int(x) for x in t[:, 0]],
                 'groups': [int(x) for x in t[:, 1]], 'state': [REPACK_STATES[int(x)] for x in t[:, 2]]}
+
+    # ------------------------------------------------------------------ extrinsic scaling
+    def set_turbo_scale(self, scale):
+        """Scale the decoders' extrinsic by `scale`, 0 < scale <= 1 (scaled
+        max-log-MAP; lte_plan_set_turbo_scale); None or 1 switches it off."""
+        C.check(C.load().lte_plan_set_turbo_scale(self.h, turbo_scale_value(scale)))
+
+    @property
+    def turbo_scale(self):
+        return float(C.load().lte_plan_turbo_scale(self.h))
 
     # ------------------------------------------------------------------ HARQ
     def harq_round(self, t):
@@ -362,7 +387,9 @@ _CACHE: "OrderedDict[tuple, Plan]" = OrderedDict()
 _CACHE_MAX = 8
 
 
-def get_plan(**kw):
+def plan_key(**kw):
+    """get_plan's cache key for these Plan keywords, and the keywords with their
+    defaults resolved (no device call)."""
     kw['precision'] = C.precision_of(kw.get('precision'))   # resolved now: part of the cache key
     kw['early_stop'] = bool(kw.get('early_stop', False))   # likewise: an early-stop plan is never a fixed one
     # likewise the re-packing boundary (True and its default are one plan)
@@ -370,7 +397,13 @@ def get_plan(**kw):
     hq = kw.get('harq')   # likewise, as a sorted tuple of its settings (None: a plain plan)
     kw['harq'] = None if hq is None else tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple, np.ndarray)) else v)
                                                       for k, v in dict(hq).items()))
+    kw['turbo_scale'] = turbo_scale_value(kw.get('turbo_scale'))   # likewise (None and 1 are one plan)
     key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple, np.ndarray)) else v) for k, v in kw.items()))
+    return key, kw
+
+
+def get_plan(**kw):
+    key, kw = plan_key(**kw)
     p = _CACHE.get(key)
     if p is None:
         p = Plan(**dict(kw, harq=None if kw['harq'] is None else dict(kw['harq'])))

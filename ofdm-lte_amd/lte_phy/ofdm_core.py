@@ -499,6 +499,11 @@ class OFDMSimulator:
     """OFDMSimulator (core/ofdm_core.py:560-2486): SISO, SISO+turbo and SIMO-MRC
     on the GPU, plus the device-resident Monte-Carlo grid `run_grid`."""
     _repack = 0   # the grid drivers' re-packing boundary while one runs (_takes_repack)
+    # Extrinsic scaling of the turbo decoders (not in the reference; scaled
+    # max-log-MAP, lte_plan_set_turbo_scale in include/lte_phy.h): every coded
+    # driver of a simulator decodes with this scale, 0 < scale <= 1; 1.0 is off
+    # (the reference's decoder).  Set it on an instance: sim.turbo_scale = 0.75.
+    turbo_scale = 1.0
 
     def __init__(self, config: Optional[LTEConfig] = None, channel_type: str = 'awgn', mode: str = 'lte',
                  enable_sc_fdm: bool = False, enable_equalization: bool = True, num_channels: int = 1,
@@ -550,7 +555,8 @@ class OFDMSimulator:
                         chain=chain, channel=ch.kind, num_rx=num_rx, delays=tuple(ch.delays),
                         gains=tuple(ch.gains), fD=ch.fD, fs=cfg.fs, n_bits=n_bits, turbo_iters=iters,
                         max_frames=max_frames, sc_fdm=sc, no_equalization=noeq, precision=self.precision,
-                        early_stop=early_stop, harq=harq, detector=detector, repack=repack)
+                        early_stop=early_stop, harq=harq, detector=detector, repack=repack,
+                        turbo_scale=self.turbo_scale if C.chain_info(chain).coded else None)
 
     def _ref_draws(self, L, num_rx=1):
         """Exactly the global-RNG consumption of one reference simulate_* call:
@@ -770,7 +776,7 @@ class OFDMSimulator:
                         chain=C.CHAIN_SFBC_CODED if coded else C.CHAIN_SFBC, channel=ch.kind, num_rx=num_rx,
                         num_tx=2, delays=tuple(ch.delays), gains=tuple(ch.gains), fD=ch.fD, fs=cfg.fs,
                         n_bits=n_bits, turbo_iters=iters, max_frames=max_frames, precision=self.precision,
-                        early_stop=early_stop, repack=repack)
+                        early_stop=early_stop, repack=repack, turbo_scale=self.turbo_scale if coded else None)
 
     def _simulate_sfbc(self, bits, snr_db, num_rx, mode):
         """simulate_miso (core/ofdm_core.py:1850-2047) / simulate_mimo (:2049-2258)
@@ -967,7 +973,8 @@ class OFDMSimulator:
                                  0 if coded else int(np.ceil(nb / (self.Nd * cfg.bits_per_symbol))), nb,
                                  frames_per_call, num_tx=sp['num_tx'], num_rx=sp['num_rx'], rank=sp['rank'],
                                  detector=DETECTORS[sp['detector'].upper()], W=W, precision=self.precision,
-                                 coded=coded, turbo_iters=turbo_iters, early_stop=early_stop, repack=repack)[0]
+                                 coded=coded, turbo_iters=turbo_iters, early_stop=early_stop, repack=repack,
+                                 turbo_scale=self.turbo_scale)[0]
         elif mimo == 'beamforming':
             from .beamforming import bf_plan
             bfo = {'num_tx': 4, 'num_rx': 1, 'update_mode': 'adaptive'}
@@ -1093,7 +1100,7 @@ def _harq_grid(sim, snr_range, num_trials, seed, n_bits, coded_bits, max_tx, rv_
 
 def _spatial_plan(config, channel_type, itu_profile, velocity_kmh, frequency_ghz, n_sym, n_bits, max_frames=1,
                   num_tx=4, num_rx=4, rank=4, detector=C.DET_MMSE, W=None, precision=None, coded=False,
-                  turbo_iters=8, early_stop=False, repack=None):
+                  turbo_iters=8, early_stop=False, repack=None, turbo_scale=None):
     ch = {'awgn': C.CH_AWGN, 'rayleigh_mp': C.CH_RAYLEIGH}.get(channel_type)
     if ch is None:
         raise ValueError(f"Tipo de canal desconocido: {channel_type}")
@@ -1109,7 +1116,7 @@ def _spatial_plan(config, channel_type, itu_profile, velocity_kmh, frequency_ghz
     Wt = tuple(complex(v) for v in np.asarray(W, dtype=complex).ravel())
     # coded: LTE_CHAIN_SPATIAL_CODED (n_sym 0: it follows from the coded length)
     kw = dict(chain=C.CHAIN_SPATIAL_CODED, turbo_iters=int(turbo_iters), early_stop=early_stop,
-              repack=repack) if coded else \
+              repack=repack, turbo_scale=turbo_scale) if coded else \
         dict(chain=C.CHAIN_SPATIAL)
     return get_plan(N=config.N, Nc=config.Nc, cp_len=config.cp_length, bps=config.bits_per_symbol, n_sym=n_sym,
                     channel=ch, num_rx=num_rx, num_tx=num_tx, delays=tuple(delays),

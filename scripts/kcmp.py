@@ -41,12 +41,12 @@ def code_object(path, tmp, tag):
 
 
 def data_symbols(co):
-    """Sorted (address, name) of the code object's data symbols (constant tables)."""
+    """Sorted (address, name, size) of the code object's data symbols (constant tables)."""
     syms = set()
     for line in tool('llvm-readelf', '-s', '--wide', co).splitlines():
         f = line.split()
         if len(f) == 8 and f[3] == 'OBJECT' and f[6].isdigit():
-            syms.add((int(f[1], 16), f[7]))
+            syms.add((int(f[1], 16), f[7], int(f[2], 0)))
     return sorted(syms)
 
 
@@ -55,7 +55,10 @@ def bodies(co):
 
     Addresses are dropped.  A pc-relative reference to constant data (getpc,
     then an add of a 32-bit literal to the low register) moves with the layout
-    of the code object, so its literal is rewritten as table + offset."""
+    of the code object, so its literal is rewritten as table + offset.  The
+    same sequence with a target in no table is a long branch inside the kernel
+    (the f64 decoders are long enough to need them): its literal is relative
+    to the kernel's own code and stays as it is."""
     syms = data_symbols(co)
     out, name, h, pcs = {}, None, None, {}
     for line in tool('llvm-objdump', '-d', '--no-show-raw-insn', '--no-leading-addr', co).splitlines():
@@ -76,7 +79,7 @@ def bodies(co):
             imm = int(m.group(3), 16)
             target = pcs.pop(m.group(1)) + (imm - (1 << 32) if imm >> 31 else imm)
             i = bisect.bisect_right(syms, (target, '\uffff'))
-            if i:
+            if i and target < syms[i - 1][0] + syms[i - 1][2]:
                 ins = f's_add_u32 {m.group(1)}, {m.group(2)}, {syms[i - 1][1]}+{target - syms[i - 1][0]}'
         h.update(ins.encode() + b'\n')
     return {k: v.hexdigest() for k, v in out.items()}
