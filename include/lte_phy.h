@@ -484,9 +484,25 @@ int lte_hard_host64(int bps, int64_t n, const double *syms, uint8_t *bits);
 int lte_rsc_encode_host(int64_t n, const uint8_t *bits, int termination, uint8_t *systematic, uint8_t *parity);
 /* Turbo encode: turbo_encode core/channel_coding/turbo_encoder.py:214-313 */
 int lte_turbo_encode_host(int K, int64_t ncb, const uint8_t *bits, uint8_t *out /*[ncb][3K+12]*/);
-/* Turbo decode: turbo_decode core/channel_coding/turbo_decoder.py:338-450 */
+/* Turbo decode: turbo_decode core/channel_coding/turbo_decoder.py:338-450
+ *
+ * The LLR domain of the float32 decoders (this entry, lte_bcjr_host and the
+ * float32 _es, _es_repack, _scaled and _es_scaled entries below, and every
+ * float32 plan): their start metrics are -1e30 (about -2^99.7), not -inf, so
+ * they are defined only while metric magnitudes stay far below 1e30.
+ * max-log-MAP is scale-invariant, and on LLRs of unit scale (|LLR| <= 16) the
+ * float32 decisions are unchanged by a factor 2^k for -120 <= k <= 92; at
+ * k = 96 sums of LLRs reach the sentinel, an unreachable state wins a max, and
+ * decisions change (tests/test_exact_llr_host.py
+ * measures the exponent; tests/test_gpu_exact_llr.py checks |k| = 64 on the
+ * device).  So keep |LLR| below about 1e28 (2^93), and non-zero |LLR| above
+ * about 1e-35 (2^-116), where float32 runs out of normal numbers.  Nothing
+ * clamps: LLRs outside that range decode to garbage without an error.  The
+ * float64 decoders start at -inf and have no such limit short of overflow
+ * (checked at 2^+-200). */
 int lte_turbo_decode_host(int K, int iters, int64_t ncb, const float *llr /*[ncb][3K+12]*/, uint8_t *bits);
-/* One max-log BCJR pass, a-posteriori output: LogMAPDecoder.decode turbo_decoder.py:181-278 */
+/* One max-log BCJR pass, a-posteriori output: LogMAPDecoder.decode turbo_decoder.py:181-278
+ * (float32: the LLR domain at lte_turbo_decode_host) */
 int lte_bcjr_host(int K, int64_t ncb, const float *ls, const float *lp, const float *la, float *app);
 /* float64 turbo decode, bit-exact with turbo_decode (core/channel_coding/turbo_decoder.py:338-450):
  * the reference's unnormalised max-log recursion in its own operation order. */
@@ -496,7 +512,9 @@ int lte_turbo_decode_host64(int K, int iters, int64_t ncb, const double *llr /*[
  * crc_poly 0x1864CFB (gCRC24A) or 0x1800063 (gCRC24B); bits [ncb][K] = D(n*),
  * iters_used [ncb] = n*.  K outside the 188 sizes, iters < 0, another
  * crc_poly or a NULL pointer: LTE_EINVAL before the device is touched.
- * LTE_EUNSUP under lte_set_decoder_mode(0). */
+ * LTE_EUNSUP under lte_set_decoder_mode(0).  The float32 entries, here and in
+ * the re-packing and scaled forms below, have the float32 decoder's LLR domain
+ * (lte_turbo_decode_host: |LLR| below about 1e28). */
 int lte_turbo_decode_es_host64(int K, int iters, int64_t ncb, const double *llr /*[ncb][3K+12]*/, uint32_t crc_poly,
                                uint8_t *bits, uint8_t *iters_used);
 int lte_turbo_decode_es_host(int K, int iters, int64_t ncb, const float *llr /*[ncb][3K+12]*/, uint32_t crc_poly,
@@ -513,7 +531,8 @@ int lte_turbo_decode_es_repack_host(int K, int iters, int64_t ncb, const float *
 /* The turbo decode entries with extrinsic scaling (lte_plan_set_turbo_scale):
  * layouts and checks of lte_turbo_decode_host64 / _host.  A scale that is NaN
  * or outside (0, 1]: LTE_EINVAL; a scale other than 1 under
- * lte_set_decoder_mode(0): LTE_EUNSUP.  scale = 1 is the unscaled entry. */
+ * lte_set_decoder_mode(0): LTE_EUNSUP.  scale = 1 is the unscaled entry.
+ * float32: the LLR domain at lte_turbo_decode_host. */
 int lte_turbo_decode_scaled_host64(int K, int iters, int64_t ncb, const double *llr /*[ncb][3K+12]*/, double scale,
                                    uint8_t *bits);
 int lte_turbo_decode_scaled_host(int K, int iters, int64_t ncb, const float *llr /*[ncb][3K+12]*/, double scale,

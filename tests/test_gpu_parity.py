@@ -161,9 +161,12 @@ def test_turbo_decode_golden(C, golden, oracle, K, its):
 
 @pytest.mark.parametrize('K,its', [(40, 8), (1024, 1), (1024, 8), (5568, 2)])
 def test_turbo_decode_golden_f32(C, golden, oracle, K, its):
-    """f32 fast mode == its float32 algorithm bit-for-bit (how that algorithm
-    relates to the float64 reference is pinned on the CPU:
-    tests/test_turbo_model.py)."""
+    """f32 fast mode == its float32 algorithm bit-for-bit.  How that algorithm
+    relates to the float64 reference: exactly equal on exact-input LLRs, below
+    the cliff too (tests/test_exact_llr_host.py for the model,
+    tests/test_gpu_exact_llr.py for the kernels themselves); on continuous
+    LLRs equal where the decoder converges and statistically close where it
+    does not (tests/test_turbo_model.py)."""
     from lte_phy import channel_coding as cc
     key = f'td_{K}_{its}'
     llr = golden[key + '_llr'].astype(np.float32)

@@ -1,6 +1,6 @@
-"""CPU: pins the GPU decoder's float32 model (oracle or_turbo_decode_f32,
-the algorithm k_turbo implements bit-for-bit -- see test_gpu_parity.py)
-against the reference decoder (turbo_decoder.py:338-450).
+"""CPU: relates the GPU decoder's float32 model (oracle or_turbo_decode_f32,
+the algorithm k_turbo implements bit-for-bit -- see test_gpu_parity.py) to the
+reference decoder (turbo_decoder.py:338-450) on continuous Gaussian LLRs.
 
   * converging cases: identical decisions to the reference's golden output and
     to the float64 oracle;
@@ -8,6 +8,11 @@ against the reference decoder (turbo_decoder.py:338-450).
     converging below about 3.5 dB SNR on these BPSK LLRs), float round-off decides
     which wrong bits come out; there the f32 model's error rate vs the sent
     code block must agree with the reference's within 0.05.
+
+Below the cliff that is a statistical band, not a pin.  The exact tie is
+tests/test_exact_llr_host.py: on LLRs on a power-of-two grid the float32 model
+must give the reference's decisions on every block after every iteration, and
+tests/test_gpu_exact_llr.py holds the float32 kernels to the same reference.
 """
 import numpy as np
 import pytest
