@@ -67,13 +67,29 @@ def csi_feedback(H, num_tx, codebook_type='TM6', noise_variance=1.0):
     return {'pmi': pmi, 'cqi': cqi, 'ri': ri, 'sinr_db': sinr_db, 'precoder': W}
 
 
+def beamforming_draws(num_tx, num_rx, n_sym, Nd):
+    """The random numbers simulate_beamforming consumes from the global RNG, in
+    its order: randn(rx, tx) x 2 for H, then per OFDM symbol randn(rx, Nd) x 2
+    (unit scale; scaled at use) -> {'H', 'z_re' [rx, n_sym * Nd], 'z_im'}."""
+    H = (np.random.randn(num_rx, num_tx) + 1j * np.random.randn(num_rx, num_tx)) / np.sqrt(2)
+    z_re = np.empty((num_rx, n_sym * Nd))
+    z_im = np.empty((num_rx, n_sym * Nd))
+    for i in range(n_sym):
+        z_re[:, i * Nd:(i + 1) * Nd] = np.random.randn(num_rx, Nd)
+        z_im[:, i * Nd:(i + 1) * Nd] = np.random.randn(num_rx, Nd)
+    return {'H': H, 'z_re': z_re, 'z_im': z_im}
+
+
 def simulate_beamforming(num: Numerology, bits, snr_db, num_tx=2, num_rx=1, codebook_type='TM6',
-                         update_mode='adaptive'):
+                         update_mode='adaptive', draws=None):
     """OFDMSimulator.simulate_beamforming (core/ofdm_core.py:2260-2477), in the
     reference's global-RNG order: H = (randn + j randn)/sqrt 2 [num_rx, num_tx];
     per OFDM symbol: PMI feedback; W = codebook precoder (static) or MRT of H
     (adaptive); x = W s; y = H x + noise (randn(rx, Nd) + j randn(rx, Nd)) *
-    sqrt(s2/2), s2 = 10^(-SNR/10); MRC with H_eff = H W; nearest-point bits."""
+    sqrt(s2/2), s2 = 10^(-SNR/10); MRC with H_eff = H W; nearest-point bits.
+    draws (beamforming_draws' format; philox.bf_draws for the device's Philox
+    mode): H and the unit normals of the noise, symbol-major, instead of the
+    global RNG (which is then left untouched)."""
     bits = np.asarray(bits)
     n0 = len(bits)
     Nd = len(num.data_idx)
@@ -81,7 +97,10 @@ def simulate_beamforming(num: Numerology, bits, snr_db, num_tx=2, num_rx=1, code
     n_sym = int(np.ceil(n0 / bpo))
     bp = np.concatenate([bits, np.zeros(n_sym * bpo - n0, dtype=int)]) if n0 < n_sym * bpo else bits
     q = bits_to_symbols(bp, num.modulation)
-    H = (np.random.randn(num_rx, num_tx) + 1j * np.random.randn(num_rx, num_tx)) / np.sqrt(2)
+    if draws is None:
+        H = (np.random.randn(num_rx, num_tx) + 1j * np.random.randn(num_rx, num_tx)) / np.sqrt(2)
+    else:
+        H = np.asarray(draws['H'], dtype=complex).reshape(num_rx, num_tx)
     s2 = 10 ** (-snr_db / 10)
     rx_all, gains, pmis = [], [], []
     W = None
@@ -100,7 +119,11 @@ def simulate_beamforming(num: Numerology, bits, snr_db, num_tx=2, num_rx=1, code
         for r in range(num_rx):
             for t in range(num_tx):
                 y[r, :] += H[r, t] * x[t, :]
-        z = (np.random.randn(num_rx, Nd) + 1j * np.random.randn(num_rx, Nd)) * np.sqrt(s2 / 2)
+        if draws is None:
+            z = (np.random.randn(num_rx, Nd) + 1j * np.random.randn(num_rx, Nd)) * np.sqrt(s2 / 2)
+        else:
+            sl = slice(i * Nd, (i + 1) * Nd)
+            z = (draws['z_re'][:, sl] + 1j * draws['z_im'][:, sl]) * np.sqrt(s2 / 2)
         rx_all.append(y + z)
     He = H @ W
     eq = []

@@ -103,11 +103,22 @@ def mimo_estimate(num: Numerology, grids: np.ndarray, num_tx: int) -> np.ndarray
 
 # --------------------------------------------------------------------------
 # a12 OFDMChannel.transmit_mimo (core/ofdm_core.py:434-543)
-def transmit_mimo_draws(num_tx: int, num_rx: int, channel: str, L: int, profile='Pedestrian_A'):
+def _paths(num: Numerology, profile, paths, spatial=False):
+    """The links' taps: the ITU profile's (itu_paths), or paths = (integer
+    delays in samples, linear gains) taken as they are (a custom tap set, as
+    lte_oracle.channel_transmit's paths=)."""
+    if paths is None:
+        return itu_paths(num, profile, spatial=spatial)
+    return np.array([int(d) for d in paths[0]]), np.array([float(v) for v in paths[1]])
+
+
+def transmit_mimo_draws(num_tx: int, num_rx: int, channel: str, L: int, profile='Pedestrian_A', n_paths=None):
     """Random numbers transmit_mimo consumes, in order: per RX, per TX link
     [rayleigh: per path rand(16); link noise normal(L) x 2 at 100 dB], then the
-    RX noise normal(L) x 2 (unit scale; scaled at use)."""
-    n_paths = len(ITU_CHANNEL_MODELS[profile]['delays_us'])
+    RX noise normal(L) x 2 (unit scale; scaled at use).  n_paths: of a custom
+    tap set (default: the profile's)."""
+    if n_paths is None:
+        n_paths = len(ITU_CHANNEL_MODELS[profile]['delays_us'])
     out = []
     for _ in range(num_rx):
         links = []
@@ -123,15 +134,19 @@ def transmit_mimo_draws(num_tx: int, num_rx: int, channel: str, L: int, profile=
 
 
 def transmit_mimo(num: Numerology, xs, num_rx: int, channel: str, snr_db: float, profile='Pedestrian_A',
-                  draws=None):
+                  draws=None, paths=None, info=None):
     """OFDMChannel.transmit_mimo: awgn links h = exp(j tx pi/2) (h = 1 for tx 0);
     rayleigh links = a ChannelSimulator at 100 dB (fading + still-drawn link
     noise) with h estimated by power ratio and correlation phase; noise per RX
-    with power (P_rx / num_tx) / SNR (Q5)."""
+    with power (P_rx / num_tx) / SNR (Q5).  paths: custom tap set instead of
+    the profile's (_paths).  info (a dict): gets 'noise_power', the RX noise
+    power per RX."""
     num_tx = len(xs)
     L = len(xs[0])
+    npows = []
     if draws is None:
-        draws = transmit_mimo_draws(num_tx, num_rx, channel, L, profile)
+        draws = transmit_mimo_draws(num_tx, num_rx, channel, L, profile,
+                                    None if paths is None else len(paths[0]))
     ys = []
     Hm = np.zeros((num_rx, num_tx), dtype=complex)
     for r in range(num_rx):
@@ -152,7 +167,7 @@ def transmit_mimo(num: Numerology, xs, num_rx: int, channel: str, snr_db: float,
                 h = 1.0 + 0j if t == 0 else np.exp(1j * (t * np.pi / 2))
                 y = x * h
             else:
-                dl, g = itu_paths(num, profile)
+                dl, g = _paths(num, profile, paths)
                 d = draws[r]['links'][t]
                 y0 = multipath(x, dl, g, d['phases'], 0.0, num.fs)
                 p = np.mean(np.abs(y0) ** 2)
@@ -175,6 +190,7 @@ def transmit_mimo(num: Numerology, xs, num_rx: int, channel: str, snr_db: float,
             s2 = (pl / 10 ** (100.0 / 10)) / 2
             sp = np.mean(np.abs(acc) ** 2) + 2.0 * s2
             npow = 2.0 * s2 + (sp / num_tx) / 10 ** (snr_db / 10)
+            npows.append(npow)
             s = np.sqrt(npow / 2)
             ys.append(acc + (s * draws[r]['z_re'] + 1j * (s * draws[r]['z_im'])))
             continue
@@ -184,18 +200,23 @@ def transmit_mimo(num: Numerology, xs, num_rx: int, channel: str, snr_db: float,
             acc = acc + (s * z0['z_re'] + 1j * (s * z0['z_im']))
         sp = np.mean(np.abs(acc) ** 2)
         npow = (sp / num_tx) / 10 ** (snr_db / 10)
+        npows.append(npow)
         s = np.sqrt(npow / 2)
         ys.append(acc + (s * draws[r]['z_re'] + 1j * (s * draws[r]['z_im'])))
+    if info is not None:
+        info['noise_power'] = np.array(npows)
     return ys, Hm
 
 
 # --------------------------------------------------------------------------
 # a13 ChannelSimulator.transmit_spatial_multiplexing (core/channel.py:397-493)
-def transmit_sm_draws(num_tx: int, num_rx: int, channel: str, L: int, profile='Pedestrian_A'):
+def transmit_sm_draws(num_tx: int, num_rx: int, channel: str, L: int, profile='Pedestrian_A', n_paths=None):
     """Draw order: rayleigh_mp: per (rx, tx) link: filter per path rand(16),
     then impulse_response per path rand(16); then per RX normal(L) x 2.
-    awgn: per (rx, tx) normal() re, normal() im (CN(0,1)); then noise."""
-    n_paths = len(ITU_CHANNEL_MODELS[profile]['delays_us'])
+    awgn: per (rx, tx) normal() re, normal() im (CN(0,1)); then noise.
+    n_paths: of a custom tap set (default: the profile's)."""
+    if n_paths is None:
+        n_paths = len(ITU_CHANNEL_MODELS[profile]['delays_us'])
     links = []
     for _ in range(num_rx):
         row = []
@@ -214,22 +235,25 @@ def transmit_sm_draws(num_tx: int, num_rx: int, channel: str, L: int, profile='P
 
 
 def transmit_sm(num: Numerology, xs, num_rx: int, channel: str, snr_db: float, profile='Pedestrian_A',
-                fD=None, draws=None):
+                fD=None, draws=None, paths=None, info=None):
     """Rayleigh: per link RayleighChannel with the gains converted a third time
     (Q2) and fD from 3 km/h @ 2 GHz by default (Q3); channel_matrix = first
-    impulse-response tap.  Noise per RX: P / SNR (no /num_tx here)."""
+    impulse-response tap.  Noise per RX: P / SNR (no /num_tx here).  paths:
+    custom tap set instead of the profile's thrice-converted one (_paths).
+    info (a dict): gets 'noise_power', the noise power per RX."""
     num_tx = len(xs)
     L = min(len(x) for x in xs)
     xs = [np.asarray(x)[:L] for x in xs]
     if fD is None:
         fD = doppler_hz(2.0, 3)
     if draws is None:
-        draws = transmit_sm_draws(num_tx, num_rx, channel, L, profile)
+        draws = transmit_sm_draws(num_tx, num_rx, channel, L, profile, None if paths is None else len(paths[0]))
     ys = [np.zeros(L, dtype=complex) for _ in range(num_rx)]
     Hm = np.zeros((num_rx, num_tx), dtype=complex)
     snr_lin = 10 ** (snr_db / 10)
+    npows = []
     if channel == 'rayleigh_mp':
-        dl, g3 = itu_paths(num, profile, spatial=True)
+        dl, g3 = _paths(num, profile, paths, spatial=True)
         for r in range(num_rx):
             for t in range(num_tx):
                 d = draws['links'][r][t]
@@ -243,8 +267,11 @@ def transmit_sm(num: Numerology, xs, num_rx: int, channel: str, snr_db: float, p
                 ys[r] += hh * xs[t]
     for r in range(num_rx):
         p = np.mean(np.abs(ys[r]) ** 2)
+        npows.append(p / snr_lin)
         s = np.sqrt((p / snr_lin) / 2)
         ys[r] += s * draws['noise'][r]['z_re'] + 1j * (s * draws['noise'][r]['z_im'])
+    if info is not None:
+        info['noise_power'] = np.array(npows)
     return ys, Hm
 
 
@@ -308,7 +335,8 @@ def _papr_db(s):
 
 # --------------------------------------------------------------------------
 # G17 configs 4 / 5 end to end
-def simulate_sfbc(num: Numerology, bits, snr_db, num_rx=2, channel='awgn', profile='Pedestrian_A', draws=None):
+def simulate_sfbc(num: Numerology, bits, snr_db, num_rx=2, channel='awgn', profile='Pedestrian_A', draws=None,
+                  paths=None):
     """OFDMSimulator.simulate_miso (num_rx == 1, core/ofdm_core.py:1850-2047) /
     simulate_mimo (:2049-2258) with the Q19 estimator fix: per OFDM symbol QAM
     + SFBC encode + SFBC grid (pilot reseeds 0, 1) + IFFT/CP; transmit_mimo;
@@ -331,7 +359,9 @@ def simulate_sfbc(num: Numerology, bits, snr_db, num_rx=2, channel='awgn', profi
         s1.append(x1)
         pap0.append(_papr_db(x0))
         pap1.append(_papr_db(x1))
-    ys, Hm = transmit_mimo(num, [np.concatenate(s0), np.concatenate(s1)], num_rx, channel, snr_db, profile, draws)
+    info = {}
+    ys, Hm = transmit_mimo(num, [np.concatenate(s0), np.concatenate(s1)], num_rx, channel, snr_db, profile, draws,
+                           paths, info)
     grids, H0s, H1s = [], [], []
     for r in range(num_rx):
         gr = _fft_symbols(num, ys[r], len(ys[r]) // (num.N + num.cp))
@@ -344,10 +374,11 @@ def simulate_sfbc(num: Numerology, bits, snr_db, num_rx=2, channel='awgn', profi
         grids.append(gr)
         H0s.append(h0l)
         H1s.append(h1l)
-    out_bits = []
+    out_bits, combined = [], []
     for i in range(min(n_sym, len(grids[0]))):
         dec = [sfbc_decode(grids[r][i][d_idx], H0s[r][i][d_idx], H1s[r][i][d_idx]) for r in range(num_rx)]
         z = np.mean(dec, axis=0)
+        combined.append(z)
         c = constellation(num.modulation)
         det = c[nearest_indices(z, num.modulation)]
         out_bits.append(hard_bits(det, num.modulation))
@@ -355,11 +386,12 @@ def simulate_sfbc(num: Numerology, bits, snr_db, num_rx=2, channel='awgn', profi
     err = int(np.sum(bits[:n0] != rxb))
     p0, p1 = float(np.mean(pap0)), float(np.mean(pap1))
     return {'bits_received_array': rxb, 'bit_errors': err, 'ber': err / n0, 'channel_matrix': Hm,
-            'papr_db_tx0': p0, 'papr_db_tx1': p1, 'papr_db': float(np.mean([p0, p1])), 'signals_rx': ys}
+            'papr_db_tx0': p0, 'papr_db_tx1': p1, 'papr_db': float(np.mean([p0, p1])), 'signals_rx': ys,
+            'symbols_rx': np.concatenate(combined), 'noise_power': info['noise_power']}
 
 
 def simulate_spatial(num: Numerology, bits, snr_db, num_tx=4, num_rx=4, rank=4, channel='awgn',
-                     profile='Pedestrian_A', velocity_kmh=3, frequency_ghz=2.0, draws=None):
+                     profile='Pedestrian_A', velocity_kmh=3, frequency_ghz=2.0, draws=None, paths=None):
     """simulate_spatial_multiplexing (core/ofdm_core.py:2489-2815), fixed rank,
     TM4 PMI 0 (rank 4 -> W = I4): H_initial draw (always), per symbol QAM ->
     layers -> precode on the first ceil(Nd/rank) data SCs (Q20) -> CRS pilots
@@ -398,7 +430,7 @@ def simulate_spatial(num: Numerology, bits, snr_db, num_tx=4, num_rx=4, rank=4, 
             sig[t].append(_ofdm_time(num, grids[t]))
     xs = [np.concatenate(s) for s in sig]
     fD = doppler_hz(frequency_ghz, velocity_kmh)
-    ys, Hm = transmit_sm(num, xs, num_rx, channel, snr_db, profile, fD, None if draws is None else draws)
+    ys, Hm = transmit_sm(num, xs, num_rx, channel, snr_db, profile, fD, None if draws is None else draws, paths)
     per_rx = [_fft_symbols(num, ys[r], n_sym) for r in range(num_rx)]
     s2 = 10 ** (-snr_db / 10)
     out_bits = []
@@ -418,7 +450,7 @@ def simulate_spatial(num: Numerology, bits, snr_db, num_tx=4, num_rx=4, rank=4, 
 # Config 4: SFBC 2 x num_rx + the coding chain (the build's composition; the
 # reference has no function that composes them, SURVEY §8c / DESIGN.md §3a)
 def simulate_sfbc_coded(num: Numerology, bits, snr_db, num_rx=2, channel='rayleigh_mp', profile='Pedestrian_A',
-                        draws=None, iters=8):
+                        draws=None, iters=8, paths=None):
     """simulate_siso_coded's coding chain (core/ofdm_core.py:925-1338: CRC-24A,
     segmentation, turbo, rate matching, QAM, T/F interleaver) with cols = the
     SFBC REs per OFDM symbol (Nd & ~1, Q18) around simulate_mimo's SFBC link
@@ -452,7 +484,9 @@ def simulate_sfbc_coded(num: Numerology, bits, snr_db, num_rx=2, channel='raylei
         g0, g1 = sfbc_map_grid(num, t0, t1)
         s0.append(_ofdm_time(num, g0))
         s1.append(_ofdm_time(num, g1))
-    ys, Hm = transmit_mimo(num, [np.concatenate(s0), np.concatenate(s1)], num_rx, channel, snr_db, profile, draws)
+    info = {}
+    ys, Hm = transmit_mimo(num, [np.concatenate(s0), np.concatenate(s1)], num_rx, channel, snr_db, profile, draws,
+                           paths, info)
     grids, H0s, H1s = [], [], []
     for r in range(num_rx):
         gr = _fft_symbols(num, ys[r], n_sym)
@@ -490,4 +524,5 @@ def simulate_sfbc_coded(num: Numerology, bits, snr_db, num_rx=2, channel='raylei
     dec = np.pad(dec, (0, n0 - len(dec))) if len(dec) < n0 else dec[:n0]
     err = int(np.sum(bits != dec))
     return {'bits_received_array': dec, 'bit_errors': err, 'ber': err / n0, 'crc_pass': bool(ok),
-            'channel_matrix': Hm, 'symbols_rx': sd, 'noise_var': nd, 'llrs': L}
+            'channel_matrix': Hm, 'symbols_rx': sd, 'noise_var': nd, 'llrs': L, 'symbols_rx_grid': z,
+            'signals_rx': ys, 'noise_power': info['noise_power']}

@@ -203,6 +203,22 @@ def sm_draws(seed: int, frame: int, L: int, num_tx: int, num_rx: int, channel: s
     return {'links': links, 'noise': noise}
 
 
+def bf_draws(seed: int, frame: int, num_tx: int, num_rx: int, n_sym: int, Nd: int):
+    """simulate_beamforming's draws (bf_oracle.simulate_beamforming format) as
+    lte_bf.hip forms them: H[r, t] = the unit normal pair of outputs (x, y) of
+    counter 0 on STREAM_BF + r * num_tx + t, times 0.7071067811865475 (k_bf_setup);
+    the noise of RX r = samples 0 .. n_sym * Nd - 1 of STREAM_NOISE + r, sample
+    l * Nd + j for data RE j of OFDM symbol l (k_bf_data)."""
+    H = np.empty((num_rx, num_tx), dtype=complex)
+    for r in range(num_rx):
+        for t in range(num_tx):
+            v = rng4(seed, frame, STREAM_BF + r * num_tx + t, [0])
+            zr, zi = box_muller(v[0], v[1])
+            H[r, t] = complex(zr[0] * 0.7071067811865475, zi[0] * 0.7071067811865475)
+    z = [normals(seed, frame, STREAM_NOISE + r, n_sym * Nd) for r in range(num_rx)]
+    return {'H': H, 'z_re': np.stack([a for a, _ in z]), 'z_im': np.stack([b for _, b in z])}
+
+
 # --------------------------------------------------------------------------
 # Bench frames through the oracle
 BENCH_SEED = 0x5EED

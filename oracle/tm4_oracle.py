@@ -191,11 +191,12 @@ def _mmse(y, He, s2):
     return (Ai @ He.conj().T) @ y
 
 
-def _sic(y, He, s2, const):
+def _sic(y, He, s2, const, trace=None):
     """_sic_detect (:200-306): order by ||h_i||^2 / (sum_{j!=i} ||h_j||^2 + s2
     + 1e-10) descending (np.argsort()[::-1]); per layer MMSE over the
     remaining columns (1 column: vdot(h, y) / (||h||^2 + s2)), nearest
-    constellation point (first index on ties), cancel with the original column."""
+    constellation point (first index on ties), cancel with the original column.
+    trace (a list): gets (layer, slicer input) of every cancellation stage."""
     nl = He.shape[1]
     if const is None:
         return _mmse(y, He, s2)
@@ -221,6 +222,8 @@ def _sic(y, He, s2, const):
         else:
             A = Hr.conj().T @ Hr + s2 * np.eye(Hr.shape[1])
             sm = (np.linalg.inv(A) @ Hr.conj().T @ yr)[rel]
+        if trace is not None:
+            trace.append((int(lyr), complex(sm)))
         sh = const[np.argmin(np.abs(const - sm))]
         out[lyr] = sh
         yr = yr - He[:, lyr] * sh
@@ -232,8 +235,8 @@ def _sic(y, He, s2, const):
     return out
 
 
-def detect_one(det, y, H, s2, W, num_layers, const=None):
-    """_detect_single (:99-133)."""
+def detect_one(det, y, H, s2, W, num_layers, const=None, trace=None):
+    """_detect_single (:99-133).  trace: _sic's."""
     He = H @ W if W is not None else H[:, :num_layers]
     det = det.upper()
     if det in ('MMSE', 'IRC'):
@@ -241,7 +244,7 @@ def detect_one(det, y, H, s2, W, num_layers, const=None):
     if det == 'ZF':
         return np.linalg.pinv(He) @ y
     if det == 'SIC':
-        return _sic(y, He, s2, const)
+        return _sic(y, He, s2, const, trace)
     if det == 'MRC':
         if num_layers != 1:
             raise ValueError("MRC solo soporta num_layers=1 (rank-1)")
@@ -250,13 +253,18 @@ def detect_one(det, y, H, s2, W, num_layers, const=None):
     raise ValueError(f"Detector '{det}' no soportado")
 
 
-def detect(det, Y, H, s2, W, num_layers, const=None):
-    """MIMODetector.detect per subcarrier (:55-97): Y [rx, n], H [rx, tx, n]."""
+def detect(det, Y, H, s2, W, num_layers, const=None, trace=None):
+    """MIMODetector.detect per subcarrier (:55-97): Y [rx, n], H [rx, tx, n].
+    trace (a list): gets one list per subcarrier of _sic's (layer, slicer input)."""
     if Y.shape[0] < num_layers:
         raise ValueError(f"num_rx ({Y.shape[0]}) debe ser >= num_layers ({num_layers})")
     out = np.zeros((num_layers, Y.shape[1]), dtype=complex)
     for k in range(Y.shape[1]):
-        out[:, k] = detect_one(det, Y[:, k], H[:, :, k], s2, W, num_layers, const)
+        tk = None
+        if trace is not None:
+            tk = []
+            trace.append(tk)
+        out[:, k] = detect_one(det, Y[:, k], H[:, :, k], s2, W, num_layers, const, tk)
     return out
 
 
@@ -275,20 +283,41 @@ def choose_rank_pmi(num_tx, num_rx, rank, snr_db, csi):
 
 
 def simulate_tm4(num: Numerology, bits, snr_db, num_tx=4, num_rx=2, rank='adaptive', detector='MMSE',
-                 channel='awgn', profile='Pedestrian_A', velocity_kmh=3, frequency_ghz=2.0, csi=True):
+                 channel='awgn', profile='Pedestrian_A', velocity_kmh=3, frequency_ghz=2.0, csi=True,
+                 draws=None, pmi=None, paths=None):
     """The reference driver with its global-RNG order: H_initial -> TX pilot
     reseeds -> transmit_spatial_multiplexing draws -> RX pilot reseeds.  Per
     OFDM symbol: QAM, zero-pad to a multiple of rank, round-robin layers,
     x_k = W layers[:, k] on the first ceil(Nd/rank) data SCs, CRS pilots per
     TX; per RX FFT; per symbol CRS estimate H[rx, tx, N], detector with the
-    nominal s2 = 10^(-SNR/10), layer demap, hard bits."""
+    nominal s2 = 10^(-SNR/10), layer demap, hard bits.
+    draws (mimo_oracle.transmit_sm's format; philox.sm_draws for the device's
+    Philox mode): the link's random numbers; no H_initial is then consumed (the
+    global RNG is left untouched) and rank and PMI are the fixed ones, W =
+    codebook(num_tx, 'TM4', rank)[pmi] (pmi=None: 0).  paths: transmit_sm's.
+    Also returned, per data RE in grid order [n_sym * Nd]: 'symbols_rx' (the
+    equalised symbols, the slicer's input) and 'kappa' (the 2-norm condition
+    number of the matrix the detector inverts on the RE's subcarrier: He^H He +
+    s2 I for MMSE / IRC / SIC's first stage, He^H He for ZF, 1 for MRC); per
+    data subcarrier [n_sym * ceil(Nd / rank)]: 'H_eff' [.., rx, rank] and 'y'
+    [.., rx], the detector's inputs, and 'layers_rx' [.., rank], its output;
+    'H_est' [n_sym, rx, tx, ceil(Nd / rank)]: the CRS estimates there;
+    'noise_power' [rx]: transmit_sm's; for SIC 'sic_stages' [.., rank]: the slicer
+    input of every cancellation stage in detection order, and 'sic_order'."""
     bits = np.asarray(bits)
     n0 = len(bits)
     Nd = len(num.data_idx)
     bpo = Nd * num.bps
     n_sym = int(np.ceil(n0 / bpo))
     bp = np.pad(bits, (0, n_sym * bpo - n0)) if n0 < n_sym * bpo else bits.copy()
-    r, pmi, W = choose_rank_pmi(num_tx, num_rx, rank, snr_db, csi)
+    if draws is None and pmi is None:
+        r, pmi, W = choose_rank_pmi(num_tx, num_rx, rank, snr_db, csi)
+    else:
+        if draws is None:
+            np.random.randn(num_rx, num_tx)            # H_initial is always drawn (core/ofdm_core.py:2581)
+            np.random.randn(num_rx, num_tx)
+        r, pmi = int(rank), int(pmi or 0)
+        W = codebook(num_tx, 'TM4', r)[pmi]
     if num_rx < r:
         raise ValueError(f"num_rx ({num_rx}) debe ser >= num_layers ({r})")
     pidx = mimo_pilot_indices(num, num_tx)
@@ -306,22 +335,46 @@ def simulate_tm4(num: Numerology, bits, snr_db, num_tx=4, num_rx=2, rank='adapti
             sig[t].append(_ofdm_time(num, grids[t]))
     xs = [np.concatenate(s) for s in sig]
     fD = doppler_hz(frequency_ghz, velocity_kmh)
-    ys, Hm = transmit_sm(num, xs, num_rx, channel, snr_db, profile, fD)
+    info = {}
+    ys, Hm = transmit_sm(num, xs, num_rx, channel, snr_db, profile, fD, draws, paths, info)
     per_rx = [_fft_symbols(num, ys[k], n_sym) for k in range(num_rx)]
     s2 = 10 ** (-snr_db / 10)
     const = constellation(num.modulation)
-    out_bits, syms = [], []
+    n_dsc = -(-Nd // r)
+    dsc = num.data_idx[:n_dsc]
+    sic = detector.upper() == 'SIC'
+    out_bits, syms, lays, Hes, yv, kap, stages, order, Hest = [], [], [], [], [], [], [], [], []
     for i in range(min(n_sym, len(per_rx[0]))):
         g = np.array([per_rx[k][i] for k in range(num_rx)])
         H = mimo_estimate(num, g, num_tx)
-        lay = detect(detector, g[:, num.data_idx], H[:, :, num.data_idx], s2, W, r, const)
+        tr = [] if sic else None
+        lay = detect(detector, g[:, num.data_idx], H[:, :, num.data_idx], s2, W, r, const, tr)
         sy = layer_demap(lay, original_length=Nd)
         syms.append(sy[:Nd])
+        lays.append(lay[:, :n_dsc].T)
         out_bits.append(hard_bits(sy[:Nd], num.modulation)[:bpo])
+        He = np.stack([H[:, :, k] @ W for k in dsc])               # [n_dsc][rx][rank]
+        Hes.append(He)
+        Hest.append(H[:, :, dsc])
+        yv.append(g[:, dsc].T)
+        if detector.upper() == 'MRC':
+            kk = np.ones(n_dsc)
+        else:
+            A = np.conj(np.swapaxes(He, 1, 2)) @ He
+            kk = np.linalg.cond(A if detector.upper() == 'ZF' else A + s2 * np.eye(r))
+        kap.append(np.repeat(kk, r)[:Nd])
+        if sic:
+            stages.append(np.array([[v for _, v in t] for t in tr[:n_dsc]]))
+            order.append(np.array([[l for l, _ in t] for t in tr[:n_dsc]]))
     rxb = np.concatenate(out_bits)[:n0]
     err = int(np.sum(bits[:n0] != rxb))
-    return {'bits_received_array': rxb, 'bit_errors': err, 'ber': err / n0, 'channel_matrix': Hm,
-            'precoder_matrix': W, 'rank': r, 'pmi_used': pmi, 'signals_rx': ys, 'symbols_rx': np.concatenate(syms)}
+    out = {'bits_received_array': rxb, 'bit_errors': err, 'ber': err / n0, 'channel_matrix': Hm,
+           'precoder_matrix': W, 'rank': r, 'pmi_used': pmi, 'signals_rx': ys, 'symbols_rx': np.concatenate(syms),
+           'kappa': np.concatenate(kap), 'layers_rx': np.concatenate(lays), 'H_est': np.stack(Hest),
+           'noise_power': info['noise_power'], 'H_eff': np.concatenate(Hes), 'y': np.concatenate(yv)}
+    if sic:
+        out['sic_stages'], out['sic_order'] = np.concatenate(stages), np.concatenate(order)
+    return out
 
 
 __all__ = ['codebook', 'select_best_pmi', 'optimal_rank', 'precoder_for_rank', 'feedback', 'detect', 'detect_one',

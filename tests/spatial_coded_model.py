@@ -124,16 +124,19 @@ def soft_rule(He, y, s2, det):
     return s / mu, e / mu, kappa, mu.min(axis=1)
 
 
-def soft_rule_chol(He, y, s2, det):
+def soft_rule_chol(He, y, s2, det, raw=False):
     """The same rule in the kernel's order: Cholesky A = L L^H, the triangular
     inverse L^-1 by forward substitution, s = L^-H (L^-1 rhs), (A^-1)_ll =
-    sum_k |(L^-1)_kl|^2 -> z, nv."""
+    sum_k |(L^-1)_kl|^2 -> z, nv.  raw: the hard-output detectors' s instead
+    (MMSE: before the division by mu; ZF and MRC: z itself)."""
     n, _, R = He.shape
     Hh = np.conj(np.swapaxes(He, 1, 2))
     G = Hh @ He
     rhs = (Hh @ y[:, :, None])[:, :, 0]
     if det == 'MRC':
         n2 = np.real(G[:, 0, 0])
+        if raw:
+            return rhs / n2[:, None]
         return rhs / n2[:, None], s2 * np.minimum(1.0 / n2, 1e6)[:, None]
     A = G if det == 'ZF' else G + s2 * np.eye(R)
     L = np.linalg.cholesky(A)
@@ -147,6 +150,8 @@ def soft_rule_chol(He, y, s2, det):
             Li[:, i, k] = v / np.real(L[:, i, i])
     u = (Li @ rhs[:, :, None])[:, :, 0]
     s = (np.conj(np.swapaxes(Li, 1, 2)) @ u[:, :, None])[:, :, 0]
+    if raw:
+        return s
     q = np.sum(np.abs(Li) ** 2, axis=1)
     if det == 'ZF':
         return s, s2 * np.minimum(q, 1e6)

@@ -27,8 +27,9 @@ Tolerances are the suite's own for the same quantities:
 B = 5 frames (odd: the wave TX's two-wave block is left half full), SNRs
 spread over 0..30 dB, 14 OFDM symbols unless stated, TB 2000 when coded.
 
-The multi-antenna chains (SFBC, spatial multiplexing, beamforming) are not
-covered: their fused kernels draw from Philox only and need the Philox oracle.
+The multi-antenna chains (SFBC, spatial multiplexing, beamforming), whose fused
+kernels draw from Philox only, are compared with the oracle on its Philox
+restatement in tests/test_gpu_mimo_philox.py.
 """
 import os
 
