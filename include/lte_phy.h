@@ -344,6 +344,27 @@ int lte_plan_early_stop_repack(const lte_plan *plan);   /* after, or 0 */
  * (zeros before the first run); entries past n are dropped.  Returns the full
  * length 2 + 3 n_cb.  LTE_EINVAL when re-packing is off. */
 int lte_plan_repack_info(const lte_plan *plan, int64_t *info, int n);
+/* The coded SISO pipeline (ABI 3, additions).  Under LTE_CODED_PIPE=1 (the
+ * default for float64 plans; float32 plans need it in the environment) a run of
+ * the LTE_CHAIN_CODED chain on its default path (fused TX + channel, fused
+ * receiver, (z, nv) hand-off; all stages, no capture, no injection, no HARQ,
+ * no early stop, max-log) is queued in slices of whole 64-frame groups: the
+ * front end of slice i + 1 runs while slice i decodes.  A slice is
+ * LTE_CODED_PIPE_GROUPS groups rounded up to the decoder rows' chunk width (32
+ * for plans of at least 32 groups of max_frames, else 1); a batch of one slice,
+ * and every other run, takes the serial path.  Every output of lte_run is bit
+ * for bit the serial run's.
+ * info [n] of the last lte_run: the slice count (0: the run was serial), the
+ * groups per slice, and why it was serial -- 0 pipelined, 1 LTE_CODED_PIPE is
+ * 0, 2 another chain, 3 another kernel path, 4 not every stage, 5 a capture,
+ * 6 an injection, 7 HARQ / early stop / log-MAP, 8 the batch is one slice;
+ * entries past n are dropped.  Returns the full length 3. */
+int lte_plan_pipe_info(const lte_plan *plan, int64_t *info, int n);
+/* The slicing rule itself (no device needed): the slices of a batch of `groups`
+ * 64-frame groups for chunk width `chunk` and LTE_CODED_PIPE_GROUPS =
+ * pipe_groups, as (first group, groups) pairs in out [n_max][2].  Returns the
+ * slice count (pairs past n_max are dropped); LTE_EINVAL for an argument below 1. */
+int lte_coded_pipe_slices(int64_t groups, int32_t chunk, int64_t pipe_groups, int32_t *out, int32_t n_max);
 /* n* of the plan's last lte_run, [n_frames][n_cb] bytes (n = n_frames * n_cb);
  * LTE_EINVAL when early stop is off, nothing has run since it was set, or n
  * is not that run's size. */

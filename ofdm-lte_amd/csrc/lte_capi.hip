@@ -1121,6 +1121,7 @@ int lte_plan_destroy(lte_plan* p) {
   if (!p) return LTE_OK;
   // the stream drains first: no buffer is freed under work that may be pending on it
   if (p->stream) (void)hipStreamSynchronize(p->stream);
+  p->pipe.reset();   // (the pipeline's decoder streams drain in its destructor)
   for (auto e : p->evpool) (void)hipEventDestroy(e);
   if (p->stream) (void)hipStreamDestroy(p->stream);
   delete p;   // every DBuf member frees itself
@@ -1210,6 +1211,19 @@ int lte_plan_repack_info(const lte_plan* p, int64_t* info, int n) {
   for (int i = 0; i < 3 * p->C; ++i) v.push_back(i < (int)p->rp_last.size() ? p->rp_last[i] : 0);
   for (int i = 0; i < n && i < (int)v.size(); ++i) info[i] = v[i];
   return (int)v.size();
+}
+
+int lte_plan_pipe_info(const lte_plan* p, int64_t* info, int n) {
+  if (!p || !info) return fail(LTE_EINVAL, "null argument");
+  for (int i = 0; i < n && i < 3; ++i) info[i] = p->pipe_last[i];
+  return 3;
+}
+
+int lte_coded_pipe_slices(int64_t groups, int32_t chunk, int64_t pipe_groups, int32_t* out, int32_t n_max) {
+  if (n_max < 0 || (n_max > 0 && !out)) return fail(LTE_EINVAL, "null argument");
+  if (groups < 1 || groups > INT32_MAX || chunk < 1 || pipe_groups < 1 || pipe_groups > INT32_MAX)
+    return fail(LTE_EINVAL, "groups, chunk and pipe_groups must be >= 1");
+  return coded_pipe_slices(groups, chunk, pipe_groups, out, n_max);
 }
 
 int lte_plan_set_turbo_scale(lte_plan* p, double scale) {
@@ -1870,27 +1884,42 @@ static int run_bf(lte_plan* p, const lte_run_args* a, int B, int n_snr, const st
   return LTE_OK;
 }
 
-// Fading taps, fused TX + channel, first-samples power fix-up and noise power.
+// run_txch's buffers that exist only once a run needs them, sized for the plan's max_frames
 template <class R>
-static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const SisoPath& path, int B,
-                    const TxSource& src, uint64_t cseed, Inj<R> inj_ph, cx<R>* cap_tx_syms, cx<R>* x_out,
-                    TxChannelT<R>* ch_out) {
+static int txch_alloc(lte_plan* p, const SisoPath& path) {
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
   const int maxd = *std::max_element(d.delays, d.delays + d.n_paths);
   // each symbol's head / tail TX samples for k_chan_fix (none when the TX forms the head power itself)
   if (path.ch_fix && c.xh.alloc((size_t)d.max_frames * p->n_sym * 2 * std::max(maxd, 1)))
     return fail(LTE_ENOMEM, "tx channel");
+  // time-varying taps: per-symbol Taylor sets
+  if (d.fD != 0.0 && c.tcoef.alloc((size_t)d.max_frames * d.num_rx * d.n_paths * p->n_sym * mimo_ncf<R>()))
+    return fail(LTE_ENOMEM, "tx channel");
+  return LTE_OK;
+}
+
+// Fading taps, fused TX + channel, first-samples power fix-up and noise power
+// for the B frames f0 .. of the batch; src, inj_ph, cap_tx_syms and x_out are
+// the caller's, already moved on to frame f0 (from_frame).
+template <class R>
+static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const SisoPath& path, int B,
+                    const TxSource& src, uint64_t cseed, Inj<R> inj_ph, cx<R>* cap_tx_syms, cx<R>* x_out,
+                    TxChannelT<R>* ch_out, int64_t f0 = 0) {
+  const lte_plan_desc& d = p->d;
+  ChainBufs<R>& c = cbuf<R>(p);
+  const int maxd = *std::max_element(d.delays, d.delays + d.n_paths);
+  if (const int e = txch_alloc<R>(p, path)) return e;
   const int rx = d.num_rx;
   const bool tv = d.fD != 0.0;   // time-varying taps: per-symbol Taylor sets
-  if (tv && c.tcoef.alloc((size_t)d.max_frames * rx * d.n_paths * p->n_sym * mimo_ncf<R>()))
-    return fail(LTE_ENOMEM, "tx channel");
+  R* const phases = from_frame(c.phases.p, f0, (int64_t)rx * d.n_paths * 16);
+  cx<R>* const tcoef = tv ? from_frame(c.tcoef.p, f0, (int64_t)rx * d.n_paths * p->n_sym * mimo_ncf<R>()) : nullptr;
   {
     Timer t(p, KN_FADING, s);
-    LCHK(launch_fading<R>(s, B, rx, d.n_paths, c.gains.p, p->fid.p, cseed, inj_ph, c.phases.p, c.coef.p));
+    LCHK(launch_fading<R>(s, B, rx, d.n_paths, c.gains.p, p->fid.p + f0, cseed, inj_ph, phases,
+                          from_frame(c.coef.p, f0, (int64_t)rx * d.n_paths)));
     if (tv)   // one (frame, RX) at a time: phases / sets are [B][rx][path]
-      LCHK(launch_jakes_sets<R>(s, B * rx, d.n_paths, p->n_sym, d.N + d.cp_len, c.phases.p, c.gains.p, d.fD, d.fs,
-                                c.tcoef.p));
+      LCHK(launch_jakes_sets<R>(s, B * rx, d.n_paths, p->n_sym, d.N + d.cp_len, phases, c.gains.p, d.fD, d.fs, tcoef));
   }
   TxChannelT<R> ch{};
   ch.tcoef = tv ? c.tcoef.p : nullptr;
@@ -1902,6 +1931,7 @@ static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const Sis
   ch.y = c.y.p;
   ch.xh = path.ch_fix ? c.xh.p : nullptr;
   ch.pow_part = c.pow_part.p;
+  ch = from_frame(ch, p->grid, f0);
   ch.x_out = x_out;
   if (ch_out) *ch_out = ch;
   {
@@ -1923,9 +1953,147 @@ static int run_txch(lte_plan* p, hipStream_t s, const lte_run_args* a, const Sis
   {
     Timer t(p, KN_CHANNEL, s);
     if (path.ch_fix) LCHK(launch_chan_fix<R>(s, p->grid, B, ch));
-    LCHK(launch_npow<R>(s, B, rx, ch.pow_part, p->n_sym, p->L, c.snr_lin.p, c.npow.p));
+    LCHK(launch_npow<R>(s, B, rx, ch.pow_part, p->n_sym, p->L, c.snr_lin.p + f0, from_frame(c.npow.p, f0, rx)));
   }
   return LTE_OK;
+}
+
+// ---------------------------------------------------------------------------
+// The coded SISO pipeline: the batch in slices of whole 64-frame
+// groups; the plan stream runs the front end (fading .. k_dematch_zn) slice
+// after slice without ever waiting, two decoder streams take the slices'
+// decodes alternately, each as soon as its rows are written, and the plan
+// stream joins them for one k_crc_count over the batch.  Same kernels, same
+// per-frame arguments and 64-frame groups as the serial run: equal outputs.
+
+// Why a run stays serial (PIPE_RAN: it does not, and *slices holds its (g0, G) pairs).
+static PipeReason pipe_select(const lte_plan* p, const lte_run_args* a, const SisoPath& path, const Knobs& k, int B,
+                              std::vector<int32_t>* slices) {
+  const lte_plan_desc& d = p->d;
+  const int stages = a->stages ? a->stages : LTE_STAGE_ALL;
+  if (!(p->f64 ? k.coded_pipe : k.coded_pipe_f32)) return PIPE_OFF;
+  if (d.chain != LTE_CHAIN_CODED || d.num_rx != 1 || p->mimo || p->bf) return PIPE_CHAIN;
+  if (stages != LTE_STAGE_ALL) return PIPE_STAGES;
+  if (a->in_signal || a->cap_signal_tx || a->cap_signal_rx || a->cap_data_syms || a->cap_H || a->cap_pilot_stats ||
+      a->cap_bits_rx || a->cap_llr || a->cap_noise_power || a->cap_tx_syms)
+    return PIPE_CAPTURE;
+  if (a->bits || a->phases || a->noise) return PIPE_INJECT;
+  if (p->harq || p->early_stop || logmap_on()) return PIPE_DECODER;
+  if (!path.fused() || path.xhand || !path.zn || (path.rx != RX_FRAME && path.rx != RX_FRAME_W)) return PIPE_PATH;
+  const int G = (B + 63) / 64, ch = turbo_plan_ch(p);
+  const int n = coded_pipe_slices(G, ch, k.coded_pipe_groups, nullptr, 0);
+  if (n < 2) return PIPE_ONE_SLICE;
+  slices->resize((size_t)2 * n);
+  coded_pipe_slices(G, ch, k.coded_pipe_groups, slices->data(), n);
+  return PIPE_RAN;
+}
+
+template <class R>
+static int run_siso_pipe(lte_plan* p, const lte_run_args* a, const SisoPath& path, int B, int n_snr,
+                         const std::vector<double>& snr_lin, const std::vector<int32_t>& slices) {
+  const lte_plan_desc& d = p->d;
+  ChainBufs<R>& c = cbuf<R>(p);
+  const Grid& g = p->grid;
+  hipStream_t s = p->stream;
+  const int ns = (int)slices.size() / 2, ch = turbo_plan_ch(p);
+  // everything a slice needs exists before the first one is queued
+  if (!p->pipe) p->pipe = std::make_unique<PipeStreams>();
+  if (!p->pipe->ensure((size_t)ns)) return fail(LTE_EHIP, "pipeline streams");
+  PipeStreams& ps = *p->pipe;
+  if (const int e = txch_alloc<R>(p, path)) return e;
+  std::vector<R> sl(B);
+  for (int b = 0; b < B; ++b) sl[b] = (R)snr_lin[b];
+  HIPCHK(hipMemcpyAsync(c.snr_lin.p, sl.data(), B * sizeof(R), hipMemcpyHostToDevice, s));
+  const TxSource src{1, p->pw.p, p->PW, p->enc.p, p->enc_words, p->tx_map.p};
+  const Scored sc{p->pw.p, p->PW, d.n_bits, p->frame_err.p};
+  const RxStreams<R> rxs{.num_rx = 1, .y = c.y.p, .rx_stride = p->L, .frame_stride = p->L, .npow = c.npow.p,
+                         .fid = p->fid.p, .seed = a->seed, .inj_z = {}};
+  const SoftOut<R> soft = soft_out<R>(p, true, true);
+  const int n_re = p->n_re_bits / d.bps;
+  {
+    Timer t(p, KN_PAYLOAD);
+    LCHK(launch_payload(s, p->pw.p, p->PW, d.n_bits, CRC24A_POLY, p->fid.p, a->seed, B, Inj<uint32_t>{}));
+  }
+  {
+    Timer t(p, KN_ENCODE);
+    LCHK(launch_encode(s, p->pw.p, p->PW, p->KWmax, p->enc.p, p->EW, p->cbi.p, p->C, B, p->enc_qmask.p, p->qstride));
+  }
+  // From here to the join a failed launch leaves work on three streams: queue()
+  // returns the error and every stream is drained before it goes to the caller.
+  int t_turbo = -1;   // the decoders' interval in the event pool
+  auto queue = [&]() -> int {
+    std::vector<TurboJob> jobs(p->C);
+    for (int i = 0; i < ns; ++i) {
+      const int g0 = slices[2 * i], G = slices[2 * i + 1];
+      const int64_t f0 = (int64_t)g0 * 64;
+      const int Bs = std::min(B - (int)f0, G * 64);
+      if (const int e = run_txch<R>(p, s, a, path, Bs, from_frame(src, f0), a->seed, Inj<R>{}, nullptr, nullptr, nullptr,
+                                    f0))
+        return e;
+      {
+        Timer t(p, KN_RX_DATA);
+        const RxStreams<R> rf = from_frame(rxs, f0);
+        const SoftOut<R> sf = from_frame(soft, f0, n_re, d.bps, (int64_t)p->n_grp * p->Nd);
+        if (path.rx == RX_FRAME_W) {
+          if constexpr (std::is_same_v<R, double>)
+            LCHK(launch_rx_frame_w(s, g, 1, Bs, rf, c.snr_lin.p + f0, sf, RxCaptures<R>{}));
+          else
+            return fail(LTE_EINVAL, "the wave receivers run in float64 plans only");
+        } else {
+          LCHK(launch_rx_frame<R>(s, g, d.chain, 1, Bs, rf, c.snr_lin.p + f0, from_frame(sc, f0), sf,
+                                  RxCaptures<R>{}));
+        }
+      }
+      {
+        // (the hand-off and the row arrays are the batch's: groups g0 .. of frames < f0 + Bs)
+        Timer t(p, KN_DEMATCH);
+        LCHK(launch_dematch_zn<R>(s, soft.z, soft.nv, n_re, p->Nd, d.bps, (int)f0 + Bs, p->rx_map.p, p->n_layers,
+                                  c.blk_ptrs.p, p->rows_dev.p, ch, g0, 0, 0));
+      }
+      HIPCHK(hipEventRecord(ps.ready[i], s));
+      // the slice's decode: the plan's arrays from chunk g0 / ch on (g0 is a multiple of ch)
+      hipStream_t ds = ps.dec[i & 1];
+      HIPCHK(hipStreamWaitEvent(ds, ps.ready[i], 0));
+      for (int r = 0; r < p->C; ++r) {
+        const CbInfo& cb = p->cbs[r];
+        const int64_t ck_rows = (int64_t)turbo_nwin(cb.K) * turbo_ck_rows(sizeof(R) == 8);
+        jobs[r] = TurboJob{c.blk[r].p + turbo_elem_ch(ch, turbo_rows(cb.K), g0, 0),
+                           c.ckpt[r].p + turbo_elem_ch(ch, ck_rows, g0, 0),
+                           p->decb[r].p + (size_t)g0 * turbo_kw(cb.K) * TURBO_RS, cb.K, cb.f1, cb.f2, G, ch};
+      }
+      if (i == 0 && p->timing) {   // `turbo`: one interval per run, from here to the join
+        t_turbo = (int)p->evuse.size() * 2;
+        while ((int)p->evpool.size() < t_turbo + 2) {
+          hipEvent_t e;
+          HIPCHK(hipEventCreate(&e));
+          p->evpool.push_back(e);
+        }
+        p->evuse.push_back({KN_TURBO, t_turbo});
+        HIPCHK(hipEventRecord(p->evpool[t_turbo], ds));
+      }
+      LCHK(launch_turbo_jobs(ds, jobs.data(), p->C, d.turbo_iters, TM_DEC1, sizeof(R) == 8 ? 1 : 0, nullptr,
+                             p->turbo_scale));
+    }
+    for (int k = 0; k < 2; ++k) {
+      HIPCHK(hipEventRecord(ps.done[k], ps.dec[k]));
+      HIPCHK(hipStreamWaitEvent(s, ps.done[k], 0));
+    }
+    if (t_turbo >= 0) HIPCHK(hipEventRecord(p->evpool[t_turbo + 1], s));
+    return LTE_OK;
+  };
+  if (const int e = queue()) {
+    (void)hipStreamSynchronize(ps.dec[0]);
+    (void)hipStreamSynchronize(ps.dec[1]);
+    (void)hipStreamSynchronize(s);
+    p->evuse.clear();   // (an interval may lack its end)
+    return e;
+  }
+  {
+    Timer t(p, KN_CRC);
+    LCHK(launch_crc_count(s, p->cbi.p, p->C, p->dec_ptrs.p, p->kw_dev.p, B, sc, p->frame_crc.p, nullptr, 0, p->fid.p,
+                          a->seed));
+  }
+  return read_back<R>(p, a, B, n_snr, true, true, (size_t)p->n_sym * p->Nd, rxs);
 }
 
 // SISO / SIMO chains (uncoded, coded, MRC) in precision R.
@@ -2147,10 +2315,22 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
   if (logmap_on() && p->turbo_scale != 1.0)
     return fail(LTE_EUNSUP, "extrinsic scaling runs the max-log decoders only (set_decoder_mode(True))");
   const Knobs knobs = read_knobs();   // the environment switches, once per run
+  p->pipe_last[0] = p->pipe_last[1] = 0;
+  p->pipe_last[2] = (p->f64 ? knobs.coded_pipe : knobs.coded_pipe_f32) ? PIPE_CHAIN : PIPE_OFF;
   if (!p->mimo && !p->bf) {
     const SisoPath path = select_siso(p, a, knobs);
-    const int e = p->f64 ? run_siso<double>(p, a, path, B, n_snr, sl, inj_bits)
-                         : run_siso<float>(p, a, path, B, n_snr, sl, inj_bits);
+    std::vector<int32_t> slices;   // the coded pipeline's (g0, G), when this run takes it
+    p->pipe_last[2] = pipe_select(p, a, path, knobs, B, &slices);
+    int e;
+    if (p->pipe_last[2] == PIPE_RAN) {
+      p->pipe_last[0] = (int)slices.size() / 2;
+      p->pipe_last[1] = slices[1];
+      e = p->f64 ? run_siso_pipe<double>(p, a, path, B, n_snr, sl, slices)
+                 : run_siso_pipe<float>(p, a, path, B, n_snr, sl, slices);
+    } else {
+      e = p->f64 ? run_siso<double>(p, a, path, B, n_snr, sl, inj_bits)
+                 : run_siso<float>(p, a, path, B, n_snr, sl, inj_bits);
+    }
     HIPCHK(hipStreamSynchronize(s));
     p->hq_round = 0;   // the next run opens a new process unless lte_plan_harq_set_round says otherwise
     return e;

@@ -147,6 +147,61 @@ struct LinkTaps {
   double fs;
 };
 
+// The same groups for the frames f0 .. of a batch: every per-frame array moved
+// on by f0 frames, everything else as it is.  A launcher handed these (and the
+// per-frame arrays it takes bare, moved on the same way) sees frame f0 as its
+// frame 0; the kernels index frames from their arguments only, and the Philox
+// draws are keyed by the frame ids, so a batch run slice by slice computes what
+// it computes in one launch (the coded SISO pipeline, lte_capi.hip).
+template <class T>
+inline T* from_frame(T* p, int64_t f0, int64_t per) { return p ? p + f0 * per : nullptr; }
+template <class R>
+inline Inj<R> from_frame(const Inj<R>& i, int64_t f0) { return {from_frame(i.p, f0, i.stride), i.stride}; }
+template <class R>
+inline RxStreams<R> from_frame(RxStreams<R> r, int64_t f0) {
+  r.y = from_frame(r.y, f0, r.frame_stride);
+  r.npow = from_frame(r.npow, f0, r.num_rx);
+  r.fid = from_frame(r.fid, f0, 1);
+  r.inj_z = from_frame(r.inj_z, f0);
+  return r;
+}
+inline TxSource from_frame(TxSource s, int64_t f0) {
+  s.pw = from_frame(s.pw, f0, s.PW);
+  s.enc = from_frame(s.enc, f0, s.enc_words);
+  return s;
+}
+inline Scored from_frame(Scored s, int64_t f0) {
+  s.pw = from_frame(s.pw, f0, s.PW);
+  s.frame_err = from_frame(s.frame_err, f0, 1);
+  return s;
+}
+// n_re: REs per frame; bps: LLRs per RE; n_nv: noise variances per frame
+template <class R>
+inline SoftOut<R> from_frame(SoftOut<R> s, int64_t f0, int64_t n_re, int bps, int64_t n_nv) {
+  s.llr = from_frame(s.llr, f0, n_re * bps);
+  s.z = from_frame(s.z, f0, n_re);
+  s.nv = from_frame(s.nv, f0, n_nv);
+  return s;
+}
+
+// The coded SISO pipeline's slices of a batch of `groups` 64-frame groups: runs
+// of `per` groups, per = knob rounded up to the decoder rows' chunk width ch
+// (so every slice's rows, checkpoints and decision words start at a chunk of
+// the plan's arrays), the last one whatever is left.  out (may be null) gets
+// (g0, G) pairs, at most n_max of them; returns the slice count (0: groups,
+// ch or knob below 1).  Pure host arithmetic.
+inline int coded_pipe_slices(int64_t groups, int ch, int64_t knob, int32_t* out, int n_max) {
+  if (groups < 1 || ch < 1 || knob < 1) return 0;
+  const int64_t per = (knob + ch - 1) / ch * ch;
+  int n = 0;
+  for (int64_t g0 = 0; g0 < groups; g0 += per, ++n)
+    if (out && n < n_max) {
+      out[2 * n] = (int32_t)g0;
+      out[2 * n + 1] = (int32_t)std::min<int64_t>(per, groups - g0);
+    }
+  return n;
+}
+
 // launchers (return hipError_t as int)
 constexpr int CRC24A_POLY = 0x864CFB, CRC24B_POLY = 0x800063;   // crc.py polynomials without x^24
 // crc: CRC polynomial to append (0: none); inj: the caller's payload words [PW] per frame in place of the Philox ones
@@ -204,6 +259,18 @@ struct TxChannelT {
   // instead of num_rx received streams; the receiver applies the taps
   cx<R>* x_out;
 };
+template <class R> constexpr int mimo_ncf();
+// the channel group for the frames f0 .. (from_frame above)
+template <class R>
+inline TxChannelT<R> from_frame(TxChannelT<R> c, const Grid& g, int64_t f0) {
+  c.coef = from_frame(c.coef, f0, (int64_t)c.num_rx * c.n_paths);
+  c.y = from_frame(c.y, f0, (int64_t)c.num_rx * g.L);
+  c.xh = from_frame(c.xh, f0, (int64_t)g.n_sym * 2 * c.max_delay);
+  c.pow_part = from_frame(c.pow_part, f0, (int64_t)c.num_rx * g.n_sym);
+  c.tcoef = from_frame(c.tcoef, f0, (int64_t)c.num_rx * c.n_paths * g.n_sym * mimo_ncf<R>());
+  c.x_out = from_frame(c.x_out, f0, (int64_t)g.n_sym * g.N);
+  return c;
+}
 bool txch_supported(const Grid& g, int n_paths, int max_delay);
 // host payload bits (one uint8 per bit, frames `stride` bytes apart) already on
 // the device -> packed MSB-first words [nf][nwd]

@@ -49,11 +49,31 @@ namespace lte {
 #define TXF_STAGE 1
 #endif
 
+// The coded SISO pipeline (run_siso_pipe, lte_capi.hip): on / off,
+// and the slice length in 64-frame groups (rounded up to the decoder rows'
+// chunk width).  Env LTE_CODED_PIPE = 0 / 1 and LTE_CODED_PIPE_GROUPS override.
+// Same-box A/B at config 2 (profiles/coded_pipe_ab.md): 256 groups 178.5-179.4 k
+// subframes/s against 174.1-174.7 k serial (352: 177.7-180.3 k, 512: 176.1-177.5 k,
+// 224, five slices: 161.0-162.3 k, slower than serial),
+// so float64 plans pipeline by default; float32 plans only when the
+// environment says 1 (306-310 k pipelined against 315-317 k serial: slower).
+#ifndef LTE_CODED_PIPE
+#define LTE_CODED_PIPE 1
+#endif
+#ifndef LTE_CODED_PIPE_F32
+#define LTE_CODED_PIPE_F32 0
+#endif
+#ifndef LTE_CODED_PIPE_GROUPS
+#define LTE_CODED_PIPE_GROUPS 256
+#endif
+
 struct Knobs {
   // SISO / SIMO chains
   bool txch_fuse, tx_frame, tx_stage, tx_wave, txw_stage, simo_tx_wave;
   bool rx_fuse, rx_wave, simo_rx_wave, rxs_pairs, simo_xhand, demap_in_dematch;
   bool harq_skip;
+  bool coded_pipe, coded_pipe_f32;   // float64 / float32 plans
+  int coded_pipe_groups;             // >= 1
   // multi-antenna chains
   bool mimo_lp_fuse, mimo_flat_fuse, txch_pr, mimo_tx_wave, txm_frame, sfbc_txch_fuse, sfbc_rx_fuse, sfbc_link_merge;
   bool chm_tay, cht_econ, mimo_rx_wave, spatial_hp, dsp_stage;
@@ -90,6 +110,11 @@ inline Knobs read_knobs() {
   k.simo_xhand = knob("LTE_SIMO_XHAND", 0);
   k.demap_in_dematch = knob("LTE_DEMAP_IN_DEMATCH", 1);   // coded 16/64-QAM: (z, nv) hand-off to k_dematch_zn (0: the LLR round trip)
   k.harq_skip = knob("LTE_HARQ_SKIP", 1);      // HARQ rounds >= 1: finished 64-frame groups skip the decoder (0: k_turbo* decode every group)
+  // coded SISO: the front end of frame slice i + 1 runs while slice i decodes (0: the stages in sequence)
+  k.coded_pipe = knob("LTE_CODED_PIPE", LTE_CODED_PIPE);
+  k.coded_pipe_f32 = knob("LTE_CODED_PIPE", LTE_CODED_PIPE_F32);   // (float32 plans: the same variable, its own default)
+  const char* pg = std::getenv("LTE_CODED_PIPE_GROUPS");   // 64-frame groups per slice (rounded up to the chunk width)
+  k.coded_pipe_groups = std::max(1, pg ? std::atoi(pg) : LTE_CODED_PIPE_GROUPS);
   // --- multi-antenna transmitter
   k.mimo_lp_fuse = knob("LTE_MIMO_LP_FUSE", 1);       // transmit_mimo's link power formed by k_ofdm_tx_mimo (0: k_link_power)
   k.mimo_flat_fuse = knob("LTE_MIMO_FLAT_FUSE", 1);   // flat links: TX + channel in one pass, k_ofdm_txch_flat

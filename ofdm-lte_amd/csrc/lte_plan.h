@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
@@ -130,6 +131,59 @@ struct GridHost {
 enum { KN_PAYLOAD, KN_ENCODE, KN_OFDM_TX, KN_FADING, KN_CHANNEL, KN_RX_CHEST, KN_RX_DATA, KN_DEMATCH, KN_TURBO,
        KN_CRC, KN_ACC, KN_CAP, KN_HARQ, KN_COUNT };
 
+// The coded SISO pipeline's two decoder streams and its dependency events
+// (created without timing), made on the first pipelined run and destroyed with
+// the plan.  The destructor drains the streams first.
+struct PipeStreams {
+  hipStream_t dec[2] = {nullptr, nullptr};
+  std::vector<hipEvent_t> ready;          // slice i's decoder rows are written (recorded on the plan stream)
+  hipEvent_t done[2] = {nullptr, nullptr};   // the last decoder launch of each stream
+  PipeStreams() = default;
+  PipeStreams(const PipeStreams&) = delete;
+  PipeStreams& operator=(const PipeStreams&) = delete;
+  ~PipeStreams() {
+    for (hipStream_t s : dec)
+      if (s) (void)hipStreamSynchronize(s);
+    for (hipEvent_t e : ready) (void)hipEventDestroy(e);
+    for (hipEvent_t e : done)
+      if (e) (void)hipEventDestroy(e);
+    for (hipStream_t s : dec)
+      if (s) (void)hipStreamDestroy(s);
+  }
+  // streams, done events and n ready events (false: a HIP call failed)
+  bool ensure(size_t n) {
+    for (hipStream_t& s : dec)
+      if (!s && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) {
+        s = nullptr;
+        return false;
+      }
+    for (hipEvent_t& e : done)
+      if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {
+        e = nullptr;
+        return false;
+      }
+    while (ready.size() < n) {
+      hipEvent_t e;
+      if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return false;
+      ready.push_back(e);
+    }
+    return true;
+  }
+};
+
+// why the last lte_run did not take the coded SISO pipeline (lte_plan_pipe_info)
+enum PipeReason {
+  PIPE_RAN = 0,        // it did
+  PIPE_OFF,            // LTE_CODED_PIPE is 0
+  PIPE_CHAIN,          // not the coded SISO chain
+  PIPE_PATH,           // not the fused TX + channel, fused receiver and (z, nv) hand-off
+  PIPE_STAGES,         // not every stage runs
+  PIPE_CAPTURE,        // a capture is asked for
+  PIPE_INJECT,         // bits, phases or noise are injected
+  PIPE_DECODER,        // HARQ, early stop / re-packing, or exact log-MAP
+  PIPE_ONE_SLICE,      // the batch is one slice
+};
+
 struct Plan {
   lte_plan_desc d;
   int L, n_sym, Nd, Np, n_grp, nblk, PW, C = 0, KWmax = 0, EW = 0, enc_words = 0;
@@ -212,6 +266,10 @@ struct Plan {
   DBuf<double2> m_pval64;
   DBuf<float> m_pig;
   DBuf<double> m_pig64, m_W;
+  // coded SISO pipeline: its streams (null until the first pipelined run) and
+  // the last lte_run's slice count (0: serial), groups per slice, PipeReason
+  std::unique_ptr<PipeStreams> pipe;
+  int pipe_last[3] = {0, 0, PIPE_OFF};
   // timing
   bool timing = false;
   double kms[KN_COUNT] = {0};

@@ -88,6 +88,8 @@ _SIGS = {
     'lte_plan_set_early_stop_repack': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'lte_plan_early_stop_repack': (ctypes.c_int, [ctypes.c_void_p]),
     'lte_plan_repack_info': (ctypes.c_int, [ctypes.c_void_p, P(c_i64), ctypes.c_int]),
+    'lte_plan_pipe_info': (ctypes.c_int, [ctypes.c_void_p, P(c_i64), ctypes.c_int]),
+    'lte_coded_pipe_slices': (ctypes.c_int, [c_i64, ctypes.c_int32, c_i64, P(ctypes.c_int32), ctypes.c_int32]),
     'lte_plan_turbo_iters_used': (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_uint8), c_i64]),
     'lte_plan_set_turbo_scale': (ctypes.c_int, [ctypes.c_void_p, c_f64]),
     'lte_plan_turbo_scale': (c_f64, [ctypes.c_void_p]),
@@ -279,6 +281,15 @@ def dft(x, inverse=False, precision=None):
     f = load().lte_dft_host64 if prec == 'f64' else load().lte_dft_host
     check(f(M, 1 if inverse else 0, x.size // M, ptr(x.view(rdt), ct), ptr(out.view(rdt), ct)))
     return out
+
+
+def coded_pipe_slices(groups, chunk, pipe_groups):
+    """The coded SISO pipeline's slices of `groups` 64-frame groups as (first
+    group, groups) pairs (lte_coded_pipe_slices; no device needed)."""
+    n = check(load().lte_coded_pipe_slices(int(groups), int(chunk), int(pipe_groups), None, 0))
+    out = np.zeros((n, 2), dtype=np.int32)
+    check(load().lte_coded_pipe_slices(int(groups), int(chunk), int(pipe_groups), ptr(out, ctypes.c_int32), n))
+    return [(int(a), int(b)) for a, b in out]
 
 
 def pilots(cell_id, n):

@@ -33,6 +33,8 @@ class RunResult(dict):
 
 REPACK_DEFAULT = 1   # the boundary repack=True stands for
 REPACK_STATES = ('none', 'packed', 'in_place')   # lte_plan_repack_info's 0 / 1 / 2
+# lte_plan_pipe_info's reason codes 0 .. 8
+PIPE_REASONS = ('pipelined', 'off', 'chain', 'path', 'stages', 'capture', 'inject', 'decoder', 'one_slice')
 
 
 def repack_boundary(repack, early_stop, turbo_iters):
@@ -206,6 +208,14 @@ class Plan:
         t = v[2:].reshape(self.n_cb, 3)
         return {'after': int(v[0]), 'n_cb': int(v[1]), 'undecided': [int(x) for x in t[:, 0]],
                 'groups': [int(x) for x in t[:, 1]], 'state': [REPACK_STATES[int(x)] for x in t[:, 2]]}
+
+    # ------------------------------------------------------------------ coded SISO pipeline
+    def pipe_info(self):
+        """lte_plan_pipe_info of the last run as a dict: slices (0: the run was
+        serial), groups (64-frame groups per slice) and reason (why it was serial)."""
+        v = np.zeros(3, dtype=np.int64)
+        C.check(C.load().lte_plan_pipe_info(self.h, C.ptr(v, C.c_i64), len(v)))
+        return {'slices': int(v[0]), 'groups': int(v[1]), 'reason': PIPE_REASONS[int(v[2])]}
 
     # ------------------------------------------------------------------ extrinsic scaling
     def set_turbo_scale(self, scale):
