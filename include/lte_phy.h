@@ -443,6 +443,38 @@ int lte_plan_harq_info(const lte_plan *plan, int64_t *info, int n);
  * of n_bits payload bits (+ 24 CRC) sent in G coded bits at bps bits per
  * symbol; returns C, or LTE_EINVAL (bad G, or n_max < C). */
 int lte_harq_code_block_bits(int32_t n_bits, int32_t bps, int64_t G, int32_t *K, int32_t *E, int32_t n_max);
+/* Re-packing of the unacknowledged frames (ABI 3, additions; opt-in, off by
+ * default).  Group g of a round's B frames has valid = min(64, B - 64 g) lanes
+ * and `active` of them not acknowledged: finished (active = 0), full (active =
+ * valid) or mixed.  Before a round t >= 1 that runs the skip-aware decoders, M
+ * = the mixed groups, A = their active frames, P = ceil(A / 64), cap = the
+ * packed arrays' groups (G_max > 4 ? ceil(G_max / 4) : 1 for G_max = ceil(
+ * max_frames / 64), as the early-stop re-packing).  The round packs iff M >= 1
+ * and P < M and P <= cap: the decoder input rows of the A frames, in ascending
+ * frame order, are gathered into P packed groups per code block slot (lanes
+ * past A zero), the full groups are decoded in place, the packed groups by the
+ * plain decoders, and the packed decisions go back to the frames' own words.
+ * Every other round runs as it does with the setting off.  counts, frame_errors,
+ * frame_crc_ok, tx_used, lte_plan_harq_info and the soft rows are those of the
+ * same process with the setting off; cap_bits_rx differs only for frames
+ * acknowledged earlier that sit in a packed mixed group: they are not decoded
+ * again, so they keep the decisions of the round that acknowledged them (the
+ * bits the latched frame_errors counts).  The first `on` allocates the packed
+ * arrays (kept until the plan is destroyed).  LTE_EINVAL: NULL plan, not a HARQ
+ * plan.  lte_run_path appends " harq_repack=1" while it is on. */
+int lte_plan_set_harq_repack(lte_plan *plan, int on);
+int lte_plan_harq_repack(const lte_plan *plan);   /* the setting, 0 / 1 */
+/* info [n] of the last lte_run: the setting, the state (0: round 0 or no run
+ * yet, 1 packed, 2 in place), M, A, P, cap, and the 64-lane groups the decoder
+ * ran per code block slot; entries past n are dropped.  Returns the full
+ * length 7.  LTE_EINVAL: NULL argument, not a HARQ plan. */
+int lte_plan_harq_repack_info(const lte_plan *plan, int64_t *info, int n);
+/* The rule itself (host only, no device): acked [n_frames], non-zero = the
+ * frame is acknowledged.  out [6]: M, A, P, 1 if the round packs, and the
+ * groups the decoder runs per code block slot without and with re-packing
+ * (full + mixed; full + P when it packs).  lte_run decides with this rule.
+ * LTE_EINVAL: NULL argument, n_frames < 1, cap < 1. */
+int lte_harq_repack_rule(const uint8_t *acked, int64_t n_frames, int64_t cap, int64_t *out);
 /* Per-kernel device time accumulated by lte_run while timing is on (HIP events
  * on the plan's stream).  names: comma-separated kernel names; ms/launches per
  * kernel in the same order.  n_max entries. */

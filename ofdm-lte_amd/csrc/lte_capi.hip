@@ -1297,6 +1297,71 @@ int lte_plan_harq_info(const lte_plan* p, int64_t* info, int n) {
   return (int)v.size();
 }
 
+int lte_plan_set_harq_repack(lte_plan* p, int on) {
+  if (!p) return fail(LTE_EINVAL, "null plan");
+  if (!p->harq) return fail(LTE_EINVAL, "not a HARQ plan");
+  if (on && p->pk_decb.empty()) {
+    // the packed arrays of early-stop re-packing (which a HARQ plan never has), one
+    // frame index for every slot, and room in hq_skip for the decoder flags and {M, A}
+    const size_t Gm = ((size_t)p->d.max_frames + 63) / 64;
+    const int cap = turbo_pack_cap((int64_t)Gm);
+    std::vector<DBuf<uint32_t>> b(p->C), x(1);
+    DBuf<uint32_t> flags;
+    bool bad = p->f64 ? alloc_packed(p, p->c64, cap) : alloc_packed(p, p->c32, cap);
+    for (int r = 0; r < p->C; ++r) bad |= b[r].alloc((size_t)cap * turbo_kw(p->cbs[r].K) * 64) != 0;
+    bad |= x[0].alloc((size_t)cap * 64) != 0;
+    bad |= flags.alloc(2 * Gm + 2) != 0;
+    // (a process may be under way: the latch's flags move with the buffer)
+    bad = bad || hipStreamSynchronize(p->stream) != hipSuccess ||
+          hipMemcpy(flags.p, p->hq_skip.p, Gm * sizeof(uint32_t), hipMemcpyDeviceToDevice) != hipSuccess;
+    if (bad) {
+      p->c64.pk_blk.clear(); p->c64.pk_ckpt.clear();
+      p->c32.pk_blk.clear(); p->c32.pk_ckpt.clear();
+      return fail(LTE_ENOMEM, "HARQ re-packing arrays");
+    }
+    p->pk_decb.swap(b);
+    p->pk_idx.swap(x);
+    p->hq_skip = std::move(flags);
+  }
+  if ((on != 0) != p->hq_repack) {   // a round under way continues in place on the latch's flags alone
+    if (p->hq_rp_G >= 0 && (int)p->hq_skip_h.size() == 2 * p->hq_rp_G + 2) p->hq_skip_h.resize(p->hq_rp_G);
+    p->hq_rp_G = -1;
+    for (auto& v : p->hq_rp_last) v = 0;
+  }
+  p->hq_repack = on != 0;
+  return LTE_OK;
+}
+
+int lte_plan_harq_repack(const lte_plan* p) {
+  if (!p) return fail(LTE_EINVAL, "null plan");
+  return p->hq_repack ? 1 : 0;
+}
+
+int lte_plan_harq_repack_info(const lte_plan* p, int64_t* info, int n) {
+  if (!p || !info) return fail(LTE_EINVAL, "null argument");
+  if (!p->harq) return fail(LTE_EINVAL, "not a HARQ plan");
+  const int64_t v[7] = {p->hq_repack ? 1 : 0, p->hq_rp_last[0], p->hq_rp_last[1], p->hq_rp_last[2], p->hq_rp_last[3],
+                        turbo_pack_cap((p->d.max_frames + 63) / 64), p->hq_rp_last[4]};
+  for (int i = 0; i < n && i < 7; ++i) info[i] = v[i];
+  return 7;
+}
+
+int lte_harq_repack_rule(const uint8_t* acked, int64_t n_frames, int64_t cap, int64_t* out) {
+  if (!acked || !out) return fail(LTE_EINVAL, "null argument");
+  if (n_frames < 1 || cap < 1) return fail(LTE_EINVAL, "n_frames and cap must be >= 1");
+  const int64_t G = (n_frames + 63) / 64;
+  int64_t finished = 0, M = 0, A = 0;
+  for (int64_t g = 0; g < G; ++g) {
+    const int64_t valid = std::min<int64_t>(64, n_frames - 64 * g);
+    int64_t active = 0;
+    for (int64_t l = 0; l < valid; ++l) active += acked[64 * g + l] ? 0 : 1;
+    if (active == 0) ++finished;
+    else if (active < valid) { ++M; A += active; }
+  }
+  harq_repack_rule(G, finished, M, A, cap, out);
+  return LTE_OK;
+}
+
 int lte_timing_enable(lte_plan* p, int on) {
   if (!p) return fail(LTE_EINVAL, "null plan");
   p->timing = on != 0;
@@ -1433,6 +1498,7 @@ struct SisoPath {
   bool xhand;      // the TX hands its symbols to the paired receiver (TxChannelT::x_out)
   bool zn;         // (z, nv) hand-off to k_dematch_zn instead of LLRs
   bool hq_skip;    // HARQ round >= 1: the skip-aware decoders (k_turbo*_skip)
+  bool hq_repack;  // ... and the plan re-packs the unacknowledged frames of mixed groups where the rule says so
   bool fused() const { return tx != TX_NONE && tx != TX_SYM; }
 };
 
@@ -1463,6 +1529,7 @@ static SisoPath select_siso(const lte_plan* p, const lte_run_args* a, const Knob
   // receiver: fused (estimation + data path per frame) unless LTE_RX_FUSE=0
   s.zn = k.demap_in_dematch && demap_in_dematch(p, a);
   s.hq_skip = p->harq && p->hq_round >= 1 && do_rx && k.harq_skip && !logmap_on();
+  s.hq_repack = s.hq_skip && p->hq_repack;
   const bool rx_fuse = do_rx && k.rx_fuse;
   const bool rxf = rx_fuse && rx_fusable(p);
   const bool rxs = rx_fuse && !rxf && rx_simo_fusable(p);
@@ -1581,9 +1648,12 @@ static int capture_bufs(lte_plan* p, const lte_run_args* a, int B, size_t n_syms
 // HARQ (SISO only): add0 = 0 is round 0, which first zeroes the rows its map
 // leaves unwritten, add0 = 1 a later round, which adds to the rows' sums;
 // hq_skip: the skip-aware decoders; the groups they skipped go to hq_last[2].
+// hq_repack: a round whose counts (k_harq_repack_index's, read back with the
+// flags) satisfy harq_repack_rule decodes the full groups in place and the
+// active frames of the mixed groups in the plan's packed arrays.
 template <class R>
 static int decode_blocks(lte_plan* p, const lte_run_args* a, int B, const int32_t* rx_map, int nd, int nv_pairs,
-                         int add0, const SoftOut<R>& soft, const Scored& sc, bool hq_skip) {
+                         int add0, const SoftOut<R>& soft, const Scored& sc, bool hq_skip, bool hq_repack = false) {
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
   hipStream_t s = p->stream;
@@ -1606,18 +1676,61 @@ static int decode_blocks(lte_plan* p, const lte_run_args* a, int B, const int32_
   }
   // HARQ rounds >= 1: groups whose frames are all acknowledged return at once
   // (k_turbo*_skip read k_harq_latch's flags); none left: no decoder launch
-  const bool skip = hq_skip && (int)p->hq_skip_h.size() == G;
+  const bool indexed = p->hq_rp_G == G && (int)p->hq_skip_h.size() == 2 * G + 2;   // (flags, decoder flags, M, A)
+  const bool skip = hq_skip && (indexed || (int)p->hq_skip_h.size() == G);
   int nskip = 0;
   if (skip)
     for (int g = 0; g < G; ++g) nskip += p->hq_skip_h[g] ? 1 : 0;
   p->hq_last[2] = nskip;
-  if (!(skip && nskip == G)) {
+  const int f64 = sizeof(R) == 8 ? 1 : 0;
+  int64_t rule[6] = {0, 0, 0, 0, G - nskip, G - nskip};
+  if (p->hq_repack && p->harq && add0 && indexed)
+    harq_repack_rule(G, skip ? nskip : 0, p->hq_skip_h[2 * G], p->hq_skip_h[2 * G + 1],
+                     turbo_pack_cap((d.max_frames + 63) / 64), rule);
+  const bool pack = hq_repack && skip && indexed && rule[3] != 0;
+  if (p->hq_repack) {
+    const int64_t last[5] = {add0 ? (pack ? TURBO_RP_PACKED : TURBO_RP_INPLACE) : TURBO_RP_NONE, rule[0], rule[1],
+                             rule[2], pack ? rule[5] : G - nskip};
+    std::copy(last, last + 5, p->hq_rp_last);
+  }
+  if (pack) {
+    const int A = (int)rule[1], P = (int)rule[2], n_full = (int)(rule[5] - rule[2]);
+    const int pch = turbo_chunk(turbo_pack_cap((d.max_frames + 63) / 64));
+    std::vector<TurboJob> pj(p->C);
+    if (!p->pipe) p->pipe = std::make_unique<PipeStreams>();
+    if (!p->pipe->ensure(1)) return fail(LTE_EHIP, "HARQ re-packing stream");
+    {
+      Timer t(p, KN_HARQ);
+      for (int r = 0; r < p->C; ++r) {
+        LCHK(launch_harq_repack_gather<R>(s, c.blk[r].p, turbo_plan_ch(p), c.pk_blk[r].p, pch, p->cbs[r].K,
+                                          p->pk_idx[0].p, A));
+        pj[r] = TurboJob{c.pk_blk[r].p, c.pk_ckpt[r].p, p->pk_decb[r].p, jobs[r].K, jobs[r].f1, jobs[r].f2, P, pch};
+      }
+    }
+    {
+      // The packed groups decode on a second stream beside the full groups
+      // (the coded pipeline's first decoder stream: a HARQ plan never takes the
+      // pipeline).  One launch after the other would cost the few packed waves a
+      // whole wave's decode -- the floor of any decoder launch -- at the tail.
+      Timer t(p, KN_TURBO);
+      PipeStreams& ps = *p->pipe;
+      HIPCHK(hipEventRecord(ps.ready[0], s));                    // the packed rows are gathered
+      HIPCHK(hipStreamWaitEvent(ps.dec[0], ps.ready[0], 0));
+      LCHK(launch_turbo_jobs(ps.dec[0], pj.data(), p->C, d.turbo_iters, TM_DEC1, f64, nullptr, p->turbo_scale));
+      HIPCHK(hipEventRecord(ps.done[0], ps.dec[0]));
+      if (n_full > 0)   // the decoder flags leave out the finished and the mixed groups
+        LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, f64, p->hq_skip.p + G, p->turbo_scale));
+      HIPCHK(hipStreamWaitEvent(s, ps.done[0], 0));              // the join: scatter and CRC follow on the plan stream
+    }
+    Timer t(p, KN_HARQ);
+    for (int r = 0; r < p->C; ++r)
+      LCHK(launch_harq_repack_scatter(s, p->pk_decb[r].p, p->pk_idx[0].p, A, turbo_kw(jobs[r].K), jobs[r].bits));
+  } else if (!(skip && nskip == G)) {
     Timer t(p, KN_TURBO);
     if (skip)
-      LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, sizeof(R) == 8 ? 1 : 0, p->hq_skip.p,
-                             p->turbo_scale));
+      LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, f64, p->hq_skip.p, p->turbo_scale));
     else
-      LCHK(plan_launch_turbo(p, s, jobs, B, sizeof(R) == 8 ? 1 : 0));
+      LCHK(plan_launch_turbo(p, s, jobs, B, f64));
   }
   Timer t(p, KN_CRC);
   LCHK(launch_crc_count(s, p->cbi.p, p->C, p->dec_ptrs.p, p->kw_dev.p, B, sc, p->frame_crc.p,
@@ -2218,7 +2331,8 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
   if (coded && do_rx) {
     // HARQ: round 0 stores zeros in the rows its map does not cover (an earlier
     // process has left sums there), later rounds add to every row they cover
-    if (const int e = decode_blocks<R>(p, a, B, rx_map, p->Nd, 0, hq_t >= 1 ? 1 : 0, soft, sc, path.hq_skip))
+    if (const int e = decode_blocks<R>(p, a, B, rx_map, p->Nd, 0, hq_t >= 1 ? 1 : 0, soft, sc, path.hq_skip,
+                                       path.hq_repack))
       return e;
     if (p->harq) {
       {
@@ -2227,8 +2341,17 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
                                p->hq_skip.p));
       }
       const int G = (B + 63) / 64;
-      p->hq_skip_h.resize(G);
-      HIPCHK(hipMemcpyAsync(p->hq_skip_h.data(), p->hq_skip.p, G * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      // re-packing: the next round's frame index, decoder flags and {M, A}, read back with the latch's flags
+      const size_t n_flags = p->hq_repack ? 2 * (size_t)G + 2 : G;
+      if (p->hq_repack) {
+        Timer t(p, KN_HARQ);
+        LCHK(launch_harq_repack_index(s, p->hq_crc.p, B, p->pk_idx[0].p,
+                                      turbo_pack_cap((d.max_frames + 63) / 64) * 64, p->hq_skip.p + G,
+                                      p->hq_skip.p + 2 * G));
+      }
+      p->hq_rp_G = p->hq_repack ? G : -1;
+      p->hq_skip_h.resize(n_flags);
+      HIPCHK(hipMemcpyAsync(p->hq_skip_h.data(), p->hq_skip.p, n_flags * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
       p->hq_last[0] = hq_t;
       p->hq_last[1] = hq_rv;
       p->hq_done = hq_t;
@@ -2379,6 +2502,7 @@ int lte_run_path(const lte_plan* p, const lte_run_args* a, char* buf, int len) {
   if (p->harq && n >= 0 && n < len)
     n += std::snprintf(buf + n, len - n, " harq=t%d,rv%d,skip=%d", p->hq_round, p->hq.rv_seq[p->hq_round],
                        select_siso(p, a, knobs).hq_skip ? 1 : 0);
+  if (p->harq && p->hq_repack && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " harq_repack=1");
   if (p->turbo_scale != 1.0 && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " ext=%g", p->turbo_scale);
   return n < len ? n : len - 1;
 }

@@ -376,6 +376,29 @@ int launch_harq_zero(hipStream_t s, const int32_t* zmap, int nz, int G, R* const
 // round's.  skip [ceil(B / 64)]: 1 when no frame of the group is still active.
 int launch_harq_latch(hipStream_t s, int B, int t, uint32_t* frame_err, uint32_t* frame_crc, uint32_t* tx_used,
                       uint32_t* l_err, uint32_t* l_crc, uint32_t* skip);
+// HARQ re-packing (lte_plan_set_harq_repack; lte_turbo.hip).  index, after the
+// latch: idx [cap_lanes] the active frames of mixed groups in ascending order
+// (those that fit), flags [ceil(B / 64)] 1 = finished or mixed, ma {M, A}.
+// gather: the 3K + 12 decoder input rows of frames idx[0 .. n) from src (chunk
+// width sch) into ceil(n / 64) packed groups of dst (chunk width dch), lanes
+// past n zero.  scatter: the packed decision words back to the frames' own.
+int launch_harq_repack_index(hipStream_t s, const uint32_t* l_crc, int B, uint32_t* idx, int cap_lanes,
+                             uint32_t* flags, uint32_t* ma);
+template <class R>
+int launch_harq_repack_gather(hipStream_t s, const R* src, int sch, R* dst, int dch, int K, const uint32_t* idx,
+                              int n);
+int launch_harq_repack_scatter(hipStream_t s, const uint32_t* pbits, const uint32_t* idx, int n, int kw,
+                               uint32_t* bits);
+// The re-packing rule from a round's counts (lte_harq_repack_rule's core): G
+// groups of which `finished` are finished, M mixed with A active frames in all.
+// out: M, A, P, pack, decoder groups per slot without / with re-packing.
+inline void harq_repack_rule(int64_t G, int64_t finished, int64_t M, int64_t A, int64_t cap, int64_t* out) {
+  const int64_t P = (A + 63) / 64, off = G - finished;
+  const bool pack = M >= 1 && P < M && P <= cap;
+  out[0] = M; out[1] = A; out[2] = P; out[3] = pack ? 1 : 0;
+  out[4] = off;
+  out[5] = pack ? off - M + P : off;
+}
 // f64 != 0: the float64 decoder (bit-exact with the reference), blk / ckpt hold doubles
 // scale (here and in the launchers below): the extrinsic scaling of
 // lte_plan_set_turbo_scale (lte_phy.h), 0 < scale <= 1.  1 launches the kernels

@@ -251,6 +251,18 @@ struct Plan {
   std::vector<uint32_t> hq_skip_h;   // hq_skip after the last round
   DBuf<int32_t> hq_zmap;             // decoder input rows (r << 24 | row) rv_seq[0]'s map leaves unwritten
   int hq_nz = 0;
+  // Re-packing of the unacknowledged frames (lte_plan_set_harq_repack).  While
+  // it is on, hq_skip holds [G] k_harq_latch's flags, [G] k_harq_repack_index's
+  // decoder flags (finished or mixed) and {M, A} (G = the round's groups), and
+  // hq_skip_h is that whole array; hq_rp_G: the groups of the last round that
+  // indexed (-1: none since round 0 opened / the setting changed).  The packed
+  // arrays are early-stop re-packing's (pk_blk / pk_ckpt, pk_decb; pk_idx[0]
+  // the frame index); hq_rp_last: the last run's (state, M, A, P, waves).  A
+  // round that packs decodes the packed groups on pipe->dec[0] (made on first
+  // use; a HARQ plan never runs the coded pipeline)
+  bool hq_repack = false;
+  int hq_rp_G = -1;
+  int64_t hq_rp_last[5] = {0, 0, 0, 0, 0};
   // the chain's row of lte_chain.h (plan_create); mimo / bf: its family is run_mimo's / run_bf's
   const ChainTraits* ct = nullptr;
   bool mimo = false, bf = false;

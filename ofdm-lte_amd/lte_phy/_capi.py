@@ -98,6 +98,10 @@ _SIGS = {
     'lte_plan_harq_tx_used': (ctypes.c_int, [ctypes.c_void_p, P(ctypes.c_uint8), c_i64]),
     'lte_plan_harq_info': (ctypes.c_int, [ctypes.c_void_p, P(c_i64), ctypes.c_int]),
     'lte_harq_code_block_bits': (ctypes.c_int, [c_i32, c_i32, c_i64, P(c_i32), P(c_i32), c_i32]),
+    'lte_plan_set_harq_repack': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'lte_plan_harq_repack': (ctypes.c_int, [ctypes.c_void_p]),
+    'lte_plan_harq_repack_info': (ctypes.c_int, [ctypes.c_void_p, P(c_i64), ctypes.c_int]),
+    'lte_harq_repack_rule': (ctypes.c_int, [P(ctypes.c_uint8), c_i64, c_i64, P(c_i64)]),
     'lte_timing_enable': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'lte_timing_read': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, P(c_f64), P(c_i64),
                                        ctypes.c_int]),
@@ -290,6 +294,18 @@ def coded_pipe_slices(groups, chunk, pipe_groups):
     out = np.zeros((n, 2), dtype=np.int32)
     check(load().lte_coded_pipe_slices(int(groups), int(chunk), int(pipe_groups), ptr(out, ctypes.c_int32), n))
     return [(int(a), int(b)) for a, b in out]
+
+
+def harq_repack_rule(acked, cap):
+    """HARQ re-packing's rule for the frames' acknowledgements `acked` (non-zero:
+    acknowledged) and `cap` packed groups (lte_harq_repack_rule; no device
+    needed): M, A, P, whether the round packs, and the decoder groups per code
+    block slot without / with re-packing."""
+    a = np.ascontiguousarray(np.asarray(acked) != 0, dtype=np.uint8)
+    out = np.zeros(6, dtype=np.int64)
+    check(load().lte_harq_repack_rule(ptr(a, ctypes.c_uint8), len(a), int(cap), ptr(out, c_i64)))
+    return {'M': int(out[0]), 'A': int(out[1]), 'P': int(out[2]), 'pack': bool(out[3]), 'waves_off': int(out[4]),
+            'waves_on': int(out[5])}
 
 
 def pilots(cell_id, n):

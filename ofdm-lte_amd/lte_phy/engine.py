@@ -69,7 +69,9 @@ class Plan:
     def __init__(self, *, N, Nc, cp_len, bps, n_sym, chain, channel, num_rx=1, delays=(), gains=(), fD=0.0,
                  fs=0.0, n_bits, turbo_iters=8, max_frames=1, cell_id=0, num_tx=1, rank=0, detector=0,
                  precoder=(), sc_fdm=0, bf_adaptive=0, no_equalization=0, precision=None, early_stop=False,
-                 harq=None, repack=None, turbo_scale=None):
+                 harq=None, harq_repack=False, repack=None, turbo_scale=None):
+        if harq_repack and harq is None:   # before any device call
+            raise ValueError('harq_repack re-packs the unacknowledged frames of a HARQ process: it needs harq=')
         after = repack_boundary(repack, early_stop, turbo_iters)   # before any device call
         scale = turbo_scale_value(turbo_scale)                     # likewise
         C.device_init()
@@ -161,6 +163,11 @@ class Plan:
         # extrinsic scaling of the decoders (lte_plan_set_turbo_scale; coded chains only; 1.0: off)
         if scale != 1.0:
             self.set_turbo_scale(scale)
+        # re-packing of the unacknowledged frames of mixed decoder groups (lte_plan_set_harq_repack;
+        # HARQ plans only): run() then also returns 'harq_repack_info'
+        self.harq_repack = False
+        if harq_repack:
+            self.set_harq_repack(True)
 
     def __del__(self):
         try:
@@ -188,6 +195,8 @@ class Plan:
             C.check(C.load().lte_plan_harq_tx_used(self.h, C.ptr(used, C.U8), used.size))
             out['tx_used'] = used
             out['harq_info'] = self.harq_info()
+            if self.harq_repack:
+                out['harq_repack_info'] = self.harq_repack_info()
         del keep
         return out
 
@@ -241,22 +250,42 @@ class Plan:
         return {'max_tx': int(v[0]), 'round': int(v[1]), 'rv': int(v[2]), 'skipped': int(v[3]),
                 'coded_bits': int(v[4]), 'n_cb': int(v[5]), 'E': [int(e) for e in v[6:]]}
 
+    def set_harq_repack(self, on):
+        """Switch the re-packing of unacknowledged frames on or off
+        (lte_plan_set_harq_repack); the packed arrays stay allocated."""
+        if self.harq is None:
+            raise ValueError('harq_repack needs a plan made with harq=')
+        C.check(C.load().lte_plan_set_harq_repack(self.h, 1 if on else 0))
+        self.harq_repack = bool(on)
+
+    def harq_repack_info(self):
+        """lte_plan_harq_repack_info of the last run as a dict: on, state ('none':
+        round 0 / 'packed' / 'in_place'), M (mixed groups), A (their active
+        frames), P (packed groups), cap and waves (decoder groups run per slot)."""
+        v = np.zeros(7, dtype=np.int64)
+        C.check(C.load().lte_plan_harq_repack_info(self.h, C.ptr(v, C.c_i64), len(v)))
+        return {'on': bool(v[0]), 'state': REPACK_STATES[int(v[1])], 'M': int(v[2]), 'A': int(v[3]), 'P': int(v[4]),
+                'cap': int(v[5]), 'waves': int(v[6])}
+
     def run_harq(self, snr_db, **kw):
         """One HARQ process: the rounds 0 .. max_tx - 1 with the same arguments,
         stopping after the first round that leaves no frame unacknowledged.
         Returns tx_used / crc_ok / frame_errors (latched), counts (after the
         last round run), counts_by_round [max_tx, n_snr, 4] (rounds not run
         repeat the last), rounds_run, skipped (decoder groups per round run),
-        and with capture= a list `rounds` of each round's captures."""
+        with capture= a list `rounds` of each round's captures, and with
+        harq_repack on the per-round list harq_repack_info."""
         if self.harq is None:
             raise ValueError('run_harq needs a plan made with harq=')
         capture = tuple(kw.get('capture', ()))
-        cbr, rounds, skipped, r = [], [], [], None
+        cbr, rounds, skipped, packs, r = [], [], [], [], None
         for t in range(self.harq['max_tx']):
             self.harq_round(t)
             r = self.run(snr_db, **kw)
             cbr.append(r['counts'].copy())
             skipped.append(r['harq_info']['skipped'])
+            if self.harq_repack:
+                packs.append(r['harq_repack_info'])
             if capture:
                 rounds.append({k: r[k] for k in capture})
             if bool(np.all(r['crc_ok'] != 0)):
@@ -267,6 +296,8 @@ class Plan:
         out.path = r.path
         if capture:
             out['rounds'] = rounds
+        if self.harq_repack:
+            out['harq_repack_info'] = packs
         return out
 
     def path(self, snr_db, **kw):
@@ -408,6 +439,7 @@ def plan_key(**kw):
     kw['harq'] = None if hq is None else tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple, np.ndarray)) else v)
                                                       for k, v in dict(hq).items()))
     kw['turbo_scale'] = turbo_scale_value(kw.get('turbo_scale'))   # likewise (None and 1 are one plan)
+    kw['harq_repack'] = bool(kw.get('harq_repack', False))   # likewise: a re-packing plan is never a plain HARQ one
     key = tuple(sorted((k, tuple(v) if isinstance(v, (list, tuple, np.ndarray)) else v) for k, v in kw.items()))
     return key, kw
 

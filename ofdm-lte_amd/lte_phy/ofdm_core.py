@@ -541,7 +541,7 @@ class OFDMSimulator:
         return len(self.grid._data)
 
     def _plan(self, chain, n_sym, n_bits, num_rx=1, max_frames=1, iters=8, early_stop=False, harq=None, detector=0,
-              repack=None):
+              repack=None, harq_repack=False):
         """SC-FDM (enable_sc_fdm / mode 'sc-fdm') reaches the uncoded SISO / SIMO
         transmitters and the SISO receiver; simulate_siso_coded ignores it, as
         the reference does (lte_plan_desc.sc_fdm, include/lte_phy.h).  The coded
@@ -555,7 +555,7 @@ class OFDMSimulator:
                         chain=chain, channel=ch.kind, num_rx=num_rx, delays=tuple(ch.delays),
                         gains=tuple(ch.gains), fD=ch.fD, fs=cfg.fs, n_bits=n_bits, turbo_iters=iters,
                         max_frames=max_frames, sc_fdm=sc, no_equalization=noeq, precision=self.precision,
-                        early_stop=early_stop, harq=harq, detector=detector, repack=repack,
+                        early_stop=early_stop, harq=harq, detector=detector, repack=repack, harq_repack=harq_repack,
                         turbo_scale=self.turbo_scale if C.chain_info(chain).coded else None)
 
     def _ref_draws(self, L, num_rx=1):
@@ -997,7 +997,8 @@ class OFDMSimulator:
         return _run_plan_grid(plan, snrs, T, seed, frames_per_call, rank, world_size, turbo_iters, early_stop)
 
     def run_harq_grid(self, snr_range, num_trials, seed=0, n_bits=None, coded_bits=None, max_tx=4,
-                      rv_seq=(0, 2, 3, 1), frames_per_call=4096, rank=0, world_size=1, turbo_iters=8, **other):
+                      rv_seq=(0, 2, 3, 1), frames_per_call=4096, rank=0, world_size=1, turbo_iters=8, *, repack=False,
+                      **other):
         """HARQ curve of the coded SISO chain on the device: every (SNR, trial)
         frame is sent up to max_tx times, transmission t with redundancy version
         rv_seq[t] and `coded_bits` coded bits (None / 0: 3K + 12 per code block),
@@ -1011,9 +1012,11 @@ class OFDMSimulator:
         0 = never), both all-reducible; bler_by_tx [S, max_tx]; mean_tx [S];
         throughput [S] = n_bits * acknowledged / transmissions; code_rate =
         (n_bits + 24) / coded bits sent; plan.  Only the coded SISO chain: the
-        run_grid keywords coded=False, num_rx > 1 or mimo= raise ValueError."""
+        run_grid keywords coded=False, num_rx > 1 or mimo= raise ValueError.
+        repack=True (keyword only): the plan re-packs the unacknowledged frames of
+        mixed decoder groups (lte_plan_set_harq_repack); the tables are the same."""
         return _harq_grid(self, snr_range, num_trials, seed, n_bits, coded_bits, max_tx, rv_seq, frames_per_call,
-                          rank, world_size, turbo_iters, other)
+                          rank, world_size, turbo_iters, other, bool(repack))
 
     @_takes_repack
     def run_scfdm_grid(self, snr_range, num_trials, seed=0, num_rx=1, equalizer='mmse', n_bits=None,
@@ -1058,7 +1061,7 @@ def _run_plan_grid(plan, snrs, T, seed, frames_per_call, rank, world_size, turbo
 
 
 def _harq_grid(sim, snr_range, num_trials, seed, n_bits, coded_bits, max_tx, rv_seq, frames_per_call, rank,
-               world_size, turbo_iters, other):
+               world_size, turbo_iters, other, repack=False):
     """OFDMSimulator.run_harq_grid's body."""
     bad = {k: v for k, v in other.items()
            if not ((k == 'coded' and v is True) or (k == 'num_rx' and v == 1) or (k == 'mimo' and v is None))}
@@ -1077,7 +1080,7 @@ def _harq_grid(sim, snr_range, num_trials, seed, n_bits, coded_bits, max_tx, rv_
     Kc, Ec = np.zeros(32, dtype=np.int32), np.zeros(32, dtype=np.int32)
     C.check(C.load().lte_harq_code_block_bits(nb, cfg.bits_per_symbol, G, C.ptr(Kc, C.I32), C.ptr(Ec, C.I32), 32))
     plan = sim._plan(C.CHAIN_CODED, 0, nb, max_frames=frames_per_call, iters=turbo_iters,
-                     harq=dict(max_tx=max_tx, rv_seq=rv_seq[:max_tx], coded_bits=G))
+                     harq=dict(max_tx=max_tx, rv_seq=rv_seq[:max_tx], coded_bits=G), harq_repack=repack)
     ids = np.array([s * T + t for s in range(S) for t in trial_shard(T, rank, world_size)], dtype=np.uint64)
     cbr = np.zeros((S, max_tx, 4), dtype=np.uint64)
     hist = np.zeros((S, max_tx + 1), dtype=np.uint64)
