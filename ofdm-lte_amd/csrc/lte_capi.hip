@@ -346,46 +346,53 @@ template <> ChainBufs<double>& cbuf<double>(lte_plan* p) { return p->c64; }
 // chunk width of the plan's decoder rows (allocated for ceil(max_frames / 64) groups)
 int turbo_plan_ch(const lte_plan* p) { return turbo_chunk((p->d.max_frames + 63) / 64); }
 
-// the plan's decoder launch: turbo_iters iterations, or (early_stop) until each
-// code block's CRC-24 holds -- gCRC24A for a transport block of one code block,
-// gCRC24B for several (segmentation.py:74-263)
-int plan_launch_turbo(lte_plan* p, hipStream_t s, const std::vector<TurboJob>& jobs, int B, int f64) {
-  const double sc = p->turbo_scale;
-  if (!p->early_stop) return launch_turbo_jobs(s, jobs.data(), p->C, p->d.turbo_iters, TM_DEC1, f64, nullptr, sc);
-  std::vector<uint32_t*> used(p->C);
-  std::vector<int> nv(p->C, B);
-  for (int r = 0; r < p->C; ++r) used[r] = p->es_used[r].p;
-  p->es_frames = B;
-  const uint32_t poly = p->C == 1 ? CRC24A_POLY : CRC24B_POLY;
-  if (!p->repack_after)
-    return launch_turbo_jobs_es(s, jobs.data(), used.data(), nv.data(), p->C, p->d.turbo_iters, f64, poly, nullptr,
-                                sc);
-  // re-packing: the undecided blocks continue in the plan's packed arrays
-  std::vector<TurboPack> pk(p->C);
-  const int cap = turbo_pack_cap((p->d.max_frames + 63) / 64);
+// groups of the plan's packed set (either re-packing)
+static int plan_pack_cap(const lte_plan* p) { return turbo_pack_cap((p->d.max_frames + 63) / 64); }
+
+// the decoder jobs of the plan's CB slots over groups g0 .. g0 + G (g0 a multiple of the chunk width)
+template <class R>
+static std::vector<TurboJob> plan_jobs(lte_plan* p, ChainBufs<R>& c, int g0, int G) {
+  const int ch = turbo_plan_ch(p);
+  std::vector<TurboJob> jobs(p->C);
   for (int r = 0; r < p->C; ++r) {
-    void* pb = f64 ? (void*)p->c64.pk_blk[r].p : (void*)p->c32.pk_blk[r].p;
-    void* pc = f64 ? (void*)p->c64.pk_ckpt[r].p : (void*)p->c32.pk_ckpt[r].p;
-    pk[r] = TurboPack{pb, pc, p->pk_decb[r].p, p->pk_used[r].p, p->pk_idx[r].p, cap};
+    const CbInfo& cb = p->cbs[r];
+    const int64_t ck_rows = (int64_t)turbo_nwin(cb.K) * turbo_ck_rows(sizeof(R) == 8);
+    jobs[r] = TurboJob{c.blk[r].p + turbo_elem_ch(ch, turbo_rows(cb.K), g0, 0),
+                       c.ckpt[r].p + turbo_elem_ch(ch, ck_rows, g0, 0),
+                       p->decb[r].p + (size_t)g0 * turbo_kw(cb.K) * TURBO_RS, cb.K, cb.f1, cb.f2, G, ch};
   }
-  p->rp_last.assign((size_t)3 * p->C, 0);
-  return launch_turbo_jobs_es_repack(s, jobs.data(), used.data(), nv.data(), p->C, p->d.turbo_iters, f64, poly,
-                                     p->repack_after, pk.data(), p->rp_cnt.p, p->rp_last.data(), sc);
+  return jobs;
 }
 
-// the packed rows / checkpoints of re-packing, cap groups per CB slot (true: out of memory)
+// The early-stop decode of a run: until each code block's CRC-24 holds --
+// gCRC24A for a transport block of one code block, gCRC24B for several
+// (segmentation.py:74-263) -- with the undecided blocks continuing in the
+// plan's packed set past the boundary where repack is set
 template <class R>
-bool alloc_packed(lte_plan* p, ChainBufs<R>& c, int cap) {
-  bool bad = false;
-  c.pk_blk.resize(p->C);
-  c.pk_ckpt.resize(p->C);
-  for (int r = 0; r < p->C; ++r) {
-    const int K = p->cbs[r].K;
-    bad |= c.pk_blk[r].alloc((size_t)turbo_galloc(cap) * turbo_rows(K) * 64) != 0;
-    bad |= c.pk_ckpt[r].alloc((size_t)turbo_galloc(cap) * turbo_nwin(K) * turbo_ck_rows(sizeof(R) == 8) * 64) != 0;
-  }
-  return bad;
+static int plan_launch_turbo_es(lte_plan* p, hipStream_t s, const std::vector<TurboJob>& jobs, int B, bool repack) {
+  const int f64 = sizeof(R) == 8 ? 1 : 0;
+  std::vector<uint32_t*> used(p->C);
+  std::vector<int> nv(p->C, B);
+  for (int r = 0; r < p->C; ++r) used[r] = p->es.used[r].p;
+  p->es.frames = B;
+  const uint32_t poly = p->C == 1 ? CRC24A_POLY : CRC24B_POLY;
+  if (!repack)
+    return launch_turbo_jobs_es(s, jobs.data(), used.data(), nv.data(), p->C, p->d.turbo_iters, f64, poly, nullptr,
+                                p->scale.ext);
+  std::vector<TurboPack> pk(p->C);
+  for (int r = 0; r < p->C; ++r) pk[r] = cbuf<R>(p).pk.pack(r);
+  p->es.rp_last.assign((size_t)3 * p->C, 0);
+  return launch_turbo_jobs_es_repack(s, jobs.data(), used.data(), nv.data(), p->C, p->d.turbo_iters, f64, poly,
+                                     p->es.repack_after, pk.data(), p->es.rp_cnt.p, p->es.rp_last.data(),
+                                     p->scale.ext);
 }
+
+// the plan's packed set: cap groups per CB slot (false: out of memory, nothing is held)
+static bool plan_alloc_pack(lte_plan* p, bool want_used, size_t idx_slots) {
+  const int cap = plan_pack_cap(p);
+  return p->f64 ? p->c64.pk.alloc(cap, p->cbs, want_used, idx_slots) : p->c32.pk.alloc(cap, p->cbs, want_used, idx_slots);
+}
+static bool plan_has_pack(const lte_plan* p) { return (p->f64 ? p->c64.pk.cap : p->c32.pk.cap) != 0; }
 
 void collect_timing(lte_plan* p) {
   for (auto& u : p->evuse) {
@@ -589,8 +596,8 @@ static int plan_coded_maps(lte_plan* p, const Knobs& k) {
   const lte_plan_desc& d = p->d;
   if (!segmentation_plan(d.n_bits + 24, p->cbs)) return fail(LTE_EINVAL, "No valid interleaver size");
   p->C = (int)p->cbs.size();
-  if (p->harq) {
-    const int e = harq_split(p->cbs, d.bps, p->hq.G);
+  if (p->hq.on) {
+    const int e = harq_split(p->cbs, d.bps, p->hq.desc.G);
     if (e) return e;
   }
   int Kmax = 0;
@@ -627,10 +634,10 @@ static int plan_coded_maps(lte_plan* p, const Knobs& k) {
   // one (tx_map, rx_map) pair per redundancy version in use, back to back: a
   // plain plan's rv 0, a HARQ plan's distinct rv_seq entries in order of first use
   std::vector<int> rvs;
-  for (int t = 0; t < (p->harq ? p->hq.max_tx : 1); ++t) {
-    const int rv = p->harq ? p->hq.rv_seq[t] : 0;
+  for (int t = 0; t < (p->hq.on ? p->hq.desc.max_tx : 1); ++t) {
+    const int rv = p->hq.on ? p->hq.desc.rv_seq[t] : 0;
     if (std::find(rvs.begin(), rvs.end(), rv) == rvs.end()) {
-      p->hq_slot[rv] = (int)rvs.size();
+      p->hq.slot[rv] = (int)rvs.size();
       rvs.push_back(rv);
     }
   }
@@ -683,7 +690,7 @@ static int plan_coded_maps(lte_plan* p, const Knobs& k) {
       }
     }
   }
-  if (p->harq) {   // the rows round 0 has to zero: every decoder input row its map (slot 0) does not write
+  if (p->hq.on) {   // the rows round 0 has to zero: every decoder input row its map (slot 0) does not write
     std::vector<int32_t> zm;
     std::vector<std::vector<char>> hit(p->C);
     for (int r = 0; r < p->C; ++r) hit[r].assign((size_t)turbo_rows(p->cbs[r].K), 0);
@@ -697,8 +704,8 @@ static int plan_coded_maps(lte_plan* p, const Knobs& k) {
       for (int i = 0; i < K + 3; ++i) { need(trow_ls(K, i)); need(trow_lp(K, 1, i)); need(trow_lp(K, 2, i)); }
       for (int j = 0; j < 3; ++j) need(trow_ls2t(K, j));
     }
-    p->hq_nz = (int)zm.size();
-    if (upload(p->hq_zmap, zm)) return fail(LTE_ENOMEM, "map upload failed");
+    p->hq.nz = (int)zm.size();
+    if (upload(p->hq.zmap, zm)) return fail(LTE_ENOMEM, "map upload failed");
   }
   p->qstride = Kmax + 32;
   std::vector<uint16_t> qm((size_t)p->C * p->qstride, 0);
@@ -711,7 +718,7 @@ static int plan_coded_maps(lte_plan* p, const Knobs& k) {
   // instruction but not the kernel time (15.34 ms with it, 15.17 without,
   // DESIGN.md §5 round 4), and its greedy search costs plan-create time on every
   // plan-cache miss.  LTE_TXF_LANE_ORDER=1 turns it on.
-  if (p->res == p->Nd && d.N >= 512 && p->Nd <= d.N / 2 && k.txf_lane_order && !p->harq) {
+  if (p->res == p->Nd && d.N >= 512 && p->Nd <= d.N / 2 && k.txf_lane_order && !p->hq.on) {
     std::vector<int32_t> tfm, tfr;
     plan_txf_lane_order(txm, p->gh.data, p->n_sym, Nd, bps, d.N / 2, tfm, tfr, p->txf_model);
     if (k.txf_lane_order_report)
@@ -987,8 +994,8 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
   p->bf = bf;
   p->f64 = d.precision != LTE_PREC_F32;
   if (harq) {
-    p->harq = true;
-    p->hq = *harq;
+    p->hq.on = true;
+    p->hq.desc = *harq;
   }
   const bool coded = ct.coded;
   if (coded && d.turbo_iters < 0) return fail(LTE_EINVAL, "bad turbo_iters");
@@ -1086,10 +1093,10 @@ static int plan_create(const lte_plan_desc* desc, const lte_harq_desc* harq, lte
   rc = plan_alloc(p);
   if (rc) return rc;
   if (p->counts.alloc(4 * 64)) return fail(LTE_ENOMEM, "counts");
-  if (p->harq) {
+  if (p->hq.on) {
     const size_t B = (size_t)d.max_frames;
-    if (p->hq_tx_used.alloc(B) || p->hq_err.alloc(B) || p->hq_crc.alloc(B) ||
-        p->hq_skip.alloc((B + 63) / 64) || hipMemset(p->hq_tx_used.p, 0, B * sizeof(uint32_t)) != hipSuccess)
+    if (p->hq.tx_used.alloc(B) || p->hq.err.alloc(B) || p->hq.crc.alloc(B) ||
+        p->hq.skip.alloc((B + 63) / 64) || hipMemset(p->hq.tx_used.p, 0, B * sizeof(uint32_t)) != hipSuccess)
       return fail(LTE_ENOMEM, "HARQ state");
   }
   *out = own.release();
@@ -1151,64 +1158,48 @@ int lte_plan_precision(const lte_plan* p) {
 
 int lte_plan_set_early_stop(lte_plan* p, int on) {
   if (!p) return fail(LTE_EINVAL, "null plan");
-  if (p->harq) return fail(LTE_EUNSUP, "CRC early termination is not combined with HARQ");
+  if (p->hq.on) return fail(LTE_EUNSUP, "CRC early termination is not combined with HARQ");
   if (!p->ct->coded)
     return fail(LTE_EINVAL, "early stop applies to the coded chains only (nothing is decoded in this plan)");
-  if (on && p->es_used.empty()) {
+  if (on && p->es.used.empty()) {
     std::vector<DBuf<uint32_t>> u(p->C);
     const size_t G = ((size_t)p->d.max_frames + 63) / 64;
     bool bad = false;
     for (auto& b : u) bad |= b.alloc(G * 64) != 0;
     if (bad) return fail(LTE_ENOMEM, "early-stop iteration counts");
-    p->es_used.swap(u);
+    p->es.used.swap(u);
   }
   if (on && p->d.turbo_iters > 255) return fail(LTE_EUNSUP, "early stop reports iterations as bytes: turbo_iters <= 255");
-  p->early_stop = on != 0;
-  p->es_frames = 0;
-  if (!on) p->repack_after = 0;
+  p->es.on = on != 0;
+  p->es.frames = 0;
+  if (!on) p->es.repack_after = 0;
   return LTE_OK;
 }
 
 int lte_plan_set_early_stop_repack(lte_plan* p, int after) {
   if (!p) return fail(LTE_EINVAL, "null plan");
-  if (!p->early_stop) return fail(LTE_EINVAL, "re-packing needs early stop (lte_plan_set_early_stop) on this plan");
+  if (!p->es.on) return fail(LTE_EINVAL, "re-packing needs early stop (lte_plan_set_early_stop) on this plan");
   if (after < 0 || after >= p->d.turbo_iters)
     return fail(LTE_EINVAL, "re-packing boundary must be in 1..turbo_iters-1 (0 switches it off): after = " +
                                 std::to_string(after) + ", turbo_iters = " + std::to_string(p->d.turbo_iters));
-  if (after && p->pk_decb.empty()) {
-    const int cap = turbo_pack_cap((p->d.max_frames + 63) / 64);
-    std::vector<DBuf<uint32_t>> b(p->C), u(p->C), x(p->C);
-    bool bad = p->f64 ? alloc_packed(p, p->c64, cap) : alloc_packed(p, p->c32, cap);
-    for (int r = 0; r < p->C; ++r) {
-      bad |= b[r].alloc((size_t)cap * turbo_kw(p->cbs[r].K) * 64) != 0;
-      bad |= u[r].alloc((size_t)cap * 64) != 0;
-      bad |= x[r].alloc((size_t)cap * 64) != 0;
-    }
-    bad |= p->rp_cnt.alloc(p->C) != 0;
-    if (bad) {
-      p->c64.pk_blk.clear(); p->c64.pk_ckpt.clear();
-      p->c32.pk_blk.clear(); p->c32.pk_ckpt.clear();
-      return fail(LTE_ENOMEM, "re-packing arrays");
-    }
-    p->pk_decb.swap(b);
-    p->pk_used.swap(u);
-    p->pk_idx.swap(x);
+  if (after && !plan_has_pack(p)) {   // the packed set with counts and an index per slot, and the slots' totals
+    if (p->es.rp_cnt.alloc(p->C) || !plan_alloc_pack(p, true, p->C)) return fail(LTE_ENOMEM, "re-packing arrays");
   }
-  p->repack_after = after;
-  p->rp_last.assign((size_t)3 * p->C, 0);
+  p->es.repack_after = after;
+  p->es.rp_last.assign((size_t)3 * p->C, 0);
   return LTE_OK;
 }
 
 int lte_plan_early_stop_repack(const lte_plan* p) {
   if (!p) return fail(LTE_EINVAL, "null plan");
-  return p->repack_after;
+  return p->es.repack_after;
 }
 
 int lte_plan_repack_info(const lte_plan* p, int64_t* info, int n) {
   if (!p || !info) return fail(LTE_EINVAL, "null argument");
-  if (!p->repack_after) return fail(LTE_EINVAL, "re-packing is off for this plan");
-  std::vector<int64_t> v = {p->repack_after, p->C};
-  for (int i = 0; i < 3 * p->C; ++i) v.push_back(i < (int)p->rp_last.size() ? p->rp_last[i] : 0);
+  if (!p->es.repack_after) return fail(LTE_EINVAL, "re-packing is off for this plan");
+  std::vector<int64_t> v = {p->es.repack_after, p->C};
+  for (int i = 0; i < 3 * p->C; ++i) v.push_back(i < (int)p->es.rp_last.size() ? p->es.rp_last[i] : 0);
   for (int i = 0; i < n && i < (int)v.size(); ++i) info[i] = v[i];
   return (int)v.size();
 }
@@ -1231,7 +1222,7 @@ int lte_plan_set_turbo_scale(lte_plan* p, double scale) {
   if (!p->ct->coded)
     return fail(LTE_EINVAL, "extrinsic scaling applies to the coded chains only (nothing is decoded in this plan)");
   if (!(scale > 0.0 && scale <= 1.0)) return fail(LTE_EINVAL, "turbo scale must be in (0, 1]");
-  p->turbo_scale = scale;
+  p->scale.ext = scale;
   return LTE_OK;
 }
 
@@ -1240,24 +1231,24 @@ double lte_plan_turbo_scale(const lte_plan* p) {
     fail(LTE_EINVAL, "null plan");
     return (double)NAN;
   }
-  return p->turbo_scale;
+  return p->scale.ext;
 }
 
 int lte_plan_early_stop(const lte_plan* p) {
   if (!p) return fail(LTE_EINVAL, "null plan");
-  return p->early_stop ? 1 : 0;
+  return p->es.on ? 1 : 0;
 }
 
 int lte_plan_turbo_iters_used(const lte_plan* p, uint8_t* out, int64_t n) {
   if (!p || !out) return fail(LTE_EINVAL, "null argument");
-  if (!p->early_stop) return fail(LTE_EINVAL, "early stop is off for this plan");
-  if (p->es_frames <= 0) return fail(LTE_EINVAL, "no decoded run since early stop was set");
-  const int B = p->es_frames;
+  if (!p->es.on) return fail(LTE_EINVAL, "early stop is off for this plan");
+  if (p->es.frames <= 0) return fail(LTE_EINVAL, "no decoded run since early stop was set");
+  const int B = p->es.frames;
   if (n != (int64_t)B * p->C)
     return fail(LTE_EINVAL, "n must be n_frames * n_cb of the last run (" + std::to_string((int64_t)B * p->C) + ")");
   std::vector<uint32_t> h(B);
   for (int r = 0; r < p->C; ++r) {
-    HIPCHK(hipMemcpy(h.data(), p->es_used[r].p, (size_t)B * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h.data(), p->es.used[r].p, (size_t)B * sizeof(uint32_t), hipMemcpyDeviceToHost));
     for (int b = 0; b < B; ++b) out[(size_t)b * p->C + r] = (uint8_t)h[b];
   }
   return LTE_OK;
@@ -1265,33 +1256,33 @@ int lte_plan_turbo_iters_used(const lte_plan* p, uint8_t* out, int64_t n) {
 
 int lte_plan_harq_set_round(lte_plan* p, int t) {
   if (!p) return fail(LTE_EINVAL, "null plan");
-  if (!p->harq) return fail(LTE_EINVAL, "not a HARQ plan");
-  if (t < 0 || t >= p->hq.max_tx)
+  if (!p->hq.on) return fail(LTE_EINVAL, "not a HARQ plan");
+  if (t < 0 || t >= p->hq.desc.max_tx)
     return fail(LTE_EINVAL, "HARQ: round " + std::to_string(t) + " outside 0..max_tx-1 (max_tx = " +
-                                std::to_string(p->hq.max_tx) + ")");
-  if (t > 0 && t != p->hq_done + 1)
+                                std::to_string(p->hq.desc.max_tx) + ")");
+  if (t > 0 && t != p->hq.done + 1)
     return fail(LTE_EINVAL, "HARQ: round " + std::to_string(t) + " must follow the last completed round (" +
-                                std::to_string(p->hq_done) + ")");
-  p->hq_round = t;
+                                std::to_string(p->hq.done) + ")");
+  p->hq.round = t;
   return LTE_OK;
 }
 
 int lte_plan_harq_tx_used(const lte_plan* p, uint8_t* out, int64_t n) {
   if (!p || !out) return fail(LTE_EINVAL, "null argument");
-  if (!p->harq) return fail(LTE_EINVAL, "not a HARQ plan");
-  if (p->hq_done < 0) return fail(LTE_EINVAL, "HARQ: no completed round");
-  if (n != (int64_t)p->hq_fids.size())
-    return fail(LTE_EINVAL, "n must be the process's n_frames (" + std::to_string(p->hq_fids.size()) + ")");
+  if (!p->hq.on) return fail(LTE_EINVAL, "not a HARQ plan");
+  if (p->hq.done < 0) return fail(LTE_EINVAL, "HARQ: no completed round");
+  if (n != (int64_t)p->hq.fids.size())
+    return fail(LTE_EINVAL, "n must be the process's n_frames (" + std::to_string(p->hq.fids.size()) + ")");
   std::vector<uint32_t> h((size_t)n);
-  HIPCHK(hipMemcpy(h.data(), p->hq_tx_used.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(h.data(), p->hq.tx_used.p, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   for (int64_t b = 0; b < n; ++b) out[b] = (uint8_t)h[b];
   return LTE_OK;
 }
 
 int lte_plan_harq_info(const lte_plan* p, int64_t* info, int n) {
   if (!p || !info) return fail(LTE_EINVAL, "null argument");
-  if (!p->harq) return fail(LTE_EINVAL, "not a HARQ plan");
-  std::vector<int64_t> v = {p->hq.max_tx, p->hq_last[0], p->hq_last[1], p->hq_last[2], p->coded_len, p->C};
+  if (!p->hq.on) return fail(LTE_EINVAL, "not a HARQ plan");
+  std::vector<int64_t> v = {p->hq.desc.max_tx, p->hq.last[0], p->hq.last[1], p->hq.last[2], p->coded_len, p->C};
   for (int r = 0; r < p->C; ++r) v.push_back(p->cbs[r].E);
   for (int i = 0; i < n && i < (int)v.size(); ++i) info[i] = v[i];
   return (int)v.size();
@@ -1299,49 +1290,37 @@ int lte_plan_harq_info(const lte_plan* p, int64_t* info, int n) {
 
 int lte_plan_set_harq_repack(lte_plan* p, int on) {
   if (!p) return fail(LTE_EINVAL, "null plan");
-  if (!p->harq) return fail(LTE_EINVAL, "not a HARQ plan");
-  if (on && p->pk_decb.empty()) {
-    // the packed arrays of early-stop re-packing (which a HARQ plan never has), one
-    // frame index for every slot, and room in hq_skip for the decoder flags and {M, A}
+  if (!p->hq.on) return fail(LTE_EINVAL, "not a HARQ plan");
+  if (on && !plan_has_pack(p)) {
+    // the packed set (no counts, one frame index for every slot) and room in
+    // hq.skip for the decoder flags and {M, A}
     const size_t Gm = ((size_t)p->d.max_frames + 63) / 64;
-    const int cap = turbo_pack_cap((int64_t)Gm);
-    std::vector<DBuf<uint32_t>> b(p->C), x(1);
     DBuf<uint32_t> flags;
-    bool bad = p->f64 ? alloc_packed(p, p->c64, cap) : alloc_packed(p, p->c32, cap);
-    for (int r = 0; r < p->C; ++r) bad |= b[r].alloc((size_t)cap * turbo_kw(p->cbs[r].K) * 64) != 0;
-    bad |= x[0].alloc((size_t)cap * 64) != 0;
-    bad |= flags.alloc(2 * Gm + 2) != 0;
     // (a process may be under way: the latch's flags move with the buffer)
-    bad = bad || hipStreamSynchronize(p->stream) != hipSuccess ||
-          hipMemcpy(flags.p, p->hq_skip.p, Gm * sizeof(uint32_t), hipMemcpyDeviceToDevice) != hipSuccess;
-    if (bad) {
-      p->c64.pk_blk.clear(); p->c64.pk_ckpt.clear();
-      p->c32.pk_blk.clear(); p->c32.pk_ckpt.clear();
+    if (flags.alloc(2 * Gm + 2) || hipStreamSynchronize(p->stream) != hipSuccess ||
+        hipMemcpy(flags.p, p->hq.skip.p, Gm * sizeof(uint32_t), hipMemcpyDeviceToDevice) != hipSuccess ||
+        !plan_alloc_pack(p, false, 1))
       return fail(LTE_ENOMEM, "HARQ re-packing arrays");
-    }
-    p->pk_decb.swap(b);
-    p->pk_idx.swap(x);
-    p->hq_skip = std::move(flags);
+    p->hq.skip = std::move(flags);
   }
-  if ((on != 0) != p->hq_repack) {   // a round under way continues in place on the latch's flags alone
-    if (p->hq_rp_G >= 0 && (int)p->hq_skip_h.size() == 2 * p->hq_rp_G + 2) p->hq_skip_h.resize(p->hq_rp_G);
-    p->hq_rp_G = -1;
-    for (auto& v : p->hq_rp_last) v = 0;
+  if ((on != 0) != p->hq.repack) {   // a round under way continues in place on the latch's flags alone
+    p->hq.latched.indexed = false;
+    for (auto& v : p->hq.rp_last) v = 0;
   }
-  p->hq_repack = on != 0;
+  p->hq.repack = on != 0;
   return LTE_OK;
 }
 
 int lte_plan_harq_repack(const lte_plan* p) {
   if (!p) return fail(LTE_EINVAL, "null plan");
-  return p->hq_repack ? 1 : 0;
+  return p->hq.repack ? 1 : 0;
 }
 
 int lte_plan_harq_repack_info(const lte_plan* p, int64_t* info, int n) {
   if (!p || !info) return fail(LTE_EINVAL, "null argument");
-  if (!p->harq) return fail(LTE_EINVAL, "not a HARQ plan");
-  const int64_t v[7] = {p->hq_repack ? 1 : 0, p->hq_rp_last[0], p->hq_rp_last[1], p->hq_rp_last[2], p->hq_rp_last[3],
-                        turbo_pack_cap((p->d.max_frames + 63) / 64), p->hq_rp_last[4]};
+  if (!p->hq.on) return fail(LTE_EINVAL, "not a HARQ plan");
+  const int64_t v[7] = {p->hq.repack ? 1 : 0, p->hq.rp_last[0], p->hq.rp_last[1], p->hq.rp_last[2], p->hq.rp_last[3],
+                        plan_pack_cap(p), p->hq.rp_last[4]};
   for (int i = 0; i < n && i < 7; ++i) info[i] = v[i];
   return 7;
 }
@@ -1528,8 +1507,8 @@ static SisoPath select_siso(const lte_plan* p, const lte_run_args* a, const Knob
   const int maxd = fuse ? *std::max_element(d.delays, d.delays + d.n_paths) : 0;
   // receiver: fused (estimation + data path per frame) unless LTE_RX_FUSE=0
   s.zn = k.demap_in_dematch && demap_in_dematch(p, a);
-  s.hq_skip = p->harq && p->hq_round >= 1 && do_rx && k.harq_skip && !logmap_on();
-  s.hq_repack = s.hq_skip && p->hq_repack;
+  s.hq_skip = p->hq.on && p->hq.round >= 1 && do_rx && k.harq_skip && !logmap_on();
+  s.hq_repack = s.hq_skip && p->hq.repack;
   const bool rx_fuse = do_rx && k.rx_fuse;
   const bool rxf = rx_fuse && rx_fusable(p);
   const bool rxs = rx_fuse && !rxf && rx_simo_fusable(p);
@@ -1641,96 +1620,137 @@ static int capture_bufs(lte_plan* p, const lte_run_args* a, int B, size_t n_syms
   return LTE_OK;
 }
 
-// The coded receive tail: the receiver's soft output -> decoder rows (rx_map;
-// soft.z set: k_dematch_zn demaps (z, nv) with nd noise variances per row,
-// nv_pairs: one per Alamouti RE pair), turbo decoding, CRC and error counts per
-// frame into sc.
-// HARQ (SISO only): add0 = 0 is round 0, which first zeroes the rows its map
-// leaves unwritten, add0 = 1 a later round, which adds to the rows' sums;
-// hq_skip: the skip-aware decoders; the groups they skipped go to hq_last[2].
-// hq_repack: a round whose counts (k_harq_repack_index's, read back with the
-// flags) satisfy harq_repack_rule decodes the full groups in place and the
-// active frames of the mixed groups in the plan's packed arrays.
+// What a run's decode does, decided once from the plan's decoder options and
+// (HARQ) the last latched round.
+enum DecodeMode {
+  DEC_FIXED,               // turbo_iters iterations of every group
+  DEC_EARLY_STOP,          // until each code block's CRC holds
+  DEC_EARLY_STOP_REPACK,   // ... the undecided blocks re-packed at the boundary
+  DEC_HARQ_SKIP,           // the skip-aware decoders on k_harq_latch's flags
+  DEC_HARQ_PACK,           // full groups in place, the mixed groups' active frames in the packed set
+  DEC_NOTHING_LEFT,        // every group is acknowledged: no decoder launch
+};
+struct Decode {
+  DecodeMode mode;
+  int nskip;         // groups the skip-aware decoders leave out as finished
+  int64_t rule[6];   // harq_repack_rule's numbers (zeros and G - nskip where it does not apply)
+};
+
+// later: a HARQ round >= 1.  hq_skip / hq_repack: the path's (SisoPath).
+static Decode decide_decode(const lte_plan* p, int B, bool later, bool hq_skip, bool hq_repack) {
+  const int G = (B + 63) / 64;
+  const HarqRound& lr = p->hq.latched;
+  // HARQ rounds >= 1: groups whose frames are all acknowledged return at once
+  const bool skip = hq_skip && lr.G == G, indexed = lr.indexed && lr.G == G;
+  Decode dc{DEC_FIXED, 0, {0, 0, 0, 0, 0, 0}};
+  if (skip)
+    for (int g = 0; g < G; ++g) dc.nskip += lr.finished(g) ? 1 : 0;
+  dc.rule[4] = dc.rule[5] = G - dc.nskip;
+  if (p->hq.repack && p->hq.on && later && indexed)
+    harq_repack_rule(G, dc.nskip, lr.M(), lr.A(), plan_pack_cap(p), dc.rule);
+  if (skip)
+    dc.mode = hq_repack && indexed && dc.rule[3] != 0 ? DEC_HARQ_PACK : dc.nskip == G ? DEC_NOTHING_LEFT : DEC_HARQ_SKIP;
+  else if (p->es.on)
+    dc.mode = p->es.repack_after ? DEC_EARLY_STOP_REPACK : DEC_EARLY_STOP;
+  return dc;
+}
+
+// DEC_HARQ_PACK: the active frames of the mixed groups gathered into the packed
+// set and decoded there beside the full groups, their decisions scattered back
 template <class R>
-static int decode_blocks(lte_plan* p, const lte_run_args* a, int B, const int32_t* rx_map, int nd, int nv_pairs,
-                         int add0, const SoftOut<R>& soft, const Scored& sc, bool hq_skip, bool hq_repack = false) {
+static int decode_harq_pack(lte_plan* p, const std::vector<TurboJob>& jobs, int G, const Decode& dc) {
   const lte_plan_desc& d = p->d;
   ChainBufs<R>& c = cbuf<R>(p);
   hipStream_t s = p->stream;
-  const int G = (B + 63) / 64;
+  const int f64 = sizeof(R) == 8 ? 1 : 0;
+  const int A = (int)dc.rule[1], P = (int)dc.rule[2], n_full = (int)(dc.rule[5] - dc.rule[2]);
+  const uint32_t* const idx = c.pk.idx[0].p;
+  std::vector<TurboJob> pj(p->C);
+  if (!p->pipe) p->pipe = std::make_unique<PipeStreams>();
+  if (!p->pipe->ensure(1)) return fail(LTE_EHIP, "HARQ re-packing stream");
+  {
+    Timer t(p, KN_HARQ);
+    for (int r = 0; r < p->C; ++r) {
+      LCHK(launch_harq_repack_gather<R>(s, (const R*)jobs[r].blk, jobs[r].ch, c.pk.blk[r].p, c.pk.ch(), jobs[r].K,
+                                        idx, A));
+      pj[r] = c.pk.job(jobs[r], r, P);
+    }
+  }
+  {
+    // The packed groups decode on a second stream beside the full groups
+    // (the coded pipeline's first decoder stream: a HARQ plan never takes the
+    // pipeline).  One launch after the other would cost the few packed waves a
+    // whole wave's decode -- the floor of any decoder launch -- at the tail.
+    Timer t(p, KN_TURBO);
+    PipeStreams& ps = *p->pipe;
+    HIPCHK(hipEventRecord(ps.ready[0], s));                    // the packed rows are gathered
+    HIPCHK(hipStreamWaitEvent(ps.dec[0], ps.ready[0], 0));
+    LCHK(launch_turbo_jobs(ps.dec[0], pj.data(), p->C, d.turbo_iters, TM_DEC1, f64, nullptr, p->scale.ext));
+    HIPCHK(hipEventRecord(ps.done[0], ps.dec[0]));
+    if (n_full > 0)   // the decoder flags leave out the finished and the mixed groups
+      LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, f64, p->hq.skip.p + G, p->scale.ext));
+    HIPCHK(hipStreamWaitEvent(s, ps.done[0], 0));              // the join: scatter and CRC follow on the plan stream
+  }
+  Timer t(p, KN_HARQ);
+  for (int r = 0; r < p->C; ++r)
+    LCHK(launch_harq_repack_scatter(s, c.pk.decb[r].p, idx, A, turbo_kw(jobs[r].K), jobs[r].bits));
+  return LTE_OK;
+}
+
+// The coded receive tail: the receiver's soft output -> decoder rows (rx_map;
+// soft.z set: k_dematch_zn demaps (z, nv) with nd noise variances per row,
+// nv_pairs: one per Alamouti RE pair), turbo decoding as decide_decode says,
+// CRC and error counts per frame into sc.
+// HARQ (SISO only): add0 = 0 is round 0, which first zeroes the rows its map
+// leaves unwritten, add0 = 1 a later round, which adds to the rows' sums;
+// hq_skip / hq_repack: the path's.
+template <class R>
+static int decode_blocks(lte_plan* p, const lte_run_args* a, int B, const int32_t* rx_map, int nd, int nv_pairs,
+                         int add0, const SoftOut<R>& soft, const Scored& sc, bool hq_skip = false,
+                         bool hq_repack = false) {
+  const lte_plan_desc& d = p->d;
+  ChainBufs<R>& c = cbuf<R>(p);
+  hipStream_t s = p->stream;
+  const int G = (B + 63) / 64, ch = turbo_plan_ch(p), f64 = sizeof(R) == 8 ? 1 : 0;
   {
     Timer t(p, KN_DEMATCH);
-    if (p->harq && !add0 && p->hq_nz)
-      LCHK(launch_harq_zero<R>(s, p->hq_zmap.p, p->hq_nz, G, c.blk_ptrs.p, p->rows_dev.p, turbo_plan_ch(p)));
+    if (p->hq.on && !add0 && p->hq.nz)
+      LCHK(launch_harq_zero<R>(s, p->hq.zmap.p, p->hq.nz, G, c.blk_ptrs.p, p->rows_dev.p, ch));
     if (soft.z)
       LCHK(launch_dematch_zn<R>(s, soft.z, soft.nv, p->n_re_bits / d.bps, nd, d.bps, B, rx_map, p->n_layers,
-                                c.blk_ptrs.p, p->rows_dev.p, turbo_plan_ch(p), 0, nv_pairs, add0));
+                                c.blk_ptrs.p, p->rows_dev.p, ch, 0, nv_pairs, add0));
     else
-      LCHK(launch_dematch<R>(s, soft.llr, p->n_re_bits, B, rx_map, p->n_layers, c.blk_ptrs.p, p->rows_dev.p,
-                             turbo_plan_ch(p), 0, add0));
+      LCHK(launch_dematch<R>(s, soft.llr, p->n_re_bits, B, rx_map, p->n_layers, c.blk_ptrs.p, p->rows_dev.p, ch, 0,
+                             add0));
   }
-  std::vector<TurboJob> jobs(p->C);
-  for (int r = 0; r < p->C; ++r) {
-    const CbInfo& cb = p->cbs[r];
-    jobs[r] = TurboJob{c.blk[r].p, c.ckpt[r].p, p->decb[r].p, cb.K, cb.f1, cb.f2, G, turbo_plan_ch(p)};
+  const std::vector<TurboJob> jobs = plan_jobs<R>(p, c, 0, G);
+  const Decode dc = decide_decode(p, B, add0 != 0, hq_skip, hq_repack);
+  const bool pack = dc.mode == DEC_HARQ_PACK;
+  p->hq.last[2] = dc.nskip;
+  if (p->hq.repack) {
+    const int64_t last[5] = {add0 ? (pack ? TURBO_RP_PACKED : TURBO_RP_INPLACE) : TURBO_RP_NONE, dc.rule[0],
+                             dc.rule[1], dc.rule[2], pack ? dc.rule[5] : G - dc.nskip};
+    std::copy(last, last + 5, p->hq.rp_last);
   }
-  // HARQ rounds >= 1: groups whose frames are all acknowledged return at once
-  // (k_turbo*_skip read k_harq_latch's flags); none left: no decoder launch
-  const bool indexed = p->hq_rp_G == G && (int)p->hq_skip_h.size() == 2 * G + 2;   // (flags, decoder flags, M, A)
-  const bool skip = hq_skip && (indexed || (int)p->hq_skip_h.size() == G);
-  int nskip = 0;
-  if (skip)
-    for (int g = 0; g < G; ++g) nskip += p->hq_skip_h[g] ? 1 : 0;
-  p->hq_last[2] = nskip;
-  const int f64 = sizeof(R) == 8 ? 1 : 0;
-  int64_t rule[6] = {0, 0, 0, 0, G - nskip, G - nskip};
-  if (p->hq_repack && p->harq && add0 && indexed)
-    harq_repack_rule(G, skip ? nskip : 0, p->hq_skip_h[2 * G], p->hq_skip_h[2 * G + 1],
-                     turbo_pack_cap((d.max_frames + 63) / 64), rule);
-  const bool pack = hq_repack && skip && indexed && rule[3] != 0;
-  if (p->hq_repack) {
-    const int64_t last[5] = {add0 ? (pack ? TURBO_RP_PACKED : TURBO_RP_INPLACE) : TURBO_RP_NONE, rule[0], rule[1],
-                             rule[2], pack ? rule[5] : G - nskip};
-    std::copy(last, last + 5, p->hq_rp_last);
-  }
-  if (pack) {
-    const int A = (int)rule[1], P = (int)rule[2], n_full = (int)(rule[5] - rule[2]);
-    const int pch = turbo_chunk(turbo_pack_cap((d.max_frames + 63) / 64));
-    std::vector<TurboJob> pj(p->C);
-    if (!p->pipe) p->pipe = std::make_unique<PipeStreams>();
-    if (!p->pipe->ensure(1)) return fail(LTE_EHIP, "HARQ re-packing stream");
-    {
-      Timer t(p, KN_HARQ);
-      for (int r = 0; r < p->C; ++r) {
-        LCHK(launch_harq_repack_gather<R>(s, c.blk[r].p, turbo_plan_ch(p), c.pk_blk[r].p, pch, p->cbs[r].K,
-                                          p->pk_idx[0].p, A));
-        pj[r] = TurboJob{c.pk_blk[r].p, c.pk_ckpt[r].p, p->pk_decb[r].p, jobs[r].K, jobs[r].f1, jobs[r].f2, P, pch};
-      }
-    }
-    {
-      // The packed groups decode on a second stream beside the full groups
-      // (the coded pipeline's first decoder stream: a HARQ plan never takes the
-      // pipeline).  One launch after the other would cost the few packed waves a
-      // whole wave's decode -- the floor of any decoder launch -- at the tail.
+  switch (dc.mode) {
+    case DEC_NOTHING_LEFT:
+      break;
+    case DEC_HARQ_PACK:
+      if (const int e = decode_harq_pack<R>(p, jobs, G, dc)) return e;
+      break;
+    case DEC_EARLY_STOP:
+    case DEC_EARLY_STOP_REPACK: {
       Timer t(p, KN_TURBO);
-      PipeStreams& ps = *p->pipe;
-      HIPCHK(hipEventRecord(ps.ready[0], s));                    // the packed rows are gathered
-      HIPCHK(hipStreamWaitEvent(ps.dec[0], ps.ready[0], 0));
-      LCHK(launch_turbo_jobs(ps.dec[0], pj.data(), p->C, d.turbo_iters, TM_DEC1, f64, nullptr, p->turbo_scale));
-      HIPCHK(hipEventRecord(ps.done[0], ps.dec[0]));
-      if (n_full > 0)   // the decoder flags leave out the finished and the mixed groups
-        LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, f64, p->hq_skip.p + G, p->turbo_scale));
-      HIPCHK(hipStreamWaitEvent(s, ps.done[0], 0));              // the join: scatter and CRC follow on the plan stream
+      LCHK(plan_launch_turbo_es<R>(p, s, jobs, B, dc.mode == DEC_EARLY_STOP_REPACK));
+      break;
     }
-    Timer t(p, KN_HARQ);
-    for (int r = 0; r < p->C; ++r)
-      LCHK(launch_harq_repack_scatter(s, p->pk_decb[r].p, p->pk_idx[0].p, A, turbo_kw(jobs[r].K), jobs[r].bits));
-  } else if (!(skip && nskip == G)) {
-    Timer t(p, KN_TURBO);
-    if (skip)
-      LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, f64, p->hq_skip.p, p->turbo_scale));
-    else
-      LCHK(plan_launch_turbo(p, s, jobs, B, f64));
+    case DEC_HARQ_SKIP:
+    case DEC_FIXED: {
+      Timer t(p, KN_TURBO);
+      LCHK(launch_turbo_jobs(s, jobs.data(), p->C, d.turbo_iters, TM_DEC1, f64,
+                             dc.mode == DEC_HARQ_SKIP ? p->hq.skip.p : nullptr, p->scale.ext));
+      break;
+    }
   }
   Timer t(p, KN_CRC);
   LCHK(launch_crc_count(s, p->cbi.p, p->C, p->dec_ptrs.p, p->kw_dev.p, B, sc, p->frame_crc.p,
@@ -1924,7 +1944,7 @@ static int run_mimo(lte_plan* p, const lte_run_args* a, const MimoPath& path, in
                                  path.det_stage ? 1 : 0));
   }
   if (coded)   // (k_det_sfbc's noise variances are per Alamouti RE pair; m.res = Nd for spatial)
-    if (const int e = decode_blocks<R>(p, a, B, p->rx_map.p, m.res, sfbc ? 1 : 0, 0, soft, sc, false)) return e;
+    if (const int e = decode_blocks<R>(p, a, B, p->rx_map.p, m.res, sfbc ? 1 : 0, 0, soft, sc)) return e;
   // this chain's own captures; lpart / lstats live until read_back has synchronised
   if (a->cap_signal_tx)
     HIPCHK(hipMemcpyAsync(a->cap_signal_tx, c.x.p, (size_t)B * m.num_tx * p->L * sizeof(V), hipMemcpyDeviceToHost, s));
@@ -2091,7 +2111,7 @@ static PipeReason pipe_select(const lte_plan* p, const lte_run_args* a, const Si
       a->cap_bits_rx || a->cap_llr || a->cap_noise_power || a->cap_tx_syms)
     return PIPE_CAPTURE;
   if (a->bits || a->phases || a->noise) return PIPE_INJECT;
-  if (p->harq || p->early_stop || logmap_on()) return PIPE_DECODER;
+  if (p->hq.on || p->es.on || logmap_on()) return PIPE_DECODER;
   if (!path.fused() || path.xhand || !path.zn || (path.rx != RX_FRAME && path.rx != RX_FRAME_W)) return PIPE_PATH;
   const int G = (B + 63) / 64, ch = turbo_plan_ch(p);
   const int n = coded_pipe_slices(G, ch, k.coded_pipe_groups, nullptr, 0);
@@ -2135,7 +2155,6 @@ static int run_siso_pipe(lte_plan* p, const lte_run_args* a, const SisoPath& pat
   // returns the error and every stream is drained before it goes to the caller.
   int t_turbo = -1;   // the decoders' interval in the event pool
   auto queue = [&]() -> int {
-    std::vector<TurboJob> jobs(p->C);
     for (int i = 0; i < ns; ++i) {
       const int g0 = slices[2 * i], G = slices[2 * i + 1];
       const int64_t f0 = (int64_t)g0 * 64;
@@ -2167,13 +2186,7 @@ static int run_siso_pipe(lte_plan* p, const lte_run_args* a, const SisoPath& pat
       // the slice's decode: the plan's arrays from chunk g0 / ch on (g0 is a multiple of ch)
       hipStream_t ds = ps.dec[i & 1];
       HIPCHK(hipStreamWaitEvent(ds, ps.ready[i], 0));
-      for (int r = 0; r < p->C; ++r) {
-        const CbInfo& cb = p->cbs[r];
-        const int64_t ck_rows = (int64_t)turbo_nwin(cb.K) * turbo_ck_rows(sizeof(R) == 8);
-        jobs[r] = TurboJob{c.blk[r].p + turbo_elem_ch(ch, turbo_rows(cb.K), g0, 0),
-                           c.ckpt[r].p + turbo_elem_ch(ch, ck_rows, g0, 0),
-                           p->decb[r].p + (size_t)g0 * turbo_kw(cb.K) * TURBO_RS, cb.K, cb.f1, cb.f2, G, ch};
-      }
+      const std::vector<TurboJob> jobs = plan_jobs<R>(p, c, g0, G);
       if (i == 0 && p->timing) {   // `turbo`: one interval per run, from here to the join
         t_turbo = (int)p->evuse.size() * 2;
         while ((int)p->evpool.size() < t_turbo + 2) {
@@ -2185,7 +2198,7 @@ static int run_siso_pipe(lte_plan* p, const lte_run_args* a, const SisoPath& pat
         HIPCHK(hipEventRecord(p->evpool[t_turbo], ds));
       }
       LCHK(launch_turbo_jobs(ds, jobs.data(), p->C, d.turbo_iters, TM_DEC1, sizeof(R) == 8 ? 1 : 0, nullptr,
-                             p->turbo_scale));
+                             p->scale.ext));
     }
     for (int k = 0; k < 2; ++k) {
       HIPCHK(hipEventRecord(ps.done[k], ps.dec[k]));
@@ -2236,10 +2249,10 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
   const bool fuse = path.fused(), xhand = path.xhand;
   // HARQ round t: its own rate-matching maps, and channel / noise streams keyed
   // by seed_t (the payload stream, and k_crc_count's re-draw of it, keep seed)
-  const int hq_t = p->harq ? p->hq_round : 0, hq_rv = p->harq ? p->hq.rv_seq[hq_t] : 0;
+  const int hq_t = p->hq.on ? p->hq.round : 0, hq_rv = p->hq.on ? p->hq.desc.rv_seq[hq_t] : 0;
   const uint64_t cseed = a->seed + (uint64_t)hq_t * 0x9E3779B97F4A7C15ull;
-  const int32_t* const tx_map = p->tx_map.p + (size_t)p->hq_slot[hq_rv] * p->n_re_bits;
-  const int32_t* const rx_map = p->rx_map.p + (size_t)p->hq_slot[hq_rv] * p->n_layers * p->n_re_bits;
+  const int32_t* const tx_map = p->tx_map.p + (size_t)p->hq.slot[hq_rv] * p->n_re_bits;
+  const int32_t* const rx_map = p->rx_map.p + (size_t)p->hq.slot[hq_rv] * p->n_layers * p->n_re_bits;
   // the launchers' argument groups, each built once (the receiver's further down, when its buffers are)
   const TxSource src{coded ? 1 : 0, p->pw.p, p->PW, p->enc.p, p->enc_words, tx_map};
   const Scored sc{p->pw.p, p->PW, d.n_bits, p->frame_err.p};
@@ -2334,27 +2347,31 @@ static int run_siso(lte_plan* p, const lte_run_args* a, const SisoPath& path, in
     if (const int e = decode_blocks<R>(p, a, B, rx_map, p->Nd, 0, hq_t >= 1 ? 1 : 0, soft, sc, path.hq_skip,
                                        path.hq_repack))
       return e;
-    if (p->harq) {
+    if (p->hq.on) {
       {
         Timer t(p, KN_HARQ);
-        LCHK(launch_harq_latch(s, B, hq_t, p->frame_err.p, p->frame_crc.p, p->hq_tx_used.p, p->hq_err.p, p->hq_crc.p,
-                               p->hq_skip.p));
+        LCHK(launch_harq_latch(s, B, hq_t, p->frame_err.p, p->frame_crc.p, p->hq.tx_used.p, p->hq.err.p, p->hq.crc.p,
+                               p->hq.skip.p));
       }
       const int G = (B + 63) / 64;
       // re-packing: the next round's frame index, decoder flags and {M, A}, read back with the latch's flags
-      const size_t n_flags = p->hq_repack ? 2 * (size_t)G + 2 : G;
-      if (p->hq_repack) {
+      // (the record names the round only once its copy is queued: a failed launch leaves nothing latched)
+      HarqRound& lr = p->hq.latched;
+      const bool indexed = p->hq.repack;
+      lr.G = 0;
+      lr.indexed = false;
+      lr.raw.resize(indexed ? 2 * (size_t)G + 2 : G);
+      if (indexed) {
         Timer t(p, KN_HARQ);
-        LCHK(launch_harq_repack_index(s, p->hq_crc.p, B, p->pk_idx[0].p,
-                                      turbo_pack_cap((d.max_frames + 63) / 64) * 64, p->hq_skip.p + G,
-                                      p->hq_skip.p + 2 * G));
+        LCHK(launch_harq_repack_index(s, p->hq.crc.p, B, cbuf<R>(p).pk.idx[0].p, plan_pack_cap(p) * 64,
+                                      p->hq.skip.p + G, p->hq.skip.p + 2 * G));
       }
-      p->hq_rp_G = p->hq_repack ? G : -1;
-      p->hq_skip_h.resize(n_flags);
-      HIPCHK(hipMemcpyAsync(p->hq_skip_h.data(), p->hq_skip.p, n_flags * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-      p->hq_last[0] = hq_t;
-      p->hq_last[1] = hq_rv;
-      p->hq_done = hq_t;
+      HIPCHK(hipMemcpyAsync(lr.raw.data(), p->hq.skip.p, lr.raw.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+      lr.G = G;
+      lr.indexed = indexed;
+      p->hq.last[0] = hq_t;
+      p->hq.last[1] = hq_rv;
+      p->hq.done = hq_t;
     }
   }
   // this chain's own captures
@@ -2394,23 +2411,23 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
     }
     fid[b] = a->frame_ids ? a->frame_ids[b] : a->frame_id0 + (uint64_t)b;
   }
-  if (p->harq) {   // a retransmission serves round 0's frames; round 0 opens a new process
-    if (p->hq_round >= 1) {
-      const int t = p->hq_round;
+  if (p->hq.on) {   // a retransmission serves round 0's frames; round 0 opens a new process
+    if (p->hq.round >= 1) {
+      const int t = p->hq.round;
       std::string bad;
-      if (p->hq_done != t - 1)
+      if (p->hq.done != t - 1)
         bad = "HARQ: round " + std::to_string(t) + " without a completed round " + std::to_string(t - 1);
-      else if ((size_t)B != p->hq_fids.size())
-        bad = "HARQ: a retransmission must bring round 0's n_frames (" + std::to_string(p->hq_fids.size()) + ")";
-      else if (fid != p->hq_fids)
+      else if ((size_t)B != p->hq.fids.size())
+        bad = "HARQ: a retransmission must bring round 0's n_frames (" + std::to_string(p->hq.fids.size()) + ")";
+      else if (fid != p->hq.fids)
         bad = "HARQ: a retransmission must bring round 0's frame ids";
       if (!bad.empty()) {
-        p->hq_round = 0;   // the refused round is not pending any more
+        p->hq.round = 0;   // the refused round is not pending any more
         return fail(LTE_EINVAL, bad);
       }
     } else {
-      p->hq_fids = fid;
-      p->hq_done = -1;
+      p->hq.fids = fid;
+      p->hq.done = -1;
     }
   }
   HIPCHK(hipMemcpyAsync(p->snr_idx.p, si.data(), B * sizeof(int32_t), hipMemcpyHostToDevice, s));
@@ -2433,9 +2450,9 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
   p->evuse.clear();
   if (logmap_on() && p->ct->coded && !p->f64)
     return fail(LTE_EUNSUP, "exact log-MAP decoding runs in float64 plans only");
-  if (logmap_on() && p->early_stop)
+  if (logmap_on() && p->es.on)
     return fail(LTE_EUNSUP, "CRC early termination runs the max-log decoders only (set_decoder_mode(True))");
-  if (logmap_on() && p->turbo_scale != 1.0)
+  if (logmap_on() && p->scale.on())
     return fail(LTE_EUNSUP, "extrinsic scaling runs the max-log decoders only (set_decoder_mode(True))");
   const Knobs knobs = read_knobs();   // the environment switches, once per run
   p->pipe_last[0] = p->pipe_last[1] = 0;
@@ -2455,7 +2472,7 @@ int lte_run(lte_plan* p, const lte_run_args* a) {
                  : run_siso<float>(p, a, path, B, n_snr, sl, inj_bits);
     }
     HIPCHK(hipStreamSynchronize(s));
-    p->hq_round = 0;   // the next run opens a new process unless lte_plan_harq_set_round says otherwise
+    p->hq.round = 0;   // the next run opens a new process unless lte_plan_harq_set_round says otherwise
     return e;
   }
   if (stages != LTE_STAGE_ALL) return fail(LTE_EUNSUP, "multi-antenna chains run all stages");
@@ -2496,14 +2513,14 @@ int lte_run_path(const lte_plan* p, const lte_run_args* a, char* buf, int len) {
                       !p->ct->coded ? "none" : s.zn ? "zn" : "llr");
   }
   // the decoder family is named only when it is not the default one
-  if (p->early_stop && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " turbo=es");
-  if (p->early_stop && p->repack_after && n >= 0 && n < len)
-    n += std::snprintf(buf + n, len - n, " repack=%d", p->repack_after);
-  if (p->harq && n >= 0 && n < len)
-    n += std::snprintf(buf + n, len - n, " harq=t%d,rv%d,skip=%d", p->hq_round, p->hq.rv_seq[p->hq_round],
+  if (p->es.on && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " turbo=es");
+  if (p->es.on && p->es.repack_after && n >= 0 && n < len)
+    n += std::snprintf(buf + n, len - n, " repack=%d", p->es.repack_after);
+  if (p->hq.on && n >= 0 && n < len)
+    n += std::snprintf(buf + n, len - n, " harq=t%d,rv%d,skip=%d", p->hq.round, p->hq.desc.rv_seq[p->hq.round],
                        select_siso(p, a, knobs).hq_skip ? 1 : 0);
-  if (p->harq && p->hq_repack && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " harq_repack=1");
-  if (p->turbo_scale != 1.0 && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " ext=%g", p->turbo_scale);
+  if (p->hq.on && p->hq.repack && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " harq_repack=1");
+  if (p->scale.on() && n >= 0 && n < len) n += std::snprintf(buf + n, len - n, " ext=%g", p->scale.ext);
   return n < len ? n : len - 1;
 }
 

@@ -812,89 +812,47 @@ __global__ __launch_bounds__(64, LTE_TURBO64_ONE_WAVE ? 1 : 2) void k_turbo64_es
 }
 
 // ---------------------------------------------------------------------------
-// Re-packing of the blocks still undecided at the boundary.
+// Re-packing of the blocks still undecided at the boundary.  The
+// kernels' bodies are the shared ones of lte_internal.h (repack_rank,
+// repack_gather, repack_scatter), which HARQ re-packing's kernels in
+// lte_turbo.hip also inline.
 //
 // k_repack_index, one 1024-thread block per code-block slot: the slot's
 // undecided blocks (valid lanes whose count is TURBO_UNDECIDED) in ascending
-// (group, lane) order.  Wave w owns a contiguous run of groups; it counts its
-// run (ballot + popcount per group), the 16 run totals are prefix-summed, and
-// a second walk over the run gives every undecided lane its rank -- prefix
-// sums, no atomics, so the order does not depend on arrival.  idx[rank] =
-// group * 64 + lane for rank < cap (the packed arrays' lanes); *count takes
-// the total whether it fits or not.
-constexpr int RPK_WAVES = 16;
-__global__ __launch_bounds__(64 * RPK_WAVES) void k_repack_index(const uint32_t* __restrict__ used, int nv, int G,
-                                                                 uint32_t* __restrict__ idx, int cap,
-                                                                 uint32_t* __restrict__ count) {
-  __shared__ int tot[RPK_WAVES];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int per = (G + RPK_WAVES - 1) / RPK_WAVES;
-  const int g0 = min(G, w * per), g1 = min(G, g0 + per);
-  int n = 0;
-  for (int g = g0; g < g1; ++g) {
-    const bool u = g * RS + lane < nv && used[(size_t)g * RS + lane] == TURBO_UNDECIDED;
-    n += __builtin_popcountll(__builtin_amdgcn_ballot_w64(u));
-  }
-  if (lane == 0) tot[w] = n;
-  __syncthreads();
-  int base = 0, all = 0;
-  for (int i = 0; i < RPK_WAVES; ++i) {
-    if (i < w) base += tot[i];
-    all += tot[i];
-  }
-  if (threadIdx.x == 0) *count = (uint32_t)all;
-  for (int g = g0; g < g1; ++g) {
-    const bool u = g * RS + lane < nv && used[(size_t)g * RS + lane] == TURBO_UNDECIDED;
-    const uint64_t m = __builtin_amdgcn_ballot_w64(u);
-    const int rank = base + __builtin_popcountll(m & ((1ull << lane) - 1ull));
-    if (u && rank < cap) idx[rank] = (uint32_t)(g * RS + lane);
-    base += __builtin_popcountll(m);
-  }
+// (group, lane) order.  idx[rank] = group * 64 + lane for rank < cap (the
+// packed arrays' lanes); *count takes the total whether it fits or not.
+__global__ __launch_bounds__(64 * REPACK_WAVES) void k_repack_index(const uint32_t* __restrict__ used, int nv, int G,
+                                                                    uint32_t* __restrict__ idx, int cap,
+                                                                    uint32_t* __restrict__ count) {
+  const int lane = threadIdx.x & 63;
+  const RepackTotals all = repack_rank(
+      G,
+      [&](int g) {
+        const uint64_t u =
+            __builtin_amdgcn_ballot_w64(g * RS + lane < nv && used[(size_t)g * RS + lane] == TURBO_UNDECIDED);
+        return RepackMask{u, u};
+      },
+      [&](int g, RepackMask m, int rank) {
+        if (((m.take >> lane) & 1ull) && rank < cap) idx[rank] = (uint32_t)(g * RS + lane);
+      });
+  if (threadIdx.x == 0) *count = (uint32_t)all.lanes;
 }
 
-// k_repack_gather: block (j, y) fills packed group j's rows [y * RPK_ROWS,
-// (y + 1) * RPK_ROWS), four waves taking every fourth row.  Lane l of a row
-// reads element idx[j * 64 + l] of the same row of the source arrays (chunk
-// width sch) and the wave stores one whole row of the packed arrays (chunk
-// width dch); lanes past n store zeros, so the packed wave computes on defined
-// values.  A wave per destination group touches one 8-byte element per live
-// block and row, not the source group's whole 512-byte row for the one or two
-// stragglers it holds at the waterfall (the copy shape is argued in DESIGN.md
-// §5); the rows are spread over the grid because the destination groups alone
-// are a few dozen waves.  Block (j, 0) also marks the packed lanes undecided.
-constexpr int RPK_ROWS = 64;
+// k_repack_gather: every row of the undecided blocks (the second window
+// resumes mid-decode), the packed lanes marked undecided in dused
 template <class T>
 __global__ __launch_bounds__(256) void k_repack_gather(const T* __restrict__ src, int sch, T* __restrict__ dst, int dch,
-                                                       int rows, const uint32_t* __restrict__ idx, int n,
+                                                       int K, const uint32_t* __restrict__ idx, int n,
                                                        uint32_t* __restrict__ dused) {
-  const int j = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int d = j * RS + lane;
-  const bool on = d < n;
-  const uint32_t sidx = on ? idx[d] : 0u;
-  const int64_t sg = sidx >> 6;
-  const int sl = (int)(sidx & 63u);
-  if (blockIdx.y == 0 && w == 0) dused[d] = TURBO_UNDECIDED;
-  const int r1 = min(rows, ((int)blockIdx.y + 1) * RPK_ROWS);
-  for (int row = blockIdx.y * RPK_ROWS + w; row < r1; row += 4) {
-    const T v = on ? src[turbo_elem_ch(sch, rows, sg, row) + sl] : (T)0;
-    dst[turbo_elem_ch(dch, rows, j, row) + lane] = v;
-  }
+  repack_gather<T, false>(src, sch, dst, dch, K, idx, n, dused);
 }
 
-// k_repack_scatter: the packed groups' decision words ([G'][kw][64]) and
-// iteration counts back to the blocks' own (group, lane); one thread per
-// packed block.
+// k_repack_scatter: decision words and iteration counts back to the blocks' own
 __global__ __launch_bounds__(64) void k_repack_scatter(const uint32_t* __restrict__ pbits,
                                                        const uint32_t* __restrict__ pused,
                                                        const uint32_t* __restrict__ idx, int n, int kw,
                                                        uint32_t* __restrict__ bits, uint32_t* __restrict__ used) {
-  const int j = blockIdx.x, lane = threadIdx.x;
-  const int d = j * RS + lane;
-  if (d >= n) return;
-  const uint32_t sidx = idx[d];
-  const size_t sg = sidx >> 6, sl = sidx & 63u;
-  for (int w = 0; w < kw; ++w) bits[(sg * kw + w) * RS + sl] = pbits[((size_t)j * kw + w) * RS + lane];
-  used[sg * RS + sl] = pused[d];
+  repack_scatter(pbits, pused, idx, n, kw, bits, used);
 }
 
 // decoder arithmetic of the f64 entry points and chains: max-log-MAP (the
@@ -1009,7 +967,7 @@ int launch_turbo_jobs_es_repack(hipStream_t s, const TurboJob* jobs, uint32_t* c
   const TurboWin w0{after, 0}, w1{after, 1};
   if (int e = launch_turbo_jobs_es(s, jobs, used, nv, n, iters, f64, poly, &w0, scale)) return e;
   for (int i = 0; i < n; ++i)
-    hipLaunchKernelGGL(k_repack_index, dim3(1), dim3(64 * RPK_WAVES), 0, s, used[i], nv[i], jobs[i].G, pk[i].idx,
+    hipLaunchKernelGGL(k_repack_index, dim3(1), dim3(64 * REPACK_WAVES), 0, s, used[i], nv[i], jobs[i].G, pk[i].idx,
                        pk[i].cap * RS, counts + i);
   if (int e = (int)hipGetLastError()) return e;
   std::vector<uint32_t> cnt(n);
@@ -1035,10 +993,10 @@ int launch_turbo_jobs_es_repack(hipStream_t s, const TurboJob* jobs, uint32_t* c
       const int pch = turbo_chunk(pk[i].cap);
       if (f64)
         hipLaunchKernelGGL(k_repack_gather<double>, grid, dim3(256), 0, s, (const double*)j.blk, j.ch,
-                           (double*)pk[i].blk, pch, (int)rows, pk[i].idx, (int)u, pk[i].used);
+                           (double*)pk[i].blk, pch, j.K, pk[i].idx, (int)u, pk[i].used);
       else
         hipLaunchKernelGGL(k_repack_gather<float>, grid, dim3(256), 0, s, (const float*)j.blk, j.ch, (float*)pk[i].blk,
-                           pch, (int)rows, pk[i].idx, (int)u, pk[i].used);
+                           pch, j.K, pk[i].idx, (int)u, pk[i].used);
       j = TurboJob{pk[i].blk, pk[i].ck, pk[i].bits, j.K, j.f1, j.f2, Gp, pch};
     }
     const int k = j.ch == 1 ? 0 : 1;

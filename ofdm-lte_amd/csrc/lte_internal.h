@@ -765,4 +765,116 @@ __host__ __device__ inline int64_t turbo_elem_ch(int ch, int64_t rows, int64_t g
 }
 __host__ __device__ inline int turbo_kw(int K) { return (K + 31) / 32; }
 
+// ---------------------------------------------------------------------------
+// Re-packing: the device code both re-packers share --
+// early stop's blocks undecided at the boundary (kernels in lte_decoder.hip)
+// and HARQ's unacknowledged frames of mixed groups (kernels in lte_turbo.hip).
+// Each translation unit keeps its own kernels, which are these bodies inlined:
+// the decoder instances' place in lte_decoder.hip's code object is part of
+// their timing (CHANGELOG.md, round 25), so that unit's kernel set stays put.
+
+// The ranking of an index kernel.  One block of 64 * REPACK_WAVES threads;
+// wave w owns a contiguous run of the G groups.  mask(g) is wave-uniform: the
+// group's candidate lanes (seen) and those of them to pack (take).  The wave
+// counts its run, the run totals are prefix-summed through LDS, and a second
+// walk calls emit(g, mask(g), rank) in uniform control flow, rank = this
+// lane's rank among all taken lanes in ascending (group, lane) order.  No
+// atomics: the order does not depend on arrival.  Returns the groups with a
+// taken lane and the taken lanes over all G.
+constexpr int REPACK_WAVES = 16;
+struct RepackMask {
+  uint64_t seen, take;
+};
+struct RepackTotals {
+  int groups, lanes;
+};
+template <class Mask, class Emit>
+__device__ __forceinline__ RepackTotals repack_rank(int G, Mask mask, Emit emit) {
+  __shared__ int tot_g[REPACK_WAVES], tot_l[REPACK_WAVES];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int per = (G + REPACK_WAVES - 1) / REPACK_WAVES;
+  const int g0 = min(G, w * per), g1 = min(G, g0 + per);
+  int ng = 0, nl = 0;
+  for (int g = g0; g < g1; ++g) {
+    const uint64_t t = mask(g).take;
+    ng += t != 0ull ? 1 : 0;
+    nl += __builtin_popcountll(t);
+  }
+  if (lane == 0) {
+    tot_g[w] = ng;
+    tot_l[w] = nl;
+  }
+  __syncthreads();
+  int base = 0;
+  RepackTotals all{0, 0};
+  for (int i = 0; i < REPACK_WAVES; ++i) {
+    if (i < w) base += tot_l[i];
+    all.groups += tot_g[i];
+    all.lanes += tot_l[i];
+  }
+  for (int g = g0; g < g1; ++g) {
+    const RepackMask m = mask(g);
+    emit(g, m, base + __builtin_popcountll(m.take & ((1ull << lane) - 1ull)));
+    base += __builtin_popcountll(m.take);
+  }
+  return all;
+}
+
+// Row i of the 3K + 12 decoder input rows in dematch order (LS with decoder
+// 1's tail, LP1, LP2, LS2T) -> its row in a block.  These are the rows the
+// fixed decoder reads before it writes: the first decoder-1 pass takes a zero
+// a priori and stores every LE row before a later pass loads it, and the
+// checkpoints are written before they are read, so LE and the checkpoints of
+// a packed group need no copy.
+__host__ __device__ inline int64_t harq_input_row(int K, int i) {
+  if (i < K + 3) return trow_ls(K, i);
+  if (i < 2 * K + 6) return trow_lp(K, 1, i - (K + 3));
+  if (i < 3 * K + 9) return trow_lp(K, 2, i - (2 * K + 6));
+  return trow_ls2t(K, i - (3 * K + 9));
+}
+
+// The gather, for a 256-thread block (j, y): rows [y * RPK_ROWS, (y + 1) *
+// RPK_ROWS) of packed group j, four waves taking every fourth -- of all
+// turbo_rows(K) rows (early stop resumes mid-decode), or with INPUT_ROWS of the
+// 3K + 12 input rows (HARQ decodes from the start).  Lane l reads element
+// idx[j * 64 + l] of the row in the source arrays (chunk width sch) and the
+// wave stores one whole row of the packed arrays (chunk width dch); lanes past
+// n store zeros, so the packed wave computes on defined values.  The copy shape
+// is argued in DESIGN.md §5.  dused set: block (j, 0) also marks the packed
+// lanes undecided.
+constexpr int RPK_ROWS = 64;
+template <class T, bool INPUT_ROWS>
+__device__ __forceinline__ void repack_gather(const T* __restrict__ src, int sch, T* __restrict__ dst, int dch, int K,
+                                              const uint32_t* __restrict__ idx, int n, uint32_t* __restrict__ dused) {
+  const int j = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int d = j * TURBO_RS + lane;
+  const bool on = d < n;
+  const uint32_t sidx = on ? idx[d] : 0u;
+  const int64_t sg = sidx >> 6;
+  const int sl = (int)(sidx & 63u);
+  if (dused && blockIdx.y == 0 && w == 0) dused[d] = TURBO_UNDECIDED;
+  const int64_t rows = turbo_rows(K);
+  const int i1 = min(INPUT_ROWS ? 3 * K + 12 : (int)rows, ((int)blockIdx.y + 1) * RPK_ROWS);
+  for (int i = blockIdx.y * RPK_ROWS + w; i < i1; i += 4) {
+    const int64_t row = INPUT_ROWS ? harq_input_row(K, i) : (int64_t)i;
+    const T v = on ? src[turbo_elem_ch(sch, rows, sg, row) + sl] : (T)0;
+    dst[turbo_elem_ch(dch, rows, j, row) + lane] = v;
+  }
+}
+
+// The scatter, one thread per packed block: the packed groups' decision words
+// ([ceil(n / 64)][kw][64]) and, where pused / used are set, iteration counts
+// back to the blocks' own (group, lane).
+__device__ __forceinline__ void repack_scatter(const uint32_t* __restrict__ pbits, const uint32_t* __restrict__ pused,
+                                               const uint32_t* __restrict__ idx, int n, int kw,
+                                               uint32_t* __restrict__ bits, uint32_t* __restrict__ used) {
+  const int j = blockIdx.x, lane = threadIdx.x;
+  const int d = j * TURBO_RS + lane;
+  if (d >= n) return;
+  const uint32_t sidx = idx[d];
+  const size_t sg = sidx >> 6, sl = sidx & 63u;
+  for (int w = 0; w < kw; ++w) bits[(sg * kw + w) * TURBO_RS + sl] = pbits[((size_t)j * kw + w) * TURBO_RS + lane];
+  if (used) used[sg * TURBO_RS + sl] = pused[d];
+}
+
 }  // namespace lte

@@ -91,6 +91,48 @@ struct TableSet {  // device copies of the static grid tables for one N (f64 cop
   DBuf<double2> pilots64, tw64, chirp64, bhat64;
 };
 
+// The packed arrays of a re-packing decode, owned: per CB slot
+// the rows, checkpoints and decision words of cap groups, laid out as the
+// slot's own at chunk width ch(); with want_used the iteration counts
+// [cap * 64] per slot; idx_slots source-index arrays [cap * 64] (early stop:
+// one per slot; HARQ: one frame index for all).  cap 0: nothing allocated.
+template <class R>
+struct PackSet {
+  int cap = 0;
+  std::vector<DBuf<R>> blk, ckpt;
+  std::vector<DBuf<uint32_t>> decb, used, idx;
+  // every array for the slots cbs (their K), or (false: out of memory) none
+  bool alloc(int groups, const std::vector<CbInfo>& cbs, bool want_used, size_t idx_slots) {
+    PackSet s;
+    const size_t C = cbs.size(), ga = (size_t)turbo_galloc(groups);
+    s.blk.resize(C);
+    s.ckpt.resize(C);
+    s.decb.resize(C);
+    s.used.resize(want_used ? C : 0);
+    s.idx.resize(idx_slots);
+    bool bad = false;
+    for (size_t r = 0; r < C; ++r) {
+      const int K = cbs[r].K;
+      bad |= s.blk[r].alloc(ga * turbo_rows(K) * 64) != 0;
+      bad |= s.ckpt[r].alloc(ga * turbo_nwin(K) * turbo_ck_rows(sizeof(R) == 8) * 64) != 0;
+      bad |= s.decb[r].alloc((size_t)groups * turbo_kw(K) * 64) != 0;
+    }
+    for (auto& b : s.used) bad |= b.alloc((size_t)groups * 64) != 0;
+    for (auto& b : s.idx) bad |= b.alloc((size_t)groups * 64) != 0;
+    if (bad) return false;
+    s.cap = groups;
+    *this = std::move(s);
+    return true;
+  }
+  int ch() const { return turbo_chunk(cap); }
+  // slot r's arrays for launch_turbo_jobs_es_repack (a set with counts and an index per slot)
+  TurboPack pack(int r) const { return TurboPack{blk[r].p, ckpt[r].p, decb[r].p, used[r].p, idx[r].p, cap}; }
+  // slot r's job `own` moved to the packed arrays: G packed groups
+  TurboJob job(const TurboJob& own, int r, int G) const {
+    return TurboJob{blk[r].p, ckpt[r].p, decb[r].p, own.K, own.f1, own.f2, G, ch()};
+  }
+};
+
 // per-precision device buffers of the signal chains (R = float / double)
 template <class R>
 struct ChainBufs {
@@ -102,7 +144,7 @@ struct ChainBufs {
   DBuf<cx<R>> Ym;
   DBuf<R> link_part, link_sigma, inj_lz, inj_lh;
   std::vector<DBuf<R>> blk, ckpt;
-  std::vector<DBuf<R>> pk_blk, pk_ckpt;   // re-packing: the packed rows / checkpoints per CB slot
+  PackSet<R> pk;   // re-packing: the plan's packed set (empty until a re-packing setter asks for it)
   DBuf<R*> blk_ptrs;
 };
 
@@ -184,6 +226,22 @@ enum PipeReason {
   PIPE_ONE_SLICE,      // the batch is one slice
 };
 
+// What the last HARQ round latched, as the next round's decode reads it: G the
+// round's groups (0: nothing latched), raw the host's copy of Harq::skip ([G]
+// latch flags; indexed: then [G] decoder flags and {M, A} of
+// k_harq_repack_index).  indexed is cleared when lte_plan_set_harq_repack
+// changes the setting: the round under way continues on the latch's flags.
+// Invariant (run_siso sets G and indexed after raw is sized and its copy is
+// queued): raw holds at least G words, and 2G + 2 while indexed.
+struct HarqRound {
+  int G = 0;
+  bool indexed = false;
+  std::vector<uint32_t> raw;
+  bool finished(int g) const { return raw[g] != 0; }
+  int64_t M() const { return raw[2 * (size_t)G]; }
+  int64_t A() const { return raw[2 * (size_t)G + 1]; }
+};
+
 struct Plan {
   lte_plan_desc d;
   int L, n_sym, Nd, Np, n_grp, nblk, PW, C = 0, KWmax = 0, EW = 0, enc_words = 0;
@@ -217,52 +275,52 @@ struct Plan {
   DBuf<int64_t> rows_dev;
   DBuf<uint32_t*> dec_ptrs;
   DBuf<int> kw_dev;
-  // CRC early termination (lte_plan_set_early_stop): per CB slot the iterations
-  // used [G][64] words; es_frames: frames of the last decoded run (0: none yet)
-  bool early_stop = false;
-  std::vector<DBuf<uint32_t>> es_used;
-  int es_frames = 0;
-  // Re-packing of the undecided blocks (lte_plan_set_early_stop_repack): the
-  // boundary (0: off); per CB slot the packed decision words [cap][kw][64],
-  // counts [cap][64] and source indices [cap * 64] (the packed rows and
-  // checkpoints are ChainBufs' pk_blk / pk_ckpt), cap = turbo_pack_cap of the
-  // plan's groups; rp_cnt: the slots' undecided counts; rp_last: the last
-  // run's (undecided, groups resumed, state) per slot
-  int repack_after = 0;
-  std::vector<DBuf<uint32_t>> pk_decb, pk_used, pk_idx;
-  DBuf<uint32_t> rp_cnt;
-  std::vector<int64_t> rp_last;
+  // The decoder options (all opt-in; DESIGN.md §5 / §5a, HARQ section).
+  // CRC early termination (lte_plan_set_early_stop).  used: per CB slot the
+  // iterations used [G][64] words; frames: frames of the last decoded run (0:
+  // none yet).  Re-packing of the undecided blocks
+  // (lte_plan_set_early_stop_repack): repack_after the boundary (0: off), the
+  // packed set is ChainBufs::pk (counts and an index per slot); rp_cnt: the
+  // slots' undecided counts; rp_last: the last run's (undecided, groups
+  // resumed, state) per slot
+  struct EarlyStop {
+    bool on = false;
+    std::vector<DBuf<uint32_t>> used;
+    int frames = 0;
+    int repack_after = 0;
+    DBuf<uint32_t> rp_cnt;
+    std::vector<int64_t> rp_last;
+  } es;
   // Extrinsic scaling of the decoders (lte_plan_set_turbo_scale): 1 = off
-  double turbo_scale = 1.0;
+  struct ExtScale { double ext = 1.0; bool on() const { return ext != 1.0; } } scale;
   // HARQ (lte_plan_create_harq).  tx_map / rx_map hold one map per distinct rv
-  // of rv_seq back to back (n_re_bits entries each, hq_slot[rv] its index).
-  // hq_round: the next lte_run's transmission; hq_done: last completed round
-  // (-1: none in this process); hq_fids: round 0's frame ids.  Per frame
-  // [max_frames]: tx_used, latched errors / verdict (a passing verdict is the
-  // acknowledgement); hq_skip [G]: 1 = every frame of the group is acknowledged
-  // (k_harq_latch)
-  bool harq = false;
-  lte_harq_desc hq{};
-  int hq_slot[4] = {0, 0, 0, 0};
-  int hq_round = 0, hq_done = -1;
-  int hq_last[3] = {-1, 0, 0};       // last run: round, rv, decoder groups skipped
-  std::vector<uint64_t> hq_fids;
-  DBuf<uint32_t> hq_tx_used, hq_err, hq_crc, hq_skip;
-  std::vector<uint32_t> hq_skip_h;   // hq_skip after the last round
-  DBuf<int32_t> hq_zmap;             // decoder input rows (r << 24 | row) rv_seq[0]'s map leaves unwritten
-  int hq_nz = 0;
-  // Re-packing of the unacknowledged frames (lte_plan_set_harq_repack).  While
-  // it is on, hq_skip holds [G] k_harq_latch's flags, [G] k_harq_repack_index's
-  // decoder flags (finished or mixed) and {M, A} (G = the round's groups), and
-  // hq_skip_h is that whole array; hq_rp_G: the groups of the last round that
-  // indexed (-1: none since round 0 opened / the setting changed).  The packed
-  // arrays are early-stop re-packing's (pk_blk / pk_ckpt, pk_decb; pk_idx[0]
-  // the frame index); hq_rp_last: the last run's (state, M, A, P, waves).  A
-  // round that packs decodes the packed groups on pipe->dec[0] (made on first
-  // use; a HARQ plan never runs the coded pipeline)
-  bool hq_repack = false;
-  int hq_rp_G = -1;
-  int64_t hq_rp_last[5] = {0, 0, 0, 0, 0};
+  // of rv_seq back to back (n_re_bits entries each, slot[rv] its index).
+  // round: the next lte_run's transmission; done: last completed round (-1:
+  // none in this process); fids: round 0's frame ids.  Per frame [max_frames]:
+  // tx_used, latched errors / verdict (a passing verdict is the
+  // acknowledgement).  skip: [G] k_harq_latch's flags (1 = every frame of the
+  // group is acknowledged) and, once re-packing has been switched on, room for
+  // [G] k_harq_repack_index's decoder flags (finished or mixed) and {M, A}
+  // behind them (G = the round's groups); latched: the host's copy.
+  // Re-packing of the unacknowledged frames (lte_plan_set_harq_repack): the
+  // packed set is ChainBufs::pk (no counts, idx[0] the one frame index);
+  // rp_last: the last run's (state, M, A, P, waves).  A round that packs
+  // decodes the packed groups on pipe->dec[0] (made on first use; a HARQ plan
+  // never runs the coded pipeline)
+  struct Harq {
+    bool on = false;
+    lte_harq_desc desc{};
+    int slot[4] = {0, 0, 0, 0};
+    int round = 0, done = -1;
+    int last[3] = {-1, 0, 0};        // last run: round, rv, decoder groups skipped
+    std::vector<uint64_t> fids;
+    DBuf<uint32_t> tx_used, err, crc, skip;
+    HarqRound latched;
+    DBuf<int32_t> zmap;              // decoder input rows (r << 24 | row) rv_seq[0]'s map leaves unwritten
+    int nz = 0;
+    bool repack = false;
+    int64_t rp_last[5] = {0, 0, 0, 0, 0};
+  } hq;
   // the chain's row of lte_chain.h (plan_create); mimo / bf: its family is run_mimo's / run_bf's
   const ChainTraits* ct = nullptr;
   bool mimo = false, bf = false;

@@ -723,16 +723,11 @@ static int turbo_host_run(int K, int iters, int64_t ncb, const T* llr, const T* 
       dbits.alloc((size_t)G * KW * 64) || (es_used && dused.alloc((size_t)G * 64)))
     return fail(LTE_ENOMEM, "turbo buffers");
   // re-packing: the packed set of the one job
-  DBuf<T> pb, pck;
-  DBuf<uint32_t> pbits, pused, pidx, pcnt;
-  const int cap = turbo_pack_cap(G);
-  if (rp_after > 0 &&
-      (pb.alloc((size_t)turbo_galloc(cap) * rows * 64) ||
-       pck.alloc((size_t)turbo_galloc(cap) * turbo_nwin(K) * turbo_ck_rows(f64) * 64) ||
-       pbits.alloc((size_t)cap * KW * 64) || pused.alloc((size_t)cap * 64) || pidx.alloc((size_t)cap * 64) ||
-       pcnt.alloc(1)))
+  PackSet<T> pset;
+  DBuf<uint32_t> pcnt;
+  if (rp_after > 0 && (pcnt.alloc(1) || !pset.alloc(turbo_pack_cap(G), {CbInfo{K}}, true, 1)))
     return fail(LTE_ENOMEM, "turbo re-packing buffers");
-  const TurboPack pk{pb.p, pck.p, pbits.p, pused.p, pidx.p, cap};
+  const TurboPack pk = rp_after > 0 ? pset.pack(0) : TurboPack{};
   int rc = LTE_OK;
   std::vector<uint32_t> hb((size_t)G * KW * 64);
   const TurboJob job{db.p, dck.p, dbits.p, K, f1, f2, G, ch};

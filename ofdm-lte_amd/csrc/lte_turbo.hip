@@ -239,113 +239,57 @@ int launch_harq_latch(hipStream_t s, int B, int t, uint32_t* frame_err, uint32_t
 // Re-packing of the unacknowledged frames (opt-in, lte_plan_set_harq_repack;
 // DESIGN.md §5a).  A group is finished (no lane active), full (every valid
 // lane active) or mixed; the active frames of the mixed groups are decoded in
-// dense packed groups instead of one wave per mixed group.
+// dense packed groups instead of one wave per mixed group.  The kernels'
+// bodies are the shared ones of lte_internal.h (repack_rank, repack_gather,
+// repack_scatter), as early-stop re-packing's in lte_decoder.hip.
 //
-// k_harq_repack_index, one 1024-thread block after k_harq_latch: as
-// k_repack_index (lte_decoder.hip), wave w owns a contiguous run of groups,
-// counts its run (ballot + popcount per group), the 16 run totals are
-// prefix-summed and a second walk ranks every active lane of a mixed group --
-// no atomics, so idx is in ascending frame order on every run.  idx[rank] =
-// frame for rank < cap_lanes; flags[g] = 1 for a finished or mixed group (what
-// the skip-aware decoders leave out in a round that packs); ma = {M, A}, the
-// mixed groups and their active frames, whether they fit or not.
-constexpr int HRP_WAVES = 16;
-__global__ __launch_bounds__(64 * HRP_WAVES) void k_harq_repack_index(const uint32_t* __restrict__ l_crc, int B,
-                                                                      uint32_t* __restrict__ idx, int cap_lanes,
-                                                                      uint32_t* __restrict__ flags,
-                                                                      uint32_t* __restrict__ ma) {
-  __shared__ int tot_m[HRP_WAVES], tot_a[HRP_WAVES];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int G = (B + 63) / 64;
-  const int per = (G + HRP_WAVES - 1) / HRP_WAVES;
-  const int g0 = min(G, w * per), g1 = min(G, g0 + per);
-  int m = 0, n = 0;
-  for (int g = g0; g < g1; ++g) {
-    const int b = g * 64 + lane;
-    const bool act = b < B && l_crc[b] == 0;
-    const int active = __builtin_popcountll(__builtin_amdgcn_ballot_w64(act));
-    const bool mixed = active > 0 && active < min(64, B - g * 64);
-    m += mixed ? 1 : 0;
-    n += mixed ? active : 0;
-  }
-  if (lane == 0) {
-    tot_m[w] = m;
-    tot_a[w] = n;
-  }
-  __syncthreads();
-  int base = 0, all_m = 0, all_a = 0;
-  for (int i = 0; i < HRP_WAVES; ++i) {
-    if (i < w) base += tot_a[i];
-    all_m += tot_m[i];
-    all_a += tot_a[i];
-  }
+// k_harq_repack_index, one 1024-thread block after k_harq_latch: the active
+// frames of the mixed groups in ascending order.  idx[rank] = frame for rank <
+// cap_lanes; flags[g] = 1 for a finished or mixed group (what the skip-aware
+// decoders leave out in a round that packs); ma = {M, A}, the mixed groups and
+// their active frames, whether they fit or not.
+__global__ __launch_bounds__(64 * REPACK_WAVES) void k_harq_repack_index(const uint32_t* __restrict__ l_crc, int B,
+                                                                         uint32_t* __restrict__ idx, int cap_lanes,
+                                                                         uint32_t* __restrict__ flags,
+                                                                         uint32_t* __restrict__ ma) {
+  const int lane = threadIdx.x & 63;
+  const RepackTotals all = repack_rank(
+      (B + 63) / 64,
+      [&](int g) {
+        const int b = g * 64 + lane;
+        const uint64_t act = __builtin_amdgcn_ballot_w64(b < B && l_crc[b] == 0);
+        const int n = __builtin_popcountll(act);
+        return RepackMask{act, n > 0 && n < min(64, B - g * 64) ? act : 0ull};   // mixed groups only
+      },
+      [&](int g, RepackMask m, int rank) {
+        if (lane == 0) flags[g] = (m.seen == 0ull || m.take != 0ull) ? 1u : 0u;
+        if (((m.take >> lane) & 1ull) && rank < cap_lanes) idx[rank] = (uint32_t)(g * 64 + lane);
+      });
   if (threadIdx.x == 0) {
-    ma[0] = (uint32_t)all_m;
-    ma[1] = (uint32_t)all_a;
-  }
-  for (int g = g0; g < g1; ++g) {
-    const int b = g * 64 + lane;
-    const bool act = b < B && l_crc[b] == 0;
-    const uint64_t mask = __builtin_amdgcn_ballot_w64(act);
-    const int active = __builtin_popcountll(mask);
-    const bool mixed = active > 0 && active < min(64, B - g * 64);
-    if (lane == 0) flags[g] = (active == 0 || mixed) ? 1u : 0u;
-    if (!mixed) continue;
-    const int rank = base + __builtin_popcountll(mask & ((1ull << lane) - 1ull));
-    if (act && rank < cap_lanes) idx[rank] = (uint32_t)b;
-    base += active;
+    ma[0] = (uint32_t)all.groups;
+    ma[1] = (uint32_t)all.lanes;
   }
 }
 
 int launch_harq_repack_index(hipStream_t s, const uint32_t* l_crc, int B, uint32_t* idx, int cap_lanes,
                              uint32_t* flags, uint32_t* ma) {
   if (B < 1 || cap_lanes < 64) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_harq_repack_index, dim3(1), dim3(64 * HRP_WAVES), 0, s, l_crc, B, idx, cap_lanes, flags, ma);
+  hipLaunchKernelGGL(k_harq_repack_index, dim3(1), dim3(64 * REPACK_WAVES), 0, s, l_crc, B, idx, cap_lanes, flags, ma);
   return (int)hipGetLastError();
 }
 
-// Row i of the 3K + 12 decoder input rows in dematch order (LS with decoder
-// 1's tail, LP1, LP2, LS2T) -> its row in a block.  These are the rows the
-// fixed decoder reads before it writes: the first decoder-1 pass takes a zero
-// a priori and stores every LE row before a later pass loads it, and the
-// checkpoints are written before they are read, so LE and the checkpoints of
-// a packed group need no copy.
-__host__ __device__ inline int64_t harq_input_row(int K, int i) {
-  if (i < K + 3) return trow_ls(K, i);
-  if (i < 2 * K + 6) return trow_lp(K, 1, i - (K + 3));
-  if (i < 3 * K + 9) return trow_lp(K, 2, i - (2 * K + 6));
-  return trow_ls2t(K, i - (3 * K + 9));
-}
-
-// k_harq_repack_gather, k_repack_gather's shape: block (j, y) fills packed
-// group j's input rows [y * HRP_ROWS, (y + 1) * HRP_ROWS), four waves taking
-// every fourth.  Lane l reads frame idx[j * 64 + l]'s element of the row in
-// the source arrays (chunk width sch) and the wave stores one whole row of the
-// packed arrays (chunk width dch); lanes past n store zeros.
-constexpr int HRP_ROWS = 64;
+// k_harq_repack_gather: the 3K + 12 decoder input rows (harq_input_row) only
 template <class T>
 __global__ __launch_bounds__(256) void k_harq_repack_gather(const T* __restrict__ src, int sch, T* __restrict__ dst,
                                                             int dch, int K, const uint32_t* __restrict__ idx, int n) {
-  const int j = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int d = j * 64 + lane;
-  const bool on = d < n;
-  const uint32_t sidx = on ? idx[d] : 0u;
-  const int64_t sg = sidx >> 6;
-  const int sl = (int)(sidx & 63u);
-  const int64_t rows = turbo_rows(K);
-  const int i1 = min(3 * K + 12, ((int)blockIdx.y + 1) * HRP_ROWS);
-  for (int i = blockIdx.y * HRP_ROWS + w; i < i1; i += 4) {
-    const int64_t row = harq_input_row(K, i);
-    const T v = on ? src[turbo_elem_ch(sch, rows, sg, row) + sl] : (T)0;
-    dst[turbo_elem_ch(dch, rows, j, row) + lane] = v;
-  }
+  repack_gather<T, true>(src, sch, dst, dch, K, idx, n, nullptr);
 }
 
 template <class R>
 int launch_harq_repack_gather(hipStream_t s, const R* src, int sch, R* dst, int dch, int K, const uint32_t* idx,
                               int n) {
   if (n < 1 || K < 8) return (int)hipErrorInvalidValue;
-  const dim3 grid((n + 63) / 64, (3 * K + 12 + HRP_ROWS - 1) / HRP_ROWS);
+  const dim3 grid((n + 63) / 64, (3 * K + 12 + RPK_ROWS - 1) / RPK_ROWS);
   hipLaunchKernelGGL(k_harq_repack_gather<R>, grid, dim3(256), 0, s, src, sch, dst, dch, K, idx, n);
   return (int)hipGetLastError();
 }
@@ -353,17 +297,11 @@ template int launch_harq_repack_gather<float>(hipStream_t, const float*, int, fl
 template int launch_harq_repack_gather<double>(hipStream_t, const double*, int, double*, int, int, const uint32_t*,
                                                int);
 
-// k_harq_repack_scatter: the packed groups' decision words ([P][kw][64]) back
-// to the frames' own (group, lane) words; one thread per packed frame.
+// k_harq_repack_scatter: the packed decision words back to the frames' own (no counts)
 __global__ __launch_bounds__(64) void k_harq_repack_scatter(const uint32_t* __restrict__ pbits,
                                                             const uint32_t* __restrict__ idx, int n, int kw,
                                                             uint32_t* __restrict__ bits) {
-  const int j = blockIdx.x, lane = threadIdx.x;
-  const int d = j * 64 + lane;
-  if (d >= n) return;
-  const uint32_t sidx = idx[d];
-  const size_t sg = sidx >> 6, sl = sidx & 63u;
-  for (int w = 0; w < kw; ++w) bits[(sg * kw + w) * 64 + sl] = pbits[((size_t)j * kw + w) * 64 + lane];
+  repack_scatter(pbits, nullptr, idx, n, kw, bits, nullptr);
 }
 
 int launch_harq_repack_scatter(hipStream_t s, const uint32_t* pbits, const uint32_t* idx, int n, int kw,

@@ -103,16 +103,18 @@ def make_plan(C, tb, prec, max_frames, repack, scale=None):
                      harq=dict(max_tx=MAX_TX, rv_seq=RV, coded_bits=TBS[tb]['G']), harq_repack=repack)
 
 
+def one_round(plan, t, snrs, capture=('bits_rx',), **kw):
+    """Round t of the process, its results copied."""
+    plan.harq_round(t)
+    r = plan.run(snrs, capture=capture, **kw)
+    d = {k: np.array(r[k]) for k in KEYS + tuple(capture)}
+    d.update(path=dict(r.path), harq_info=r['harq_info'], info=r.get('harq_repack_info'))
+    return d
+
+
 def rounds(plan, snrs, capture=('bits_rx',), **kw):
     """The process's four rounds, each round's results copied."""
-    out = []
-    for t in range(MAX_TX):
-        plan.harq_round(t)
-        r = plan.run(snrs, capture=capture, **kw)
-        d = {k: np.array(r[k]) for k in KEYS + tuple(capture)}
-        d.update(path=dict(r.path), harq_info=r['harq_info'], info=r.get('harq_repack_info'))
-        out.append(d)
-    return out
+    return [one_round(plan, t, snrs, capture, **kw) for t in range(MAX_TX)]
 
 
 def both(C, tb, prec, max_frames, snrs, capture=('bits_rx',), scale=None, **kw):
@@ -318,6 +320,60 @@ def test_a_second_process_starts_clean(C, monkeypatch):
         for k in KEYS:
             assert np.array_equal(off[t][k], new[t][k]), (t, k)
         assert off[t]['harq_info'] == new[t]['harq_info']
+
+
+def test_setting_changed_between_rounds(C, oracle, monkeypatch):
+    """The setting changed between rounds of a process under way, on a plan made
+    with it off.  Switched on after round 1 (first use: the packed arrays are
+    allocated and the latch's flags move), round 2 has no index yet and runs in
+    place on the flags alone, round 3 follows the rule on round 2's verdicts; a
+    second process switches off again after round 2.  Every round of both equals
+    the process that never had the setting."""
+    from lte_phy import engine
+    clear_switches(monkeypatch)
+    tb, max_frames, _ = CASES['partly']
+    bits, snrs = inputs('partly')
+    off, _, _, cap = case_runs(C, oracle, 'partly', 'f64')
+    B = len(snrs)
+    G = -(-B // 64)
+    for back_off in (False, True):
+        engine.clear_cache()
+        plan = make_plan(C, tb, 'f64', max_frames, False)
+        got = []
+        for t in range(MAX_TX):
+            if t == 2:
+                plan.set_harq_repack(True)
+            if t == 3 and back_off:
+                plan.set_harq_repack(False)
+            got.append(one_round(plan, t, snrs, seed=tb, bits=bits))
+        for t in range(MAX_TX):
+            a, b = off[t], got[t]
+            tag = (back_off, t)
+            for k in KEYS:
+                assert np.array_equal(a[k], b[k]), (tag, k)
+            assert a['harq_info'] == b['harq_info'], tag
+            active = got[t - 1]['crc_ok'] == 0 if t else np.ones(B, dtype=bool)
+            assert np.array_equal(a['bits_rx'][active], b['bits_rx'][active]), tag
+        for t in (0, 1):
+            assert got[t]['info'] is None and 'harq_repack' not in got[t]['path'], (back_off, t)
+        # right after switching on: no index exists yet
+        info, prev = got[2]['info'], got[1]['crc_ok']
+        finished = sum(1 for g in range(G) if prev[g * 64:(g + 1) * 64].all())
+        assert got[2]['path']['harq_repack'] == '1' and info['on'] and info['cap'] == cap, (back_off, info)
+        assert (info['state'], info['M'], info['A'], info['P']) == ('in_place', 0, 0, 0), (back_off, info)
+        assert finished >= 1 and info['waves'] == G - finished, (back_off, info, finished)
+        if back_off:
+            assert got[3]['info'] is None and 'harq_repack' not in got[3]['path']
+            continue
+        # the next round: the rule's numbers on round 2's verdicts
+        info, prev = got[3]['info'], got[2]['crc_ok']
+        want = C.harq_repack_rule(prev, cap)
+        assert want == RM.rule(prev, cap)
+        assert got[3]['path']['harq_repack'] == '1'
+        assert (info['M'], info['A'], info['P']) == (want['M'], want['A'], want['P']), (info, want)
+        assert info['state'] == ('packed' if want['pack'] else 'in_place') and info['waves'] == want['waves_on'], \
+            (info, want)
+        assert want['pack'] and info['P'] == PACKS['partly']     # (the case is built to pack)
 
 
 def test_a_packed_round_runs_under_the_existing_timers(C, monkeypatch):
